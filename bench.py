@@ -5,7 +5,11 @@ A "step" = the linear-algebra work of one Ipopt iteration on one KKT system: ONE
 factorisation (with inertia) + TWO triangular solves (the solve and the forced refinement step,
 reference IpPDFullSpaceSolver.cpp:40-47,256-346), values and right-hand side already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line.  --dump-outputs DIR writes what the last timed step
+computed (the solution, the inertia) as DIR/<name>.npy.  --full adds everything beside the headline figure: the host-buffer
+step, the per-kernel roofline, the other single-GPU configurations (`also`), the CPU baseline and the end-to-end Ipopt runs.
 
 Workloads (synthetic data of the named shape, inertia known by construction -- tests/support/kktgen.py):
     lukvle1_1e4   BASELINE.json configs[1]: KKT of ScalableProblems LukVlE1 n=10 000 (dim 19 998, triplet nnz 69 991)
@@ -13,8 +17,8 @@ Workloads (synthetic data of the named shape, inertia known by construction -- t
     grid_1e5      PDE-constrained-like KKT, 160x125 grid, 3 dof + 2 constraints per node (CI-sized sibling of configs[3])
     synth_1e6     BASELINE.json configs[3]: n = 10^6, nnz ~ 2e7 (500x400 grid, 3 dof + 2 constraints per node)
 Default: synth_1e6 at every N -- BASELINE.json quotes the GFLOP/s metric on the synthetic n = 10^6 system "at 1, 2, 4 and 8
-GPUs"; it fits one GPU, and the driver's scaling efficiency needs the same workload at every N.  The N=1 line also carries
-the LukVlE1 configurations (configs[1] and the 10^6-variable target) under "also".
+GPUs"; it fits one GPU, and the driver's scaling efficiency needs the same workload at every N.  With --full the N=1 line also
+carries the LukVlE1 configurations (configs[1] and the 10^6-variable target) under "also".
 
 Prints ONE JSON line (rank 0).  value = algorithmic GFLOP/s of factor + 2 solves, flop counts as defined
 in SURVEY 8(d): F_fact = sum_j (c_j-1)(c_j+2), F_solve = 4 nnz(L) - 3 n per rhs, for the ordering actually used.
@@ -260,17 +264,36 @@ def e2e_block(problem="LukVlE1", size=1000000, cpu_threads=None):
         return {"error": str(e)[:300]}
 
 
+def dump_outputs(d, arrays, limit=32 << 20):
+    """DIR/<name>.npy (float64) for every output array; an array of more than `limit` bytes (a recorded system of more than 4 * 10^6
+    unknowns) is written as a fixed, seeded sample of its elements, their indices in DIR/<name>_index.npy."""
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64).ravel()
+        if a.nbytes > limit:
+            idx = np.sort(np.random.default_rng(20260923).choice(a.size, size=limit // 16, replace=False))
+            np.save(os.path.join(d, f"{name}_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(d, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="auto")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (solution, inertia) as DIR/<name>.npy (single GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the host-buffer step, the per-kernel roofline, the other configurations, the CPU baseline and the end-to-end runs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) no CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="(with --full) no other configurations")
+    ap.add_argument("--no-e2e", action="store_true", help="(with --full, or --gpus N) no end-to-end Ipopt runs")
     ap.add_argument("--e2e-only", default="", help="PROBLEM:SIZE[:threads,...] -- print only the end-to-end block of that ScalableProblems instance (e.g. MBndryCntrl1:700:1,16)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or "WORLD_SIZE" in os.environ or os.environ.get("MI355X_KKT_FORCE_MULTI")):
+        raise SystemExit("--dump-outputs: single-GPU runs only")
     if args.e2e_only:
         f = args.e2e_only.split(":")
         thr = [int(t) for t in f[2].split(",")] if len(f) > 2 else None
@@ -313,10 +336,10 @@ def main():
         st, nneg, nzero = s.factor_device(dv.data_ptr())
         for _ in range(NSOLVE):
             s.solve_device2(db.data_ptr(), dx.data_ptr())
-        return st, nneg
+        return st, nneg, nzero
 
     for _ in range(max(args.warmup, 1)):
-        st, nneg = step()
+        st, nneg, _ = step()
     assert st == 0 and nneg == neg, f"inertia {nneg} != {neg} (status {st})"
     x = dx.cpu().numpy()
     res = float(np.abs(K @ x - b).max() / (abs(K).sum(axis=1).max() * np.abs(x).max() + np.abs(b).max()))
@@ -324,93 +347,14 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:       # what a caller of the timed path receives from its last step: the solution and (status, num_neg, num_zero)
+        dump_outputs(args.dump_outputs, {"x": dx.cpu().numpy(), "inertia": np.array(last, dtype=np.float64)})
     flops_step = I.flops_factor + NSOLVE * I.flops_solve
     bytes_step = I.bytes_factor + NSOLVE * I.bytes_solve
     J = s.info()
-    # the same step through the reference's HOST-buffer contract (GetValuesArrayPtr + MultiSolve on host arrays,
-    # IpSparseSymLinearSolverInterface.hpp:155,190): values copied into the pinned staging buffer, right-hand sides pageable,
-    # PCIe both ways.  Reported next to `value`, never as `value`.
-    tfill = [0.0]
-    def host_step():
-        tf = time.perf_counter()
-        s.values()[:] = v                                  # (what TripletHelper::FillValues does in Ipopt: host work, timed apart)
-        xh = b.copy(); xh2 = b.copy()
-        tfill[0] += time.perf_counter() - tf
-        s.multi_solve(True, xh, True, neg)
-        s.multi_solve(False, xh2)
-    host_step()
-    hreps = max(3, min(args.steps, 10))
-    tfill[0] = 0.0
-    t0 = time.perf_counter()
-    for _ in range(hreps):
-        host_step()
-    dth_all = (time.perf_counter() - t0) / hreps
-    dth = dth_all - tfill[0] / hreps
-
-    # ---- roofline of the dominant kernel: hip events around every launch (eager), averaged over reps ----
-    reps = 5
-    prof = s.profile(reps)
-    work = per_kind_work(s)
-    per_rep = {kname: (ms / reps, ln // reps) for kname, (ms, ln) in prof.items() if ln > 0}
-    # the solve kinds run once per profile rep; a step has NSOLVE solves
-    weight = {kname: (NSOLVE if (kname.startswith("fwd") or kname.startswith("bwd") or kname == "solve_perm") else 1) for kname in per_rep}
-    dom = max(per_rep, key=lambda kname: per_rep[kname][0] * weight[kname])
-    dms, dlaunch = per_rep[dom]
-    w = work.get(dom, dict(bytes=0, flops=0))
-    if dom == "big_schur":
-        roof = schur_roofline(w, dms)
-    else:
-        ach = w["bytes"] / (dms * 1e-3) / 1e9
-        kn = {"front_wave": "k_front_dpp16 + k_front_reg<64,2|4>", "front_lds64": "k_front_reg<64,8>", "front_lds128": "k_front_reg<256,6|8>(fast + strict)", "big_diag": "k_big_diag_reg<4> / k_grp_fused / k_big_diag_trsm",
-              "fwd_wave": "k_fwd<64,false>", "bwd_wave": "k_bwd<64,false>", "fwd_lds": "k_fwd<*,false>", "bwd_lds": "k_bwd<*,false>",
-              "fwd_big": "k_fwd_grp", "bwd_big": "k_bwd_grp", "fwd_big_upd": "k_fwd_grp_upd", "bwd_big_dot": "k_bwd_grp_dot"}.get(dom, "k_" + dom)
-        roof = dict(bound="hbm", kernel=kn, achieved=ach, peak=HBM_PEAK_GBS, unit="GB/s", frac=ach / HBM_PEAK_GBS)
-    roof.update(launches_per_factor_solve=dlaunch, avg_launch_us=1e3 * dms / max(dlaunch, 1),
-                algorithmic_bytes_per_launch=w["bytes"] / max(dlaunch, 1), algorithmic_flops_per_launch=w["flops"] / max(dlaunch, 1), traffic=None)
-    tfile = os.path.join(ROOT, "profiles", "traffic_latest.json")
-    if os.path.exists(tfile):
-        try:
-            tj = json.load(open(tfile))
-            # a cached PMC figure (tools/prof.sh, separate --pmc passes): only valid for the sources it was measured with
-            same_src = tj.get("source_hash") == source_hash()
-            kch = None if same_src else kernel_code_hash(roof["kernel"])
-            if tj.get("workload") == wl and tj.get("kernel") == roof["kernel"] and (same_src or (kch is not None and kch == tj.get("kernel_code_hash"))):
-                roof["traffic"] = tj["hbm_bytes_per_factorisation"] / max(dlaunch, 1)     # per launch, like `achieved`
-                roof["traffic_source"] = ("profiles/traffic_latest.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, same sources: hash %s)" % tj["source_hash"]) if same_src else \
-                    ("profiles/traffic_latest.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE; other sources have changed since, the machine code of %s in the built library "
-                     "is the one measured: kernel_code_hash %s)" % (roof["kernel"], kch))
-            elif tj.get("workload") == wl and tj.get("kernel") == roof["kernel"]:
-                # not emitted as `traffic`: the sources have changed since the PMC passes; reported beside it so that the reader can judge
-                roof["traffic_stale"] = {"value": tj["hbm_bytes_per_factorisation"] / max(dlaunch, 1), "measured_with_source_hash": tj.get("source_hash"),
-                                         "current_source_hash": source_hash(), "note": "PMC figure of tools/prof.sh for an earlier state of ipopt_amd/csrc; rerun tools/prof.sh"}
-        except Exception:
-            pass
-    # the same kernel's time as rocprofv3 --kernel-trace --stats saw it in the TIMED schedule (tools/prof.sh -> profiles/rocprof_latest.json), cached under
-    # the same two keys as the PMC traffic: the hip-event figure above comes from an eager replay without the look-ahead stream
-    rfile = os.path.join(ROOT, "profiles", "rocprof_latest.json")
-    roof["frac_rocprof"] = None
-    if os.path.exists(rfile):
-        try:
-            rj = json.load(open(rfile))
-            same_src = rj.get("source_hash") == source_hash()
-            kch = None if same_src else kernel_code_hash(roof["kernel"])
-            if rj.get("workload") == wl and rj.get("kernel") == roof["kernel"] and (same_src or (kch is not None and kch == rj.get("kernel_code_hash"))):
-                per_f = (w["flops"] if roof["bound"] == "mfma" else w["bytes"])
-                ach_r = per_f / (rj["ms_per_factorisation"] * 1e-3) / (1e12 if roof["bound"] == "mfma" else 1e9)
-                roof["achieved_rocprof"] = ach_r
-                roof["frac_rocprof"] = ach_r / roof["peak"]
-                if "other_roof" in roof:      # (the same rocprof time against the other roof)
-                    o = roof["other_roof"]
-                    o["frac_rocprof"] = (w["flops"] if o["bound"] == "mfma" else w["bytes"]) / (rj["ms_per_factorisation"] * 1e-3) / (1e12 if o["bound"] == "mfma" else 1e9) / o["peak"]
-                roof["rocprof_ms_per_factorisation"] = rj["ms_per_factorisation"]
-                roof["rocprof_source"] = "profiles/rocprof_latest.json (rocprofv3 --kernel-trace --stats of bench.py, " + ("same sources" if same_src else "same machine code of the kernel") + ")"
-        except Exception:
-            pass
-    kernel_ms = {kname: round(ms * weight[kname], 4) for kname, (ms, _) in per_rep.items()}
-
     line = {
         "metric": "KKT factor+solve GFLOP/s (1 numeric LDL^T factorisation + 2 solves per Ipopt iteration)",
         "value": flops_step / dt / 1e9, "unit": "GFLOP/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -420,81 +364,164 @@ def main():
                    "flops_per_solve": I.flops_solve, "solves_per_step": NSOLVE, "ordering": "nested dissection + minimum-degree leaves (own)",
                    "supernodes": I.num_sn, "tree_levels": I.num_levels, "maxfront": I.maxfront, "num_neg": nneg, "scaled_residual": res},
         "algorithmic_GBps": bytes_step / dt / 1e9,
-        "host_buffer_step": {"ms_per_step": dth * 1e3, "value": flops_step / dth / 1e9, "unit": "GFLOP/s",
-                             "fill_of_the_staging_buffers_ms": 1e3 * tfill[0] / hreps,
-                             "what": "same step through the host-buffer boundary Ipopt uses: pinned values upload (8 nnz bytes) + 2 pageable rhs round trips over PCIe; "
-                                     "the caller's fill of the staging buffer (numpy copies here, TripletHelper::FillValues in Ipopt) is reported apart"},
-        "device_ms": {"factor": J.time_factor_ms, "solve": J.time_solve_ms, "by_kernel_per_step": kernel_ms,
-                      "by_kernel_mode": "hip events around every launch of an eager replay of the launch structure that is timed, the look-ahead split of the "
-                                        "largest updates onto the second stream included (its events are recorded on that stream): the times are those of the "
-                                        "TIMED schedule (fused pivot-block + panel-solve launches and the chain-group launches are booked under big_diag)"},
+        "device_ms": {"factor": J.time_factor_ms, "solve": J.time_solve_ms},
         "analyse_s": I.time_analyse,
-        "roofline": roof,
     }
-    if args.workload == "auto" and not args.no_also:
-        # the other single-GPU configurations (same step definition, GPU only); the default line stays on the metric's config
-        also = {}
-        del s, dv, db, dx
-        for w2 in ("lukvle1_1e4", "mbndry1_100", "lukvle1_1e6"):
+    if args.full:       # everything beside the headline figure, measured after the timed steps
+        # the same step through the reference's HOST-buffer contract (GetValuesArrayPtr + MultiSolve on host arrays,
+        # IpSparseSymLinearSolverInterface.hpp:155,190): values copied into the pinned staging buffer, right-hand sides pageable,
+        # PCIe both ways.  Reported next to `value`, never as `value`.
+        tfill = [0.0]
+        def host_step():
+            tf = time.perf_counter()
+            s.values()[:] = v                                  # (what TripletHelper::FillValues does in Ipopt: host work, timed apart)
+            xh = b.copy(); xh2 = b.copy()
+            tfill[0] += time.perf_counter() - tf
+            s.multi_solve(True, xh, True, neg)
+            s.multi_solve(False, xh2)
+        host_step()
+        hreps = max(3, min(args.steps, 10))
+        tfill[0] = 0.0
+        t0 = time.perf_counter()
+        for _ in range(hreps):
+            host_step()
+        dth_all = (time.perf_counter() - t0) / hreps
+        dth = dth_all - tfill[0] / hreps
+
+        # ---- roofline of the dominant kernel: hip events around every launch (eager), averaged over reps ----
+        reps = 5
+        prof = s.profile(reps)
+        work = per_kind_work(s)
+        per_rep = {kname: (ms / reps, ln // reps) for kname, (ms, ln) in prof.items() if ln > 0}
+        # the solve kinds run once per profile rep; a step has NSOLVE solves
+        weight = {kname: (NSOLVE if (kname.startswith("fwd") or kname.startswith("bwd") or kname == "solve_perm") else 1) for kname in per_rep}
+        dom = max(per_rep, key=lambda kname: per_rep[kname][0] * weight[kname])
+        dms, dlaunch = per_rep[dom]
+        w = work.get(dom, dict(bytes=0, flops=0))
+        if dom == "big_schur":
+            roof = schur_roofline(w, dms)
+        else:
+            ach = w["bytes"] / (dms * 1e-3) / 1e9
+            kn = {"front_wave": "k_front_dpp16 + k_front_reg<64,2|4>", "front_lds64": "k_front_reg<64,8>", "front_lds128": "k_front_reg<256,6|8>(fast + strict)", "big_diag": "k_big_diag_reg<4> / k_grp_fused / k_big_diag_trsm",
+                  "fwd_wave": "k_fwd<64,false>", "bwd_wave": "k_bwd<64,false>", "fwd_lds": "k_fwd<*,false>", "bwd_lds": "k_bwd<*,false>",
+                  "fwd_big": "k_fwd_grp", "bwd_big": "k_bwd_grp", "fwd_big_upd": "k_fwd_grp_upd", "bwd_big_dot": "k_bwd_grp_dot"}.get(dom, "k_" + dom)
+            roof = dict(bound="hbm", kernel=kn, achieved=ach, peak=HBM_PEAK_GBS, unit="GB/s", frac=ach / HBM_PEAK_GBS)
+        roof.update(launches_per_factor_solve=dlaunch, avg_launch_us=1e3 * dms / max(dlaunch, 1),
+                    algorithmic_bytes_per_launch=w["bytes"] / max(dlaunch, 1), algorithmic_flops_per_launch=w["flops"] / max(dlaunch, 1), traffic=None)
+        tfile = os.path.join(ROOT, "profiles", "traffic_latest.json")
+        if os.path.exists(tfile):
             try:
-                n2, r2, c2, v2, neg2 = make_workload(w2)
-                s2 = ipopt_amd.KKTSolver(device=0); s2.initialize_structure(n2, r2, c2, vals=v2)
-                K2 = kktgen.to_scipy(n2, r2, c2, v2); b2 = K2 @ np.ones(n2)
-                dv2 = torch.tensor(v2, dtype=torch.float64, device="cuda"); db2 = torch.tensor(b2, dtype=torch.float64, device="cuda"); dx2 = torch.empty_like(db2)
-                torch.cuda.synchronize()
-                def step2():
-                    st_ = s2.factor_device(dv2.data_ptr())
-                    for _ in range(NSOLVE):
+                tj = json.load(open(tfile))
+                # a cached PMC figure (tools/prof.sh, separate --pmc passes): only valid for the sources it was measured with
+                same_src = tj.get("source_hash") == source_hash()
+                kch = None if same_src else kernel_code_hash(roof["kernel"])
+                if tj.get("workload") == wl and tj.get("kernel") == roof["kernel"] and (same_src or (kch is not None and kch == tj.get("kernel_code_hash"))):
+                    roof["traffic"] = tj["hbm_bytes_per_factorisation"] / max(dlaunch, 1)     # per launch, like `achieved`
+                    roof["traffic_source"] = ("profiles/traffic_latest.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, same sources: hash %s)" % tj["source_hash"]) if same_src else \
+                        ("profiles/traffic_latest.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE; other sources have changed since, the machine code of %s in the built library "
+                         "is the one measured: kernel_code_hash %s)" % (roof["kernel"], kch))
+                elif tj.get("workload") == wl and tj.get("kernel") == roof["kernel"]:
+                    # not emitted as `traffic`: the sources have changed since the PMC passes; reported beside it so that the reader can judge
+                    roof["traffic_stale"] = {"value": tj["hbm_bytes_per_factorisation"] / max(dlaunch, 1), "measured_with_source_hash": tj.get("source_hash"),
+                                             "current_source_hash": source_hash(), "note": "PMC figure of tools/prof.sh for an earlier state of ipopt_amd/csrc; rerun tools/prof.sh"}
+            except Exception:
+                pass
+        # the same kernel's time as rocprofv3 --kernel-trace --stats saw it in the TIMED schedule (tools/prof.sh -> profiles/rocprof_latest.json), cached under
+        # the same two keys as the PMC traffic: the hip-event figure above comes from an eager replay without the look-ahead stream
+        rfile = os.path.join(ROOT, "profiles", "rocprof_latest.json")
+        roof["frac_rocprof"] = None
+        if os.path.exists(rfile):
+            try:
+                rj = json.load(open(rfile))
+                same_src = rj.get("source_hash") == source_hash()
+                kch = None if same_src else kernel_code_hash(roof["kernel"])
+                if rj.get("workload") == wl and rj.get("kernel") == roof["kernel"] and (same_src or (kch is not None and kch == rj.get("kernel_code_hash"))):
+                    per_f = (w["flops"] if roof["bound"] == "mfma" else w["bytes"])
+                    ach_r = per_f / (rj["ms_per_factorisation"] * 1e-3) / (1e12 if roof["bound"] == "mfma" else 1e9)
+                    roof["achieved_rocprof"] = ach_r
+                    roof["frac_rocprof"] = ach_r / roof["peak"]
+                    if "other_roof" in roof:      # (the same rocprof time against the other roof)
+                        o = roof["other_roof"]
+                        o["frac_rocprof"] = (w["flops"] if o["bound"] == "mfma" else w["bytes"]) / (rj["ms_per_factorisation"] * 1e-3) / (1e12 if o["bound"] == "mfma" else 1e9) / o["peak"]
+                    roof["rocprof_ms_per_factorisation"] = rj["ms_per_factorisation"]
+                    roof["rocprof_source"] = "profiles/rocprof_latest.json (rocprofv3 --kernel-trace --stats of bench.py, " + ("same sources" if same_src else "same machine code of the kernel") + ")"
+            except Exception:
+                pass
+        kernel_ms = {kname: round(ms * weight[kname], 4) for kname, (ms, _) in per_rep.items()}
+
+        line["host_buffer_step"] = {"ms_per_step": dth * 1e3, "value": flops_step / dth / 1e9, "unit": "GFLOP/s",
+                                    "fill_of_the_staging_buffers_ms": 1e3 * tfill[0] / hreps,
+                                    "what": "same step through the host-buffer boundary Ipopt uses: pinned values upload (8 nnz bytes) + 2 pageable rhs round trips over PCIe; "
+                                            "the caller's fill of the staging buffer (numpy copies here, TripletHelper::FillValues in Ipopt) is reported apart"}
+        line["device_ms"].update(by_kernel_per_step=kernel_ms,
+                                 by_kernel_mode="hip events around every launch of an eager replay of the launch structure that is timed, the look-ahead split of the "
+                                                "largest updates onto the second stream included (its events are recorded on that stream): the times are those of the "
+                                                "TIMED schedule (fused pivot-block + panel-solve launches and the chain-group launches are booked under big_diag)")
+        line["roofline"] = roof
+        if args.workload == "auto" and not args.no_also:
+            # the other single-GPU configurations (same step definition, GPU only); the default line stays on the metric's config
+            also = {}
+            del s, dv, db, dx
+            for w2 in ("lukvle1_1e4", "mbndry1_100", "lukvle1_1e6"):
+                try:
+                    n2, r2, c2, v2, neg2 = make_workload(w2)
+                    s2 = ipopt_amd.KKTSolver(device=0); s2.initialize_structure(n2, r2, c2, vals=v2)
+                    K2 = kktgen.to_scipy(n2, r2, c2, v2); b2 = K2 @ np.ones(n2)
+                    dv2 = torch.tensor(v2, dtype=torch.float64, device="cuda"); db2 = torch.tensor(b2, dtype=torch.float64, device="cuda"); dx2 = torch.empty_like(db2)
+                    torch.cuda.synchronize()
+                    def step2():
+                        st_ = s2.factor_device(dv2.data_ptr())
+                        for _ in range(NSOLVE):
+                            s2.solve_device2(db2.data_ptr(), dx2.data_ptr())
+                        return st_
+                    for _ in range(3):
+                        st2 = step2()
+                    torch.cuda.synchronize(); t1 = time.perf_counter()
+                    for _ in range(20):
+                        step2()
+                    torch.cuda.synchronize(); dt2 = (time.perf_counter() - t1) / 20
+                    x2 = dx2.cpu().numpy(); I2 = s2.info()
+                    res2 = float(np.abs(K2 @ x2 - b2).max() / (abs(K2).sum(axis=1).max() * np.abs(x2).max() + np.abs(b2).max()))
+                    also[w2] = {"kkt_dim": n2, "ms_per_step": dt2 * 1e3, "GFLOP/s": (I2.flops_factor + NSOLVE * I2.flops_solve) / dt2 / 1e9,
+                                "algorithmic_GBps": (I2.bytes_factor + NSOLVE * I2.bytes_solve) / dt2 / 1e9, "num_neg_ok": bool(st2[0] == 0 and st2[1] == neg2),
+                                "scaled_residual": res2, "device_ms": {"factor": I2.time_factor_ms, "solve": I2.time_solve_ms}}
+                    if not args.no_cpu_baseline:      # every configuration carries its own CPU leg (the reference's PARDISO path on the same matrix)
+                        cb2 = cpu_baseline(n2, r2, c2, v2, b2, x2, st2[1], NSOLVE)
+                        also[w2]["cpu_baseline"] = {"ms_per_step": cb2["seconds_per_step"] * 1e3, "cores": cb2["cores"], "kind": cb2["kind"], "ms_per_step_by_threads": cb2["legs"],
+                                                    "parity_vs_gpu": cb2["parity"], "speedup": cb2["seconds_per_step"] / dt2}
+                    if w2 == "mbndry1_100":
+                        also[w2]["what"] = "BASELINE.json configs[2]: the KKT system of the 4th boundary call of the reference's MBndryCntrl1 N = 100 run (tests/golden/mbndry1_100.kktrec)"
+                    if w2 == "lukvle1_1e6":      # the maximum-product matching scaling (the job of MC64) on the device, per factorisation (scaling mode 5)
+                        s2.set_scaling(5)
+                        for _ in range(2):
+                            st5 = s2.factor_device(dv2.data_ptr())
                         s2.solve_device2(db2.data_ptr(), dx2.data_ptr())
-                    return st_
-                for _ in range(3):
-                    st2 = step2()
-                torch.cuda.synchronize(); t1 = time.perf_counter()
-                for _ in range(20):
-                    step2()
-                torch.cuda.synchronize(); dt2 = (time.perf_counter() - t1) / 20
-                x2 = dx2.cpu().numpy(); I2 = s2.info()
-                res2 = float(np.abs(K2 @ x2 - b2).max() / (abs(K2).sum(axis=1).max() * np.abs(x2).max() + np.abs(b2).max()))
-                also[w2] = {"kkt_dim": n2, "ms_per_step": dt2 * 1e3, "GFLOP/s": (I2.flops_factor + NSOLVE * I2.flops_solve) / dt2 / 1e9,
-                            "algorithmic_GBps": (I2.bytes_factor + NSOLVE * I2.bytes_solve) / dt2 / 1e9, "num_neg_ok": bool(st2[0] == 0 and st2[1] == neg2),
-                            "scaled_residual": res2, "device_ms": {"factor": I2.time_factor_ms, "solve": I2.time_solve_ms}}
-                if not args.no_cpu_baseline:      # every configuration carries its own CPU leg (the reference's PARDISO path on the same matrix)
-                    cb2 = cpu_baseline(n2, r2, c2, v2, b2, x2, st2[1], NSOLVE)
-                    also[w2]["cpu_baseline"] = {"ms_per_step": cb2["seconds_per_step"] * 1e3, "cores": cb2["cores"], "kind": cb2["kind"], "ms_per_step_by_threads": cb2["legs"],
-                                                "parity_vs_gpu": cb2["parity"], "speedup": cb2["seconds_per_step"] / dt2}
-                if w2 == "mbndry1_100":
-                    also[w2]["what"] = "BASELINE.json configs[2]: the KKT system of the 4th boundary call of the reference's MBndryCntrl1 N = 100 run (tests/golden/mbndry1_100.kktrec)"
-                if w2 == "lukvle1_1e6":      # the maximum-product matching scaling (the job of MC64) on the device, per factorisation (scaling mode 5)
-                    s2.set_scaling(5)
-                    for _ in range(2):
-                        st5 = s2.factor_device(dv2.data_ptr())
-                    s2.solve_device2(db2.data_ptr(), dx2.data_ptr())
-                    x5 = dx2.cpu().numpy(); I5 = s2.info()
-                    also[w2]["matching_scaling_on_device"] = {
-                        "ms": I5.matching_ms, "auction_rounds": I5.matching_rounds, "unmatched_columns": I5.matching_unmatched, "factor_ms_behind_it": I5.time_factor_ms,
-                        "num_neg_ok": bool(st5[0] == 0 and st5[1] == neg2),
-                        "scaled_residual": float(np.abs(K2 @ x5 - b2).max() / (abs(K2).sum(axis=1).max() * np.abs(x5).max() + np.abs(b2).max())),
-                        "what": "mi355x_kkt_set_scaling(5): Jacobi auction over the symmetric row view (kernels_match.hip.inc), hip events around the whole computation"}
-                    s2.set_scaling(1)
-                del s2, dv2, db2, dx2
-            except Exception as e:      # never lose the main line over the extras
-                also[w2] = {"error": str(e)[:200]}
-        line["also"] = also
-    if not args.no_cpu_baseline:
-        cb = cpu_baseline(n, r, c, v, b, x, nneg, NSOLVE)
-        line["cpu_baseline"] = {"value": flops_step / cb["seconds_per_step"] / 1e9, "unit": "GFLOP/s", "cores": cb["cores"], "kind": cb["kind"],
-                                "sample": cb["sample"], "ms_per_step": cb["seconds_per_step"] * 1e3, "ms_per_step_by_threads": cb["legs"],
-                                "parity_vs_gpu": cb["parity"], "host_cores_available": os.cpu_count()}
-        assert cb["parity"]["inertia_equal"], cb["parity"]
-    if args.workload == "auto" and not args.no_e2e:
-        e2e = e2e_block()
-        if e2e is not None:
-            line["e2e"] = e2e
-        # the CUTEst-style ~10^6 stand-in of BASELINE.json configs[4]: MBndryCntrl1 N = 700 (n = 492 800, m = 490 000, KKT dim 982 800;
-        # reference examples/ScalableProblems/solve_problem.cpp:28-91), CPU leg at 16 MKL threads (one thread takes ~50 s per run)
-        e2e5 = e2e_block("MBndryCntrl1", 700, [min(16, os.cpu_count() or 1)])
-        if e2e5 is not None:
-            line["e2e_config5_standin"] = e2e5
+                        x5 = dx2.cpu().numpy(); I5 = s2.info()
+                        also[w2]["matching_scaling_on_device"] = {
+                            "ms": I5.matching_ms, "auction_rounds": I5.matching_rounds, "unmatched_columns": I5.matching_unmatched, "factor_ms_behind_it": I5.time_factor_ms,
+                            "num_neg_ok": bool(st5[0] == 0 and st5[1] == neg2),
+                            "scaled_residual": float(np.abs(K2 @ x5 - b2).max() / (abs(K2).sum(axis=1).max() * np.abs(x5).max() + np.abs(b2).max())),
+                            "what": "mi355x_kkt_set_scaling(5): Jacobi auction over the symmetric row view (kernels_match.hip.inc), hip events around the whole computation"}
+                        s2.set_scaling(1)
+                    del s2, dv2, db2, dx2
+                except Exception as e:      # never lose the main line over the extras
+                    also[w2] = {"error": str(e)[:200]}
+            line["also"] = also
+        if not args.no_cpu_baseline:
+            cb = cpu_baseline(n, r, c, v, b, x, nneg, NSOLVE)
+            line["cpu_baseline"] = {"value": flops_step / cb["seconds_per_step"] / 1e9, "unit": "GFLOP/s", "cores": cb["cores"], "kind": cb["kind"],
+                                    "sample": cb["sample"], "ms_per_step": cb["seconds_per_step"] * 1e3, "ms_per_step_by_threads": cb["legs"],
+                                    "parity_vs_gpu": cb["parity"], "host_cores_available": os.cpu_count()}
+            assert cb["parity"]["inertia_equal"], cb["parity"]
+        if args.workload == "auto" and not args.no_e2e:
+            e2e = e2e_block()
+            if e2e is not None:
+                line["e2e"] = e2e
+            # the CUTEst-style ~10^6 stand-in of BASELINE.json configs[4]: MBndryCntrl1 N = 700 (n = 492 800, m = 490 000, KKT dim 982 800;
+            # reference examples/ScalableProblems/solve_problem.cpp:28-91), CPU leg at 16 MKL threads (one thread takes ~50 s per run)
+            e2e5 = e2e_block("MBndryCntrl1", 700, [min(16, os.cpu_count() or 1)])
+            if e2e5 is not None:
+                line["e2e_config5_standin"] = e2e5
     print(json.dumps(line))
 
 

@@ -41,9 +41,12 @@ all: $(OUT)/libipopt_ref.so $(OUT)/hs071_cpp $(OUT)/scalable.a $(OUT)/ref_driver
      $(OUT)/libipopt_ref_mi355x.so $(OUT)/ipopt_patched_driver
 
 $(OUT)/mkl/.stamp:
-	mkdir -p $(OUT)/mkl
-	for f in $(MKLDIR)/libmkl_* $(MKLDIR)/libiomp5.so; do ln -sf $$f $(OUT)/mkl/; done
+	$(MAKE) -f $(firstword $(MAKEFILE_LIST)) mkl-links
 	touch $@
+# the links alone: build() re-creates them where oracle/_ref/ arrives as a copy that did not carry links out of the tree
+mkl-links:
+	mkdir -p $(OUT)/mkl
+	for f in $(wildcard $(MKLDIR)/libmkl_* $(MKLDIR)/libiomp5.so); do ln -sf $$f $(OUT)/mkl/; done
 
 $(OUT)/obj/%.o: $(REF)/src/%.cpp
 	@mkdir -p $(dir $@)
@@ -131,4 +134,4 @@ $(OUT)/ipopt_patched_driver: oracle/ref_driver.cpp $(OUT)/libipopt_ref_mi355x.so
 
 clean:
 	rm -rf $(OUT)
-.PHONY: all clean
+.PHONY: all clean mkl-links

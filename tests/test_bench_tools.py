@@ -88,3 +88,23 @@ def test_host_only_model_tools_run_without_a_device():
     assert abs(8.0 * s.info().cb_doubles / 2 ** 30 - tot) <= 0.01
     p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "level_model.py"), "grid_1e5"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0 and "big fronts=" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
+
+
+def test_dump_outputs_writes_float64_and_samples_a_large_array_the_same_way_every_time(tmp_path):
+    """bench.py --dump-outputs: every output as DIR/<name>.npy in float64; an array over the size limit becomes a fixed, seeded sample of its
+    elements with their indices beside it, so that two runs (two builds) can be compared output for output."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    x = np.linspace(0.0, 1.0, 1000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"x": x, "inertia": (0, 7, 0)}, limit=1024)
+    for d in ("a", "b"):
+        assert sorted(os.listdir(tmp_path / d)) == ["inertia.npy", "x.npy", "x_index.npy"]
+    xa, ia = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "a" / "x_index.npy")
+    assert xa.dtype == np.float64 and xa.size == 1024 // 16 and xa.nbytes + ia.nbytes <= 1024
+    assert np.array_equal(xa, x[ia.astype(np.int64)]) and np.all(np.diff(ia) > 0)
+    assert np.array_equal(xa, np.load(tmp_path / "b" / "x.npy")) and np.array_equal(ia, np.load(tmp_path / "b" / "x_index.npy"))
+    assert np.load(tmp_path / "a" / "inertia.npy").tolist() == [0.0, 7.0, 0.0]
+    bench.dump_outputs(str(tmp_path / "c"), {"x": x})
+    assert os.listdir(tmp_path / "c") == ["x.npy"] and np.array_equal(np.load(tmp_path / "c" / "x.npy"), x)

@@ -6,7 +6,7 @@ WL=${1:-synth_1e6}
 KERN=${2:-k_big_schur}        # kernel whose HBM traffic goes to profiles/traffic_latest.json
 OUT=$R/gpurun_out/prof_$WL
 rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python $R/bench.py --workload $WL --steps 20 --no-cpu-baseline --no-also > $OUT/bench_under_trace.json 2> $OUT/trace.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python $R/bench.py --full --workload $WL --steps 20 --no-cpu-baseline --no-also > $OUT/bench_under_trace.json 2> $OUT/trace.log
 find $OUT/trace -name "*kernel_stats*" | head -3
 f=$(find $OUT/trace -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && cp $f $OUT/kernel_stats.csv && head -25 $f
@@ -30,8 +30,8 @@ if sel:
               open("$OUT/rocprof_latest.json", "w"), indent=1)
 PY
 # separate PMC passes (FETCH_SIZE costs 3 TCC slots, WRITE_SIZE 2: one pass each)
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -o pmc -- python $R/bench.py --workload $WL --steps 3 --warmup 1 --no-cpu-baseline --no-also > /dev/null 2> $OUT/pmc_fetch.log
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write -o pmc -- python $R/bench.py --workload $WL --steps 3 --warmup 1 --no-cpu-baseline --no-also > /dev/null 2> $OUT/pmc_write.log
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -o pmc -- python $R/bench.py --full --workload $WL --steps 3 --warmup 1 --no-cpu-baseline --no-also > /dev/null 2> $OUT/pmc_fetch.log
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write -o pmc -- python $R/bench.py --full --workload $WL --steps 3 --warmup 1 --no-cpu-baseline --no-also > /dev/null 2> $OUT/pmc_write.log
 python3 - <<PY
 import csv, glob, collections, json
 def agg(d, name):

@@ -7,8 +7,8 @@ WL=${1:-synth_1e6}
 OUT=$R/gpurun_out/prof_mfma_$WL
 rm -rf $OUT; mkdir -p $OUT
 rocprofv3 --pmc MfmaUtil --kernel-trace --output-format csv -d $OUT/micro -o pmc -- $R/tools/micro/mfma_f64_peak.bin > $OUT/micro.log 2>&1
-rocprofv3 --pmc MfmaUtil --kernel-trace --output-format csv -d $OUT/bench -o pmc -- python $R/bench.py --workload $WL --steps 2 --warmup 1 --no-cpu-baseline --no-also > /dev/null 2> $OUT/bench.log
-rocprofv3 --pmc LDSBankConflict --kernel-trace --output-format csv -d $OUT/lds -o pmc -- python $R/bench.py --workload $WL --steps 2 --warmup 1 --no-cpu-baseline --no-also > /dev/null 2> $OUT/lds.log
+rocprofv3 --pmc MfmaUtil --kernel-trace --output-format csv -d $OUT/bench -o pmc -- python $R/bench.py --full --workload $WL --steps 2 --warmup 1 --no-cpu-baseline --no-also > /dev/null 2> $OUT/bench.log
+rocprofv3 --pmc LDSBankConflict --kernel-trace --output-format csv -d $OUT/lds -o pmc -- python $R/bench.py --full --workload $WL --steps 2 --warmup 1 --no-cpu-baseline --no-also > /dev/null 2> $OUT/lds.log
 python3 - <<PY | tee $OUT/summary.txt
 import csv, glob, collections
 def agg(d):
