@@ -278,6 +278,17 @@ const char* mi355x_kkt_last_error(mi355x_kkt_handle h);
  *  28   the offset (doubles, inside the contribution-block arena) of every front's block as (low, high) halves: 2 * num_sn ints. */
 int  mi355x_kkt_get_symbolic(mi355x_kkt_handle h, int what, int* out, int64_t capacity);
 
+/* ---- launch-plan introspection (host only: works after the analysis, needs no device): the launch plan rank `rank` of `nranks` (the world
+ * size of the analysis) would run.  *count = ints of array `what`; out == NULL only queries the count.  what:
+ *   "level_list" the launch list (entries of the buckets, of the solve units, of the join lists and of the grouped schedules), "tiny16" /
+ *   "tiny_split" / "mid_split" / "big_split" (per level: leading fronts of the sorted single-GPU WAVE / LDS128 / BIG buckets taken by another kernel),
+ *   "<s>.ptr|base|maxm|maxk|last0|last1|allsolo" for schedule <s> = single, local (own subtrees), stage<d> (replicated fronts of exchange step d),
+ *   "lc_ptr" / "lc_fronts" (leaf chains: their fronts, leaf first), "df_runs" ({lv0, lv1, tab0, nlev, nq} per k_front_df run),
+ *   "chain_segs" (9 ints per data-flow sweep segment), "chain_links" ({s, k, koff, fi} per link), "chain_descs" ({link0, nlinks, tail, ktot, s0, init}
+ *   per chain), "join" ({base, count, maxm, who} per kind), "exchange" ({step, glo, gsz, arena doubles, top-rhs doubles} per range),
+ *   "col_owner", "stat_owner", "scalars" {levels, exchange steps, leaf-chain levels, leaf chains, look-ahead, grouped, tfuse fronts, big fronts, stages}. */
+int  mi355x_kkt_get_launch_plan(mi355x_kkt_handle h, int nranks, int rank, const char* what, int* out, int64_t capacity, int64_t* count);
+
 /* ---- measurement: device time per kernel kind (hip events around every launch of an eager, graph-less factor + one
  * solve -- on the stream the kernel is launched on: the look-ahead parts of the largest trailing updates run, and are
  * measured, on the solver's second stream exactly as in a timed factorisation --, accumulated over `reps` repetitions).

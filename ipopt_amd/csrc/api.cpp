@@ -3,6 +3,7 @@
 #include "../../include/mi355x_kkt.h"
 #include "symbolic.h"
 #include "numeric.h"
+#include "launch_plan.h"
 #include "matching_scaling.h"
 #include "comm_shm.h"
 #include "env_knobs.h"
@@ -509,6 +510,48 @@ int mi355x_kkt_get_symbolic(mi355x_kkt_handle h, int what, int* out, int64_t cap
     if ((int64_t)v->size() > cap) { h->err = "get_symbolic: buffer too small"; return MI355X_KKT_FATAL; }
     if (!v->empty()) std::memcpy(out, v->data(), v->size() * sizeof(int));
     return MI355X_KKT_SUCCESS;
+}
+
+/* launch-plan introspection (host only, no device): the plan rank `rank` of `nranks` would run, array `what` (see include/mi355x_kkt.h) */
+int mi355x_kkt_get_launch_plan(mi355x_kkt_handle h, int nranks, int rank, const char* what, int* out, int64_t cap, int64_t* count)
+{
+    if (!h || !what || !count) return MI355X_KKT_FATAL;
+    if (!h->analysed) { h->err = "get_launch_plan: analyse() first"; return MI355X_KKT_FATAL; }
+    if (nranks != std::max(1, h->so.nranks) || rank < 0 || rank >= nranks) { h->err = "get_launch_plan: nranks is the analysis's, 0 <= rank < nranks"; return MI355X_KKT_FATAL; }
+    try {
+        const LaunchPlan P = build_launch_plan(h->sym, plan_inputs_from_env(nranks, rank, nranks > 1, 0));
+        if (!P.error.empty()) { h->err = P.error; return MI355X_KKT_FATAL; }
+        std::vector<int> v;
+        auto put = [&](std::initializer_list<long long> x) { for (long long e : x) v.push_back((int)e); };
+        const std::string w(what);
+        const Sched* sc = w.rfind("single.", 0) == 0 ? &P.single : w.rfind("local.", 0) == 0 ? &P.local : nullptr;
+        if (w.rfind("stage", 0) == 0) { const int d = atoi(w.c_str() + 5); if (d >= 0 && d < (int)P.stage.size()) sc = &P.stage[d]; }
+        const std::string field = sc ? w.substr(w.find('.') + 1) : w;
+        if (sc) {
+            if (field == "ptr") v = sc->ptr; else if (field == "base") put({sc->base}); else if (field == "maxm") v = sc->maxm; else if (field == "maxk") v = sc->maxk;
+            else if (field == "last0") v = sc->last0; else if (field == "last1") v = sc->last1; else if (field == "allsolo") v.assign(sc->allsolo.begin(), sc->allsolo.end());
+            else { h->err = "get_launch_plan: unknown schedule field"; return MI355X_KKT_FATAL; }
+        } else if (w == "scalars") put({P.nlevels, P.ndepth, P.lc_levels, P.lc_nchains, P.la_any, P.grouped, P.ntfuse, P.nbig, (long long)P.stage.size()});
+        else if (w == "level_list") v = P.lvl_list;
+        else if (w == "tiny16") v = P.tiny16;
+        else if (w == "tiny_split") v = P.tiny_split;
+        else if (w == "mid_split") v = P.mid_split;
+        else if (w == "big_split") v = P.big_split;
+        else if (w == "lc_ptr") v = P.lc_ptr;
+        else if (w == "lc_fronts") { for (const LeafLink& K : P.lc_link) v.push_back(K.s); if (P.lc_levels == 0) v.clear(); }
+        else if (w == "df_runs") for (const DfRun& R : P.df_runs) put({R.lv0, R.lv1, R.tab0, R.nlev, R.nq});
+        else if (w == "chain_segs") for (const ChainSeg& G : P.chain_segs) put({G.lv0, G.lv1, G.desc0, G.ndesc, G.nwg_f, G.nwg_b, G.maxtail, G.wgf0, G.wgb0});
+        else if (w == "chain_links") for (const ChainLink& K : P.chl) put({K.s, K.k, K.koff, K.fi});
+        else if (w == "chain_descs") for (const ChainDesc& D : P.chd) put({D.link0, D.nlinks, D.tail, D.ktot, D.s0, D.init});
+        else if (w == "join") for (const JoinList& J : P.join) put({J.base, J.count, J.maxm, J.who});
+        else if (w == "exchange") for (const RangeSeg& G : P.ex.rsegs) put({G.d, G.glo, G.gsz, G.aend - G.abeg, G.tend - G.tbeg});
+        else if (w == "col_owner") v = P.col_owner;
+        else if (w == "stat_owner") v = P.stat_owner;
+        else { h->err = "get_launch_plan: unknown array"; return MI355X_KKT_FATAL; }
+        *count = (int64_t)v.size();
+        if (out) { if ((int64_t)v.size() > cap) { h->err = "get_launch_plan: buffer too small"; return MI355X_KKT_FATAL; } std::copy(v.begin(), v.end(), out); }
+        return MI355X_KKT_SUCCESS;
+    } catch (...) { h->err = "get_launch_plan: unexpected exception"; return MI355X_KKT_FATAL; }
 }
 
 int mi355x_kkt_profile(mi355x_kkt_handle h, int reps, double* ms, int* launches, int capacity)

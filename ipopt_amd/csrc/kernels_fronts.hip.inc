@@ -1196,7 +1196,6 @@ __device__ __forceinline__ void front_lds32_body(const DevView& V, double* G, in
 // and every workgroup takes its virtual workgroups in ascending order, children before parents: no wait can be circular.  Optimistic schedule only (a
 // rejected front raises qstat[4]: the factorisation is repeated level by level with the strict kernels).
 // ================================================================================================
-struct DfLevel { int b0, n16, nb, q0; };      // a level's bucket of one-wavefront fronts: first launch-list entry, fronts of order <= 16 (they come first), all fronts; its first virtual workgroup
 __global__ __launch_bounds__(64) void k_front_df(DevView V, const DfLevel* lv, int nlev, int nq)
 {
     __shared__ double Fs[4][16 * 17];      // (one front of order 17 .. 32 uses the four squares as its 32 x 33 one)

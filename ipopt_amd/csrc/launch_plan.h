@@ -1,0 +1,95 @@
+// launch_plan.h -- the launch plan of the numeric phase: every launch the factorisation and the solves make, and the tables the kernels
+// read, computed on the host from the symbolic structure alone (launch_plan.cpp; no device).  numeric.hip materialises it on the device.
+#pragma once
+#include "symbolic.h"
+#include "kernel_tables.h"
+#include <cstddef>
+#include <string>
+#include <vector>
+
+namespace mi355x {
+
+// what the plan depends on besides the structure: the rank, and the MI355X_KKT_DISABLE / _TUNE settings it reads (env_knobs.h)
+struct PlanInputs {
+    int nranks = 1, rank = 0;
+    bool multi = false;                  // the multi-rank schedule (nranks > 1, or MI355X_KKT_FORCE_MULTI)
+    int verbose = 0;
+    bool chain_solve = true, fuse_dt = true, fastpiv = true, asm_pull = true, leafchain = true, front_df = true, tfuse = true, fuse_upd = true,
+         selfasm = true, grouped = true, xcd_tiles = true, lookahead = true, pair_solve = true, p1_small = true;
+    int la_wgs = 1 << 20, la_min_nt = 8, grp_rbw_max = 8, chain_solve_maxc = 128, fuse_dt_maxwg = 448;
+    long long la_min_tiles = 4000;
+    double fastpiv_floor = 1e-4;         // (0.01 up to r03a: 9 % of the synth_1e6 blocks then took the strict loop and set the pace of their level: 23.1 -> 22.0 ms)
+    // the factor pool in pieces (numeric.hip setup): a linear offset lin of the  L | cb  layout lies at lin + pool_delta[i] from V.L, i = the last
+    // pool_cut <= lin.  Empty: one piece, the identity.
+    std::vector<long long> pool_cut, pool_delta;
+};
+PlanInputs plan_inputs_from_env(int nranks, int rank, bool multi, int verbose);
+
+// buckets (level, class) of the fronts of one schedule and their launch geometry
+struct Sched { std::vector<int> ptr; int base = 0; std::vector<int> maxm, maxk, tiles, tiles64, last0, last1; std::vector<char> allsolo; };   // last0/1: per level, the group-last BIG fronts (solve units)
+// grouped schedule: per level the chain groups whose FIRST link sits there (entries = FrontMeta of the LAST link, sorted by order, split at 1024
+// rows like the BIG buckets), launch geometry, look-ahead tiles
+struct GrpSched { std::vector<int> g0, g1, split, nrb, tiles64, tiles, la1, la2, p1t, la3, nsplit; };      // p1t: 64 x 64 tiles of a split front's part 1, la3: tiles of the fronts not split, nsplit: split fronts (among the large ones)
+// a run of consecutive levels of pure chain links, one data-flow launch per sweep
+struct ChainSeg { int lv0, lv1, desc0, ndesc, nwg_f, nwg_b, maxtail, wgf0, wgb0; };
+// Exchange steps (subtree-to-subcube mapping; the classic replicated top is the case of ONE step): a replicated front is held by a range of
+// ranks; what its children OUTSIDE that range -- subtrees owned by one rank, fronts of a sub-range -- contribute travels through the front's
+// arena square / top-rhs accumulator, written by ONE reporting rank per child (its owner; the first rank of its range) and summed over the
+// ranks, all ranges of one depth in one collective, deepest first.  join[c]: the fronts this rank reports a child of kind c to
+// (c = 0: own subtree roots, c = 1 + d: fronts of its depth-d range) and the code those children carry in ChildMeta::owner.
+struct JoinList { int base = 0, count = 0, maxm = 0, who = -1; };
+struct RangeSeg { int d, glo, gsz; long long abeg, aend, tbeg, tend; };      // the part of a step of every range of ranks [glo, glo + gsz)
+// runs of consecutive tree levels that hold nothing but one-wavefront fronts (order <= 32): one persistent data-flow launch each (k_front_df)
+struct DfRun { int lv0, lv1, tab0, nlev, nq; };
+
+struct ExchangeLayout {
+    std::vector<long long> aoff, troff;                  // per front: its arena square / top-rhs accumulator, or -1
+    std::vector<long long> abeg, aend, tbeg, tend;       // per step: its part of the arena / of the top right-hand sides
+    std::vector<RangeSeg> rsegs;                         // ... and inside a step the part of every range of ranks
+    long long arena_doubles = 0, toprhs_doubles = 0;
+};
+ExchangeLayout exchange_layout(const Symbolic& Sy, int ndepth);
+void comm_plan(const Symbolic& S, int nranks, int rank, bool range_local, std::vector<int>& out6);
+
+struct LaunchPlan {
+    int nlevels = 0;
+    // the launch list (DevView::level_sn, FrontMeta parallel to it): the single-GPU buckets (level_ptr order, each sorted by front order), the
+    // multi-rank schedules and join lists, the single-GPU solve units, the grouped schedules
+    std::vector<int> lvl_list;
+    Sched single;                                        // every front; its buckets are Symbolic::level_ptr
+    int ndepth = 1;
+    Sched local; std::vector<Sched> stage;              // multi-rank: the rank's own subtrees; stage[d]: the replicated fronts of exchange step d it holds
+    std::vector<JoinList> join;
+    ExchangeLayout ex;
+    // single-GPU buckets: leading fronts of order <= 16 (FC_WAVE), <= 96 (FC_LDS128), <= 1024 (FC_BIG)
+    std::vector<int> tiny16, tiny_split, mid_split, big_split, part_tiles[2];
+    std::vector<size_t> mid_lds, reg_lds;                // LDS need of the register-tiled front kernel: the <= 96 part, every (level, class) bucket
+    std::vector<int> wave_kmax, wave_mmax, wave_mmin;
+    bool pair_solve = true;                              // solves of the order <= 32 fronts: two fronts per wavefront (k_fwd_pair / k_bwd_pair)
+    // data-flow solve sweeps
+    std::vector<ChainSeg> chain_segs; std::vector<int> seg_at_lv0, seg_at_lv1;      // level -> segment index (or -1)
+    std::vector<char> in_seg;
+    std::vector<ChainLink> chl; std::vector<ChainDesc> chd; std::vector<int> chwait, wgf, wgb;
+    int ntailflags = 0, ndots = 0;
+    // look-ahead of the group-end trailing updates (single-GPU schedule): per level the grids of the two parts
+    std::vector<int> la_tiles1, la_tiles2; std::vector<char> la_full;
+    bool la_any = false;
+    std::vector<int> tile_tab;                           // XCD-aware tile orders of the large full updates
+    std::vector<char> lv_asm_skip;                       // every big front of the level is a pure in-place chain link: no assembly launch at all
+    std::vector<int> lv_narrow_tiles;                    // > 0: every big front of the level is a chain link with a narrow update; the 64 x 64 tiles of the largest one
+    bool grouped = false;
+    std::vector<GrpSched> grp;                           // [0]: every front (one GPU) / the rank's own subtrees; [1 + d]: replicated fronts of step d
+    std::vector<char> asm_fast_ok; std::vector<int> asmcut;      // per launch-list entry: k_big_assemble2's fast path (children it pulls, 0: not for it); FrontMeta::asmcut (-1: nothing to assemble)
+    int ntfuse = 0, nbig = 0;
+    std::string error;                                   // non-empty: no plan (an internal inconsistency)
+    int lc_levels = 0, lc_nchains = 0;                   // leaf chains: the tree levels below lc_levels are lc_nchains chains of fronts of order <= 16
+    std::vector<int> lc_ptr; std::vector<LeafLink> lc_link;
+    std::vector<DfRun> df_runs; std::vector<int> df_run_at; std::vector<DfLevel> df_tab; std::vector<long long> cbt_off; long long cbt_len = 0;
+    // the tables
+    std::vector<FrontMeta> fmeta; std::vector<ChildMeta> cmeta; std::vector<GroupLink> gtab; std::vector<int> relinv;
+    std::vector<long long> panel_off, cb_off;            // remapped pool offsets
+    std::vector<int> stat_owner, col_owner;
+};
+LaunchPlan build_launch_plan(const Symbolic& Sy, const PlanInputs& in);
+
+} // namespace mi355x

@@ -35,6 +35,7 @@
 #include <string>
 #include <algorithm>
 #include "numeric.h"
+#include "launch_plan.h"
 #include "env_knobs.h"
 #include "matching_scaling.h"
 
@@ -233,52 +234,15 @@ public:
         for (int i = 0; i < S->n; ++i) out[S->perm[i]] = sp[i];
         return true;
     }
-    std::vector<int> big_maxm, big_maxk, big_tiles, big_tiles64, big_last0, big_last1;
-    std::vector<int> lv_narrow_tiles;   // > 0: every big front of the level is a chain link with a narrow update; the 64 x 64 tiles of the largest one
-    std::vector<char> lv_asm_skip;      // every big front of the level is a pure in-place chain link: no assembly launch at all
-    // sync-free chain sweeps: runs of consecutive levels made of pure chain links (single-GPU schedule, per-link solves)
+    PlanInputs knobs;          // the settings the plan was built with (the launch code reads the launch-time ones from here)
+    LaunchPlan P;              // every launch of the factorisation and the solves, and the tables behind them (launch_plan.cpp)
+    // look-ahead events per level with a part 2 (part 1 done on the main stream / part 2 done on the second): [0] the single-GPU schedule, [1 + i] grouped schedule P.grp[i]
+    struct LaEvents { std::vector<hipEvent_t> A, B; };
+    std::vector<LaEvents> la_ev;
+    int grp_step = 0;                          // multi-GPU: the exchange step launch_fronts is working on
     size_t strace_n = 0; struct TraceDesc { int chain, w, nlinks, tail; }; std::vector<TraceDesc> strace_desc;
-    std::vector<char> in_seg;         // fronts handled by the data-flow sweeps
-    struct ChainSeg { int lv0, lv1, desc0, ndesc, nwg_f, nwg_b, maxtail, wgf0, wgb0; };
-    std::vector<ChainSeg> chain_segs; std::vector<int> seg_at_lv0, seg_at_lv1;      // level -> segment index (or -1)
-    bool pair_solve = true; std::vector<int> wave_kmax, wave_mmax, wave_mmin;   // solves of the order <= 32 fronts: two fronts per wavefront (k_fwd_pair / k_bwd_pair); largest pivot count per level
-    bool fuse_dt = true;                               // pivot block + panel solve in one launch where a level has few fronts
-    int fuse_dt_maxwg = 448;                           // ... few = this many workgroups (pivot blocks + 64-row panel blocks) at most
-    bool chain_solve = true; int chain_maxc = 128;       // only where few chains run side by side (the latency-bound top of the tree)
-    std::vector<char> lv_allsolo;       // every big solve unit of the level is one link with nothing to gather (fused forward kernel)
-    std::vector<int> big_split, part_mm[2], part_kk[2], part_tiles[2];   // single-GPU schedule: BIG buckets split at 1024 rows
-    // look-ahead of the group-end trailing updates (single-GPU schedule): per level the grids of the two parts, second stream
-    std::vector<int> la_tiles1, la_tiles2; std::vector<char> la_full;     // la_full: the level has a full (group-last) update
-    // grouped schedule (single GPU): per level the chain groups whose FIRST link sits there (entries = FrontMeta of the LAST link, sorted by
-    // order, split at 1024 rows like the BIG buckets), launch geometry, look-ahead tiles
-    bool grouped = false;
-    struct GrpSched { std::vector<int> g0, g1, split, nrb, tiles64, tiles, la1, la2, p1t, la3, nsplit; std::vector<hipEvent_t> evA, evB; };      // p1t: 64 x 64 tiles of a split front's part 1, la3: tiles of the fronts not split, nsplit: split fronts (among the large ones)
-    GrpSched gs_single, gs_local;              // one-GPU schedule; multi-GPU: the rank's own subtrees
-    std::vector<GrpSched> gs_stage;            // multi-GPU: the replicated fronts this rank holds, per exchange step (sn_gdepth)
-    GrpSched* gs_cur = nullptr;                // ... the step launch_fronts is working on
-    std::vector<hipEvent_t> la_evA, la_evB;
     hipStream_t stream3 = nullptr;             // third stream: the side buckets of small fronts next to a level's main launches (enqueue_factor)
-    hipStream_t stream2 = nullptr; bool la_pending = false; hipEvent_t la_last = nullptr; bool lookahead = true, la_any = false; int la_wgs = 1 << 20, la_min_nt = 8;
-    std::vector<size_t> reg_lds;
-    std::vector<int> mid_split; std::vector<size_t> mid_lds;   // per level: leading FC_LDS128 fronts of order <= 96 (6x6-tile kernel, 2 workgroups per CU) and their LDS need
-    std::vector<int> tiny_split;      // per level: number of leading FC_WAVE fronts of order <= 16 that use the 2x2-tile kernel
-    std::vector<int> tiny16;          // per level: leading FC_WAVE fronts of order <= 16 (the four-per-wavefront static-order kernel takes them first)
-    // multi-GPU schedules: buckets (level, class) of the fronts this rank owns / of the replicated top, stored behind
-    // the single-GPU list in the same device array
-    struct Sched { std::vector<int> ptr; int base = 0; std::vector<int> maxm, maxk, tiles, tiles64, last0, last1; std::vector<char> allsolo; };   // last0/1: per level, the group-last BIG fronts (solve units)
-    Sched sch_local; std::vector<Sched> sch_stage;      // sch_stage[d]: replicated fronts of exchange step d (ranges of ranks d bisections below the whole machine) that this rank holds
-    // Exchange steps (subtree-to-subcube mapping; the classic replicated top is the case of ONE step): a replicated front is held by a range of
-    // ranks; what its children OUTSIDE that range -- subtrees owned by one rank, fronts of a sub-range -- contribute travels through the front's
-    // arena square / top-rhs accumulator, written by ONE reporting rank per child (its owner; the first rank of its range) and summed over the
-    // ranks, all ranges of one depth in one collective, deepest first.  join[c]: the fronts this rank reports a child of kind c to
-    // (c = 0: own subtree roots, c = 1 + d: fronts of its depth-d range) and the code those children carry in ChildMeta::owner.
-    struct JoinList { int base = 0, count = 0, maxm = 0, who = -1; };
-    std::vector<JoinList> join;
-    int ndepth = 1;
-    std::vector<long long> abeg, aend, tbeg, tend;            // per step: its part of the arena / of the top right-hand sides
-    struct RangeSeg { int d, glo, gsz; long long abeg, aend, tbeg, tend; };      // ... and inside a step the part of every range of ranks [glo, glo + gsz)
-    std::vector<RangeSeg> rsegs;
-    long long arena_doubles = 0, toprhs_doubles = 0;
+    hipStream_t stream2 = nullptr; bool la_pending = false; hipEvent_t la_last = nullptr;      // second stream: part 2 of the split group-end updates
     bool multi = false;
 
     // ---- device-side value assembly: per segment a device source buffer + a pinned staging buffer of the same length ----
@@ -390,11 +354,11 @@ public:
     void make_subcomms() {
         destroy_subcomms();
         if (comm_kind != 2 || !rccl.comm || !rccl.CommSplit || knob_disabled("subcomm")) return;
-        rccl.sub.assign(ndepth, nullptr);
+        rccl.sub.assign(P.ndepth, nullptr);
         bool ok = true;
-        for (int d = 0; d < ndepth; ++d) {
+        for (int d = 0; d < P.ndepth; ++d) {
             bool partial = false; int color = -1;      // NCCL_SPLIT_NOCOLOR
-            for (const RangeSeg& sg : rsegs) if (sg.d == d && sg.gsz < opt.nranks) { partial = true; if (sg.glo <= opt.rank && opt.rank < sg.glo + sg.gsz) color = sg.glo; }
+            for (const RangeSeg& sg : P.ex.rsegs) if (sg.d == d && sg.gsz < opt.nranks) { partial = true; if (sg.glo <= opt.rank && opt.rank < sg.glo + sg.gsz) color = sg.glo; }
             if (!partial) continue;
             ncclComm_t nc = nullptr;
             if (rccl.CommSplit(rccl.comm, color, opt.rank, &nc, nullptr) != ncclSuccess) ok = false;
@@ -431,14 +395,14 @@ public:
     bool exchange_step(int d, int what) {
         double* base = what == 0 ? V.arena : V.top_rhs;
         if (range_local()) {
-            for (const RangeSeg& sg : rsegs) {
+            for (const RangeSeg& sg : P.ex.rsegs) {
                 if (sg.d != d || !(sg.glo <= opt.rank && opt.rank < sg.glo + sg.gsz)) continue;
                 const long long b = what == 0 ? sg.abeg : sg.tbeg, e = what == 0 ? sg.aend : sg.tend;
                 if (!allreduce_range(base + b, e - b, 0, d, sg.glo, sg.gsz)) return false;
             }
             return true;
         }
-        const long long b = what == 0 ? abeg[d] : tbeg[d], e = what == 0 ? aend[d] : tend[d];
+        const long long b = what == 0 ? P.ex.abeg[d] : P.ex.tbeg[d], e = what == 0 ? P.ex.aend[d] : P.ex.tend[d];
         return e > b ? allreduce(base + b, e - b, 0) : true;
     }
     bool set_comm_callback(int (*fn)(void*, void*, int64_t, int, void*), void* ctx) {
@@ -513,11 +477,8 @@ public:
             if (ev0) { (void)hipEventDestroy(ev0); ev0 = nullptr; }
             if (ev1) { (void)hipEventDestroy(ev1); ev1 = nullptr; }
         }
-        for (auto e : la_evA) if (e) (void)hipEventDestroy(e);
-        for (auto e : la_evB) if (e) (void)hipEventDestroy(e);
-        la_evA.clear(); la_evB.clear();
-        { std::vector<GrpSched*> all{&gs_single, &gs_local}; for (auto& g : gs_stage) all.push_back(&g);
-          for (GrpSched* g : all) { for (auto* v : {&g->evA, &g->evB}) { for (auto e : *v) if (e) (void)hipEventDestroy(e); v->clear(); } } }
+        for (LaEvents& E : la_ev) for (auto* v : {&E.A, &E.B}) for (auto e : *v) if (e) (void)hipEventDestroy(e);
+        la_ev.clear();
         for (auto* v : {&side_evF, &side_evJ}) { for (auto e : *v) if (e) (void)hipEventDestroy(e); v->clear(); }
         la_last = nullptr; la_pending = false;
         if (!keep) {
@@ -525,7 +486,7 @@ public:
             if (stream2) { (void)hipStreamDestroy(stream2); stream2 = nullptr; }
             if (stream) { (void)hipStreamDestroy(stream); stream = nullptr; }
         }
-        arena_doubles = 0; toprhs_doubles = 0;
+        P = LaunchPlan();
         ready = false;
     }
     template <class T, class A> bool upload(const std::vector<T, A>& h, const T** d) {
@@ -540,75 +501,6 @@ public:
         *d = p; return true;
     }
 
-    // The layout of the exchange steps (a function of the symbolic structure only, the same on every rank; no device needed -- the C ABI's
-    // mi355x_kkt_comm_plan walks it on a machine without a GPU): top-rhs accumulators for every replicated front; arena squares only for those
-    // with a child from outside their range (the joins): that is all the all-reduce has to carry (A is replicated input, not reduced).  Only the
-    // LOWER triangle of a square travels (packed by columns, the layout the front kernels assemble into), and inside a step the squares are
-    // grouped by the range of ranks that holds their front: what a front receives comes from ranks of its own range only, so a range sums its
-    // part among its own ranks (sub-communicator / range callback) -- the other ranks neither send nor receive it.
-    static void exchange_layout(const Symbolic& Sy, int ndepth, std::vector<long long>& aoff, std::vector<long long>& troff, std::vector<long long>& abeg, std::vector<long long>& aend,
-                                std::vector<long long>& tbeg, std::vector<long long>& tend, std::vector<RangeSeg>& rsegs, long long& arena_doubles, long long& toprhs_doubles) {
-        auto same_range = [&](int a, int b) { return Sy.sn_owner[a] < 0 && Sy.sn_owner[b] < 0 && Sy.sn_glo[a] == Sy.sn_glo[b] && Sy.sn_gsz[a] == Sy.sn_gsz[b]; };
-        auto crosses = [&](int c) { const int pa = Sy.sn_parent[c]; return pa >= 0 && Sy.sn_owner[pa] < 0 && !same_range(c, pa); };
-        aoff.assign(Sy.num_sn, -1); troff.assign(Sy.num_sn, -1);
-        arena_doubles = 0; toprhs_doubles = 0;
-        std::vector<char> is_join(Sy.num_sn, 0);
-        for (int c = 0; c < Sy.num_sn; ++c) if (crosses(c)) is_join[Sy.sn_parent[c]] = 1;
-        abeg.assign(ndepth, 0); aend.assign(ndepth, 0); tbeg.assign(ndepth, 0); tend.assign(ndepth, 0);
-        rsegs.clear();
-        for (int d = 0; d < ndepth; ++d) {
-            abeg[d] = arena_doubles; tbeg[d] = toprhs_doubles;
-            std::vector<std::pair<int, int>> ranges;
-            for (int s = 0; s < Sy.num_sn; ++s) if (Sy.sn_owner[s] < 0 && Sy.sn_gdepth[s] == d) {
-                const std::pair<int, int> rg(Sy.sn_glo[s], Sy.sn_gsz[s]);
-                if (std::find(ranges.begin(), ranges.end(), rg) == ranges.end()) ranges.push_back(rg);
-            }
-            std::sort(ranges.begin(), ranges.end());
-            for (const auto& rg : ranges) {
-                RangeSeg sg{d, rg.first, rg.second, arena_doubles, 0, toprhs_doubles, 0};
-                for (int s = 0; s < Sy.num_sn; ++s) if (Sy.sn_owner[s] < 0 && Sy.sn_gdepth[s] == d && Sy.sn_glo[s] == rg.first && Sy.sn_gsz[s] == rg.second) {
-                    const long long m = Sy.sn_rowptr[s + 1] - Sy.sn_rowptr[s];
-                    troff[s] = toprhs_doubles; toprhs_doubles += m;
-                    if (is_join[s]) { aoff[s] = arena_doubles; arena_doubles += m * (m + 1) / 2; }
-                }
-                sg.aend = arena_doubles; sg.tend = toprhs_doubles;
-                rsegs.push_back(sg);
-            }
-            aend[d] = arena_doubles; tend[d] = toprhs_doubles;
-        }
-    }
-    // The collectives ONE rank issues, in order, for a factorisation and for one solve -- and the ncclCommSplit calls of make_subcomms() before them:
-    // records of 6 ints {what, depth, colour, range size, count, dtype}; what: 0 = ncclCommSplit (colour -1: NCCL_SPLIT_NOCOLOR, key = rank), 1 = all-reduce of
-    // arena squares, 2 = inertia / pivot statistics, 3 = all-reduce of top right-hand sides, 4 = solution pieces; colour = first rank of the range (sub-communicator
-    // of that step) or -2 = the whole communicator.  The SAME walk as factor_dist / solve_dist / make_subcomms / exchange_step, without a device.
-    static void comm_plan(const Symbolic& Sy, int nranks, int rank, bool range_local, int n, std::vector<int>& out) {
-        const int ndepth = std::max(1, Sy.num_gdepths);
-        std::vector<long long> aoff, troff, abeg, aend, tbeg, tend; std::vector<RangeSeg> rsegs; long long ad = 0, td = 0;
-        exchange_layout(Sy, ndepth, aoff, troff, abeg, aend, tbeg, tend, rsegs, ad, td);
-        auto rec = [&](int what, int d, int colour, int gsz, long long count, int dtype) { out.push_back(what); out.push_back(d); out.push_back(colour); out.push_back(gsz); out.push_back((int)std::min<long long>(count, 0x7fffffffll)); out.push_back(dtype); };
-        if (range_local)
-            for (int d = 0; d < ndepth; ++d) {
-                bool partial = false; int color = -1;
-                for (const RangeSeg& sg : rsegs) if (sg.d == d && sg.gsz < nranks) { partial = true; if (sg.glo <= rank && rank < sg.glo + sg.gsz) color = sg.glo; }
-                if (partial) rec(0, d, color, 0, 0, 1);
-            }
-        auto step = [&](int d, int what) {
-            if (range_local) {
-                for (const RangeSeg& sg : rsegs) {
-                    if (sg.d != d || !(sg.glo <= rank && rank < sg.glo + sg.gsz)) continue;
-                    const long long cnt = what == 1 ? sg.aend - sg.abeg : sg.tend - sg.tbeg;
-                    if (cnt > 0) rec(what, d, sg.gsz >= nranks ? -2 : sg.glo, sg.gsz, cnt, 0);
-                }
-            } else {
-                const long long cnt = what == 1 ? aend[d] - abeg[d] : tend[d] - tbeg[d];
-                if (cnt > 0) rec(what, d, -2, nranks, cnt, 0);
-            }
-        };
-        for (int d = ndepth - 1; d >= 0; --d) step(d, 1);
-        rec(2, 0, -2, nranks, 8, 1);
-        for (int d = ndepth - 1; d >= 0; --d) step(d, 3);
-        if (n > 0) rec(4, 0, -2, nranks, n, 0);
-    }
     // Delayed pivots changed the structure (symbolic.cpp restructure_delays): everything derived from it is rebuilt, the rest (see release) stays
     bool restructure(const Symbolic& Sy) {
         if (!have_device || !stream) { err_ = "restructure: solver not set up"; return false; }
@@ -639,9 +531,6 @@ public:
             HIPCHK(hipStreamCreateWithPriority(&stream2, hipStreamNonBlocking, plo));
             HIPCHK(hipStreamCreateWithPriority(&stream3, hipStreamNonBlocking, (plo + phi) / 2));
         }
-        lookahead = !knob_disabled("lookahead");
-        la_wgs = (int)std::max(1ll, knob_int("la_wgs", la_wgs));          // development knobs
-        la_min_nt = (int)std::max(3ll, knob_int("la_min_nt", la_min_nt));
         if (!keep) {
             HIPCHK(hipEventCreate(&ev0)); HIPCHK(hipEventCreate(&ev1));
             if (opt.prewarmed_vals && opt.prewarmed_count >= std::max<size_t>(Sy.nnz_in, 1)) h_vals = (double*)opt.prewarmed_vals;       // (made while the analysis ran)
@@ -653,6 +542,7 @@ public:
         }
         opt.prewarmed_vals = nullptr;
         lap("device, streams, pinned buffer");
+        // 1. fit check
         {   // Everything numeric is allocated once, here; the bulk is ONE pool  L | cb  (every contribution block resident: DESIGN.md "Data layout").  A structure
             // whose pool does not fit -- a 3-D problem beyond MBndryCntrl_3D N ~ 120 on 288 GB, or a device shared with another process -- is refused with
             // the numbers, before the allocation is attempted: factor() / solve() then answer MI355X_KKT_FATAL with this message (no partial set-up, no
@@ -673,6 +563,9 @@ public:
                 err_ = msg; return false;
             }
         }
+        multi = opt.nranks > 1 || getenv("MI355X_KKT_FORCE_MULTI") != nullptr;   // (1-rank multi path: plumbing tests on a 1-GPU box)
+        PlanInputs in = plan_inputs_from_env(opt.nranks, opt.rank, multi, opt.verbose);
+        // 2. pool
         // The pool in PIECES (round 5; MI355X_KKT_POOL_PIECE_MIB, default: one block).  hipMalloc of ONE block takes 0.5 s at 16 GiB, 1.4 s at 32, 2.2-2.7 s at the 74 GiB
         // of MBndryCntrl_3D 78 (tools/micro/malloc_time.hip) -- the largest item of that run's whole set-up -- and ten blocks of 7.4 GiB took 3 ms in the micro benchmark,
         // but only because the process had held and freed that memory before: in a fresh process twelve pieces cost what the one block costs (1.6-2.1 s: the price is per
@@ -680,9 +573,9 @@ public:
         // The layout  L | cb  stays ONE linear offset space (symbolic.cpp step 12); it is cut between the blocks of two fronts (the panel or the contribution block of
         // a front that is not in place on a child: everything an in-place chain touches lies inside its first link's block) into segments of at most `piece` doubles,
         // every segment is its own allocation, and an offset of the symbolic structure becomes  offset + (address of its segment - address of segment 0) / 8 - (start
-        // of the segment):  V.L + offset then points into the right allocation; every table the kernels read is built from PO() / CO() below.
-        std::vector<long long> pool_cut, pool_delta;
+        // of the segment):  V.L + offset then points into the right allocation; every table the kernels read is built with that remap (PlanInputs::pool_cut / pool_delta).
         {
+            std::vector<long long>& pool_cut = in.pool_cut;
             const long long total = Sy.l_doubles + Sy.cb_doubles;
             long long piece = 1ll << 60;      // default: ONE block (see above: pieces do not make the allocation faster)
             if (const char* e = getenv("MI355X_KKT_POOL_PIECE_MIB")) piece = std::max(1ll, atoll(e)) << 17;      // (MiB -> doubles; a device too fragmented for one block, tests)
@@ -712,648 +605,55 @@ public:
                     kept_pool = pp; kept_pool_doubles = cap;
                 } else if (!dalloc(&pp, (size_t)std::max<long long>(end - pool_cut[i], 1))) return false;
                 base[i] = (char*)pp;
-                pool_delta.push_back((long long)((base[i] - base[0]) / (ptrdiff_t)sizeof(double)) - pool_cut[i]);
+                in.pool_delta.push_back((long long)((base[i] - base[0]) / (ptrdiff_t)sizeof(double)) - pool_cut[i]);
             }
             V.L = (double*)base[0];
             if (opt.verbose >= 2) fprintf(stderr, "[mi355x_kkt]   pool: %.2f GiB in %zu pieces\n", 8.0 * (double)total / (1024.0 * 1024.0 * 1024.0), pool_cut.size());
         }
-        auto pool_remap = [&](long long lin) { const size_t i = (size_t)(std::upper_bound(pool_cut.begin(), pool_cut.end(), lin) - pool_cut.begin()) - 1; return lin + pool_delta[i]; };
-        auto PO = [&](int sn) { return pool_remap(Sy.panel_off[sn]); };                                   // panel of a front, relative to V.L
-        auto CO = [&](int sn) { return pool_remap(Sy.l_doubles + Sy.cb_off[sn]) - Sy.l_doubles; };        // contribution block, relative to V.cb = V.L + l_doubles
         lap("pool");
-        std::vector<long long> poff(Sy.num_sn), coff(Sy.num_sn), moff(Sy.minv_off.begin(), Sy.minv_off.end());
-        for (int sn = 0; sn < Sy.num_sn; ++sn) { poff[sn] = PO(sn); coff[sn] = CO(sn); }
-        multi = opt.nranks > 1 || getenv("MI355X_KKT_FORCE_MULTI") != nullptr;   // (1-rank multi path: plumbing tests on a 1-GPU box)
-        std::vector<int> lvl_list(Sy.level_sn.begin(), Sy.level_sn.end());
-        std::vector<char> solve_entry;      // parallel to lvl_list: 1 = entry of a solve-unit list
-        std::vector<long long> aoff(Sy.num_sn, -1), troff(Sy.num_sn, -1);
-        std::vector<int> colown(Sy.n, 0);
-        if (multi) {
-            const int P = std::max(1, opt.nranks);
-            ndepth = std::max(1, Sy.num_gdepths);
-            auto held = [&](int s) { return Sy.sn_owner[s] < 0 && Sy.sn_glo[s] <= opt.rank && opt.rank < Sy.sn_glo[s] + Sy.sn_gsz[s]; };      // replicated front on this rank
-            auto build = [&](Sched& sc, int depth) {      // depth < 0: the rank's own subtrees
-                sc.ptr.assign((size_t)Sy.num_levels * FC_COUNT + 1, 0); sc.base = (int)lvl_list.size();
-                sc.maxm.assign(Sy.num_levels, 0); sc.maxk.assign(Sy.num_levels, 0); sc.tiles.assign(Sy.num_levels, 0); sc.tiles64.assign(Sy.num_levels, 0);
-                std::vector<std::vector<int>> bucket((size_t)Sy.num_levels * FC_COUNT);
-                for (int s = 0; s < Sy.num_sn; ++s) {
-                    const bool mine = depth >= 0 ? (held(s) && Sy.sn_gdepth[s] == depth) : (Sy.sn_owner[s] == opt.rank);
-                    if (!mine) continue;
-                    bucket[(size_t)Sy.sn_level[s] * FC_COUNT + Sy.sn_class[s]].push_back(s);
-                    if (Sy.sn_class[s] == FC_BIG) { sc.maxm[Sy.sn_level[s]] = std::max(sc.maxm[Sy.sn_level[s]], Sy.sn_rowptr[s + 1] - Sy.sn_rowptr[s]);
-                                                    sc.maxk[Sy.sn_level[s]] = std::max(sc.maxk[Sy.sn_level[s]], Sy.sn_colptr[s + 1] - Sy.sn_colptr[s]);
-                                                    sc.tiles[Sy.sn_level[s]] = std::max(sc.tiles[Sy.sn_level[s]], schur_tiles(Sy, s));
-                                                    sc.tiles64[Sy.sn_level[s]] = std::max(sc.tiles64[Sy.sn_level[s]], schur_tiles64(Sy, s)); }
-                }
-                for (size_t b = 0; b < bucket.size(); ++b) { sc.ptr[b + 1] = sc.ptr[b] + (int)bucket[b].size(); lvl_list.insert(lvl_list.end(), bucket[b].begin(), bucket[b].end()); }
-                sc.last0.assign(Sy.num_levels, 0); sc.last1.assign(Sy.num_levels, 0);
-                for (int lv = 0; lv < Sy.num_levels; ++lv) {
-                    sc.last0[lv] = (int)lvl_list.size();
-                    for (int sn : bucket[(size_t)lv * FC_COUNT + FC_BIG]) if (Sy.grp_rem[sn] == 0 || !Sy.solve_group) { lvl_list.push_back(sn); solve_entry.resize(lvl_list.size(), 0); solve_entry.back() = 1; }
-                    sc.last1[lv] = (int)lvl_list.size();
-                }
-                sc.allsolo.assign(Sy.num_levels, 0);
-                if (!Sy.solve_group)
-                    for (int lv = 0; lv < Sy.num_levels; ++lv) {
-                        bool all = sc.last1[lv] > sc.last0[lv];
-                        for (int q = sc.last0[lv]; q < sc.last1[lv]; ++q) {
-                            const int sn = lvl_list[q], nch = Sy.child_ptr[sn + 1] - Sy.child_ptr[sn];
-                            if (!((Sy.alias_child[sn] >= 0 && nch == 1) || (Sy.alias_child[sn] < 0 && nch == 0))) all = false;
-                        }
-                        sc.allsolo[lv] = all ? 1 : 0;
-                    }
-            };
-            build(sch_local, -1);
-            sch_stage.assign(ndepth, Sched());
-            for (int d = 0; d < ndepth; ++d) build(sch_stage[d], d);
-            // a child goes through the arena / the top-rhs accumulators when its parent is a replicated front of ANOTHER range of ranks
-            auto same_range = [&](int a, int b) { return Sy.sn_owner[a] < 0 && Sy.sn_owner[b] < 0 && Sy.sn_glo[a] == Sy.sn_glo[b] && Sy.sn_gsz[a] == Sy.sn_gsz[b]; };
-            auto crosses = [&](int c) { const int pa = Sy.sn_parent[c]; return pa >= 0 && Sy.sn_owner[pa] < 0 && !same_range(c, pa); };
-            exchange_layout(Sy, ndepth, aoff, troff, abeg, aend, tbeg, tend, rsegs, arena_doubles, toprhs_doubles);
-            // what this rank reports: its own subtree roots (kind 0), and -- as the first rank of its depth-d range -- that range's fronts (kind 1 + d)
-            join.assign(ndepth + 1, JoinList());
-            for (int c = 0; c <= ndepth; ++c) {
-                JoinList& J = join[c]; J.base = (int)lvl_list.size(); J.who = opt.rank + P * c;
-                std::vector<char> listed(Sy.num_sn, 0);
-                for (int ch = 0; ch < Sy.num_sn; ++ch) {
-                    if (!crosses(ch)) continue;
-                    const bool rep = c == 0 ? Sy.sn_owner[ch] == opt.rank : (Sy.sn_owner[ch] < 0 && Sy.sn_gdepth[ch] == c - 1 && Sy.sn_glo[ch] == opt.rank);
-                    if (rep) listed[Sy.sn_parent[ch]] = 1;
-                }
-                for (int s = 0; s < Sy.num_sn; ++s) if (listed[s]) { lvl_list.push_back(s); ++J.count; J.maxm = std::max(J.maxm, Sy.sn_rowptr[s + 1] - Sy.sn_rowptr[s]); }
-            }
-            // the solution pieces are summed over the ranks: a column is reported by its owner / by the first rank of its front's range
-            for (int s = 0; s < Sy.num_sn; ++s) {
-                const int o = Sy.sn_owner[s] >= 0 ? Sy.sn_owner[s] : (Sy.sn_glo[s] == opt.rank ? opt.rank : P);
-                for (int j = Sy.sn_colptr[s]; j < Sy.sn_colptr[s + 1]; ++j) colown[j] = o;
-            }
-        }
-        // inside every (level, FC_WAVE) bucket of the single-GPU schedule: fronts of order <= 16 first.  When there are many of
-        // them (throughput regime) they run on the 2x2-tile instantiation, whose small register footprint doubles the
-        // number of resident wavefronts.
-        tiny_split.assign(Sy.num_levels, 0); tiny16.assign(Sy.num_levels, 0);
-        for (int lv = 0; lv < Sy.num_levels; ++lv) {
-            const int b0 = Sy.level_ptr[(size_t)lv * FC_COUNT + FC_WAVE], b1 = Sy.level_ptr[(size_t)lv * FC_COUNT + FC_WAVE + 1];
-            auto order_of = [&](int sn) { return Sy.sn_rowptr[sn + 1] - Sy.sn_rowptr[sn]; };
-            std::stable_sort(lvl_list.begin() + b0, lvl_list.begin() + b1, [&](int a, int b) { return order_of(a) < order_of(b); });
-            int q = b0; while (q < b1 && order_of(lvl_list[q]) <= 16) ++q;
-            tiny_split[lv] = (q - b0 >= 2048) ? q - b0 : 0;
-            tiny16[lv] = q - b0;
-        }
-        // same for the (level, FC_LDS128) buckets: fronts of order <= 96 first; they run on the 6x6-tile instantiation (half the
-        // registers and LDS of the 8x8 one => two workgroups per CU)
-        mid_split.assign(Sy.num_levels, 0); mid_lds.assign(Sy.num_levels, 0);
-        for (int lv = 0; lv < Sy.num_levels; ++lv) {
-            const int b0 = Sy.level_ptr[(size_t)lv * FC_COUNT + FC_LDS128], b1 = Sy.level_ptr[(size_t)lv * FC_COUNT + FC_LDS128 + 1];
-            auto order_of = [&](int sn) { return Sy.sn_rowptr[sn + 1] - Sy.sn_rowptr[sn]; };
-            std::stable_sort(lvl_list.begin() + b0, lvl_list.begin() + b1, [&](int a, int b) { return order_of(a) < order_of(b); });
-            int q = b0;
-            while (q < b1 && order_of(lvl_list[q]) <= 96) {
-                const int sn = lvl_list[q];
-                const size_t m = order_of(sn), k = Sy.sn_colptr[sn + 1] - Sy.sn_colptr[sn], ld = m | 1, ldi = k | 1;
-                mid_lds[lv] = std::max(mid_lds[lv], (std::max(m * (m + 1) / 2, k * ld + k * ldi) + 4 * 96 + 3 * k) * sizeof(double) + 2 * k * sizeof(int) + 64);
-                ++q;
-            }
-            mid_split[lv] = (q - b0 >= 256) ? q - b0 : 0;
-        }
-        // (level, FC_BIG) buckets of the single-GPU schedule: sorted by order and split at 1024 rows.  The two halves are
-        // launched separately: tighter rectangular grids on heterogeneous levels, and the small fronts (a handful of tiles,
-        // K = 16..64) take the 256-thread 64 x 64 trailing-update kernel while the large ones take the 1024-thread one.
-        big_split.assign(Sy.num_levels, 0);
-        for (int h = 0; h < 2; ++h) { part_mm[h].assign(Sy.num_levels, 0); part_kk[h].assign(Sy.num_levels, 0); part_tiles[h].assign(Sy.num_levels, 0); }
-        for (int lv = 0; lv < Sy.num_levels; ++lv) {
-            const int b0 = Sy.level_ptr[(size_t)lv * FC_COUNT + FC_BIG], b1 = Sy.level_ptr[(size_t)lv * FC_COUNT + FC_BIG + 1];
-            auto order_of = [&](int sn) { return Sy.sn_rowptr[sn + 1] - Sy.sn_rowptr[sn]; };
-            std::stable_sort(lvl_list.begin() + b0, lvl_list.begin() + b1, [&](int a, int b) { return order_of(a) < order_of(b); });
-            int q = b0; while (q < b1 && order_of(lvl_list[q]) <= 1024) ++q;
-            big_split[lv] = q - b0;
-            for (int e = b0; e < b1; ++e) {
-                const int sn = lvl_list[e], h = e < q ? 0 : 1;
-                part_mm[h][lv] = std::max(part_mm[h][lv], order_of(sn));
-                part_kk[h][lv] = std::max(part_kk[h][lv], Sy.sn_colptr[sn + 1] - Sy.sn_colptr[sn]);
-                part_tiles[h][lv] = std::max(part_tiles[h][lv], h == 0 ? schur_tiles64(Sy, sn) : schur_tiles(Sy, sn));
-            }
-        }
-        // single-GPU schedule: per level the group-last BIG fronts (the units of the triangular solves)
-        big_last0.assign(Sy.num_levels, 0); big_last1.assign(Sy.num_levels, 0);
-        for (int lv = 0; lv < Sy.num_levels; ++lv) {
-            big_last0[lv] = (int)lvl_list.size();
-            for (int q = Sy.level_ptr[(size_t)lv * FC_COUNT + FC_BIG]; q < Sy.level_ptr[(size_t)lv * FC_COUNT + FC_BIG + 1]; ++q)
-                if (Sy.grp_rem[Sy.level_sn[q]] == 0 || !Sy.solve_group) { lvl_list.push_back(Sy.level_sn[q]); solve_entry.resize(lvl_list.size(), 0); solve_entry.back() = 1; }
-            big_last1[lv] = (int)lvl_list.size();
-        }
-        lv_allsolo.assign(Sy.num_levels, 0);
-        if (!Sy.solve_group)
-            for (int lv = 0; lv < Sy.num_levels; ++lv) {
-                bool all = big_last1[lv] > big_last0[lv];
-                for (int q = big_last0[lv]; q < big_last1[lv]; ++q) {
-                    const int sn = lvl_list[q], nch = Sy.child_ptr[sn + 1] - Sy.child_ptr[sn];
-                    if (!((Sy.alias_child[sn] >= 0 && nch == 1) || (Sy.alias_child[sn] < 0 && nch == 0))) all = false;
-                }
-                lv_allsolo[lv] = all ? 1 : 0;
-            }
-        // ---- sync-free (data-flow) sweeps over the latency-bound top of the tree: a SEGMENT is a run of consecutive levels whose fronts are
-        // all BIG with <= 64 pivots and of which there are at most chain_maxc per level; its fronts are cut into CHAINS (maximal runs of
-        // in-place links: every link after the first has the previous link as its only child and shares its vector), and ONE launch per
-        // sweep runs the whole segment: workgroups wait on flags for exactly what they consume (see k_fwd_chain / k_bwd_chain) ----
-        std::vector<ChainLink> chl; std::vector<ChainDesc> chd; std::vector<int> chwait, wgf, wgb;
-        int ntailflags = 0, ndots = 0;
-        chain_segs.clear(); in_seg.clear(); seg_at_lv0.assign(Sy.num_levels, -1); seg_at_lv1.assign(Sy.num_levels, -1);
-        chain_solve = !knob_disabled("chain_solve");
-        fuse_dt = !knob_disabled("fuse_dt");
-        V.fastpiv = !knob_disabled("fastpiv") ? 1 : 0;
-        V.asm_pull = !knob_disabled("asm_pull") ? 1 : 0;
-        grp_rbw_max = (int)std::max(1ll, knob_int("grp_rbw_max", grp_rbw_max));
-        V.fastu = 1e-4; { double fl; if (knob_tune("fastpiv_floor", &fl)) V.fastu = fl; }      // (0.01 up to r03a: 9 % of the synth_1e6 blocks then took the strict loop and set the pace of their level: 23.1 -> 22.0 ms)
-        fuse_dt_maxwg = (int)knob_int("fuse_dt_maxwg", fuse_dt_maxwg);
-        pair_solve = !knob_disabled("pair_solve") && !multi;
-        wave_kmax.assign(Sy.num_levels, 0); wave_mmax.assign(Sy.num_levels, 0); wave_mmin.assign(Sy.num_levels, 1 << 30);
-        for (int sn = 0; sn < Sy.num_sn; ++sn) if (Sy.sn_class[sn] == FC_WAVE) {
-            wave_kmax[Sy.sn_level[sn]] = std::max(wave_kmax[Sy.sn_level[sn]], Sy.sn_colptr[sn + 1] - Sy.sn_colptr[sn]);
-            wave_mmax[Sy.sn_level[sn]] = std::max(wave_mmax[Sy.sn_level[sn]], Sy.sn_rowptr[sn + 1] - Sy.sn_rowptr[sn]);
-            wave_mmin[Sy.sn_level[sn]] = std::min(wave_mmin[Sy.sn_level[sn]], Sy.sn_rowptr[sn + 1] - Sy.sn_rowptr[sn]);
-        }
-        chain_maxc = (int)std::max(1ll, knob_int("chain_solve_maxc", chain_maxc));
-        if (!Sy.solve_group && chain_solve) {
-            auto Kc = [&](int sn) { return Sy.sn_colptr[sn + 1] - Sy.sn_colptr[sn]; };
-            auto Mr = [&](int sn) { return Sy.sn_rowptr[sn + 1] - Sy.sn_rowptr[sn]; };
-            auto nchild = [&](int sn) { return Sy.child_ptr[sn + 1] - Sy.child_ptr[sn]; };
-            auto cnt = [&](int l) { return Sy.level_ptr[(size_t)l * FC_COUNT + FC_COUNT] - Sy.level_ptr[(size_t)l * FC_COUNT]; };
-            // multi-GPU: only runs of >= 4 levels made of pure links of the replicated top (nothing to gather inside the launch: the
-            // distributed sweeps exchange the joins between launches)
-            auto pure = [&](int sn) { return Sy.sn_class[sn] == FC_BIG && Sy.alias_child[sn] >= 0 && nchild(sn) == 1 && Kc(sn) <= 64; };
-            std::vector<char> lvok(Sy.num_levels, 0);
-            for (int lv = 0; lv < Sy.num_levels; ++lv) {
-                const int a = Sy.level_ptr[(size_t)lv * FC_COUNT], b = Sy.level_ptr[(size_t)lv * FC_COUNT + FC_COUNT];
-                bool ok = b > a && b - a <= chain_maxc;
-                for (int q = a; q < b && ok; ++q) {
-                    const int sn = Sy.level_sn[q];
-                    if (multi) ok = pure(sn) && Sy.sn_level[Sy.alias_child[sn]] == lv - 1 && Sy.sn_owner[sn] < 0 && Sy.sn_gdepth[sn] == 0 && Sy.sn_gsz[sn] >= opt.nranks;
-                    else       ok = Kc(sn) <= 64;          // (any class: to the sweeps a small front is a one-link chain like any other)
-                }
-                lvok[lv] = ok ? 1 : 0;
-            }
-            std::vector<int> chain_of(Sy.num_sn, -1);
-            in_seg.assign(Sy.num_sn, 0);
-            for (int lv = 0; lv < Sy.num_levels; ) {
-                if (!lvok[lv]) { ++lv; continue; }
-                int e = lv;
-                while (e + 1 < Sy.num_levels && lvok[e + 1] && (!multi || cnt(e + 1) == cnt(lv))) ++e;
-                if (e - lv + 1 >= (multi ? 4 : 2)) {
-                    ChainSeg sg{lv, e, (int)chd.size(), 0, 0, 0, 0, (int)wgf.size(), (int)wgb.size()};
-                    // chains, in the order of their first links' levels
-                    const size_t chl0 = chl.size();
-                    for (int l = lv; l <= e; ++l)
-                        for (int q = Sy.level_ptr[(size_t)l * FC_COUNT]; q < Sy.level_ptr[(size_t)l * FC_COUNT + FC_COUNT]; ++q) {
-                            const int sn = Sy.level_sn[q], ac = Sy.alias_child[sn];
-                            in_seg[sn] = 1;
-                            ChainLink L{}; L.panel_off = PO(sn); L.minv_off = Sy.minv_off[sn]; L.c0 = Sy.sn_colptr[sn]; L.k = Kc(sn); L.ldp = Sy.sn_ldp[sn];
-                            L.s = sn; L.r0 = Sy.sn_rowptr[sn];
-                            const int cprev = (ac >= 0 && nchild(sn) == 1 && Sy.sn_level[ac] >= lv) ? chain_of[ac] : -1;
-                            if (cprev >= 0) {          // next link of its child's chain (the child is that chain's last link so far)
-                                ChainDesc& D = chd[cprev];
-                                L.koff = D.ktot; D.ktot += L.k; D.nlinks++; D.tail = Mr(sn) - L.k; L.fi = cprev;
-                                chain_of[sn] = cprev;
-                            } else {
-                                ChainDesc D{}; D.cvb = Sy.cv_off[sn]; D.nlinks = 1; D.ktot = L.k; D.tail = Mr(sn) - L.k; D.ch0 = Sy.child_ptr[sn]; D.ch1 = Sy.child_ptr[sn + 1];
-                                D.alias0 = ac >= 0 ? 1 : 0; D.s0 = sn;
-                                L.koff = 0; L.fi = (int)chd.size();
-                                chain_of[sn] = (int)chd.size(); chd.push_back(D);
-                            }
-                            chl.push_back(L);
-                        }
-                    sg.ndesc = (int)chd.size() - sg.desc0;
-                    {   // flatten: links chain by chain, bottom link first
-                        const size_t first = chl0;
-                        std::vector<ChainLink> part(chl.begin() + first, chl.end());
-                        std::stable_sort(part.begin(), part.end(), [](const ChainLink& x, const ChainLink& y) { return x.fi < y.fi; });
-                        std::copy(part.begin(), part.end(), chl.begin() + first);
-                        int cur = -1;
-                        for (size_t t = first; t < chl.size(); ++t) { if (chl[t].fi != cur) { cur = chl[t].fi; chd[cur].link0 = (int)t; } }
-                        for (size_t t = first; t < chl.size(); ++t) chl[t].fi = (int)t;
-                    }
-                    // workgroups: forward in chain order (children's chains first), backward in reverse (parents first)
-                    for (int d = sg.desc0; d < sg.desc0 + sg.ndesc; ++d) {
-                        ChainDesc& D = chd[d];
-                        const int nt = (D.tail + 63) / 64;
-                        D.wg0f = sg.nwg_f; D.tf0 = ntailflags; ntailflags += nt;
-                        for (int w = 0; w < D.nlinks + nt; ++w) wgf.push_back(d);
-                        sg.nwg_f += D.nlinks + nt; sg.maxtail = std::max(sg.maxtail, D.tail);
-                    }
-                    for (int d = sg.desc0 + sg.ndesc - 1; d >= sg.desc0; --d) {      // per chain: its dot workgroups (256 rows beyond the chain x one link each), then its links
-                        ChainDesc& D = chd[d];
-                        const int nw = D.nlinks * ((D.tail + 255) / 256 + 1);
-                        D.wg0b = sg.nwg_b; sg.nwg_b += nw;
-                        D.dot0 = ndots; ndots += D.nlinks * ((D.tail + 255) / 256);
-                        for (int w = 0; w < nw; ++w) wgb.push_back(d);
-                    }
-                    // what a chain waits for: forward, the rows beyond each child chain of its first link (all of them before anything is
-                    // gathered); backward, the bottom link of the chain its parent lives in
-                    for (int d = sg.desc0; d < sg.desc0 + sg.ndesc; ++d) {
-                        ChainDesc& D = chd[d];
-                        D.gw0 = (int)chwait.size();
-                        bool gathers = false;
-                        for (int q = D.ch0; q < D.ch1; ++q) {
-                            const int c = Sy.child_idx[q];
-                            if (c != Sy.alias_child[D.s0]) gathers = true;
-                            if (Sy.sn_level[c] < lv || chain_of[c] < 0) continue;
-                            const ChainDesc& X = chd[chain_of[c]];
-                            for (int b = 0; b < (X.tail + 63) / 64; ++b) chwait.push_back(X.tf0 + b);
-                        }
-                        D.gw1 = (int)chwait.size();
-                        // 0: the vector is in place (in-place link of a front below the segment), 1: fresh vector, nothing to gather, 2: gather step
-                        D.init = (gathers || D.gw1 > D.gw0) ? 2 : (D.alias0 ? 0 : 1);
-                        if (multi && D.init != 0) { fprintf(stderr, "[mi355x_kkt] internal: chain segment with a gather in a distributed schedule\n"); return false; }
-                        const int last = chl[D.link0 + D.nlinks - 1].s, par = Sy.sn_parent[last];
-                        D.pw0 = (int)chwait.size();
-                        if (par >= 0 && Sy.sn_level[par] <= e && chain_of[par] >= 0) { const ChainDesc& P = chd[chain_of[par]]; for (int t = 0; t < P.nlinks; ++t) chwait.push_back(P.link0 + t); }
-                        D.pw1 = (int)chwait.size();
-                    }
-                    seg_at_lv0[lv] = seg_at_lv1[e] = (int)chain_segs.size(); chain_segs.push_back(sg);
-                }
-                lv = e + 1;
-            }
-            if (opt.verbose) { int nl = 0; for (auto& sg : chain_segs) nl += sg.lv1 - sg.lv0 + 1; fprintf(stderr, "[mi355x_kkt] data-flow solve sweeps: %d segments covering %d of %d levels, %d chains, %d links\n", (int)chain_segs.size(), nl, Sy.num_levels, (int)chd.size(), (int)chl.size()); }
-        }
-        if (!upload(wgf, &V.chwg_f) || !upload(wgb, &V.chwg_b) || !upload(chwait, &V.chwait)) return false;
-        V.strace = nullptr; V.strace_b = (int)wgf.size(); strace_n = 0;
-        if (knob_trace("solve") && !wgf.empty()) {
-            strace_n = 4 * (wgf.size() + wgb.size());
-            if (!dalloc(&V.strace, strace_n)) return false;
-            strace_desc.clear();
-            for (size_t i = 0; i < wgf.size(); ++i) { const ChainDesc& D = chd[wgf[i]]; strace_desc.push_back({wgf[i], (int)i - D.wg0f - chain_segs[0].wgf0 * 0, D.nlinks, D.tail}); }
-            for (size_t i = 0; i < wgb.size(); ++i) { const ChainDesc& D = chd[wgb[i]]; strace_desc.push_back({wgb[i], (int)i - D.wg0b - D.nlinks * ((D.tail + 255) / 256), D.nlinks, D.tail}); }      // (dot workgroups: negative)
-        }
-        n_sflag_dot = (size_t)std::max(ndots, 1) * FLAG_STRIDE; n_dpart = (size_t)std::max(ndots, 1) * 64; n_sflag_t = (size_t)std::max(ntailflags, 1) * FLAG_STRIDE; n_sflag_b = std::max<size_t>(chl.size(), 1) * FLAG_STRIDE;
-        if (!dalloc(&V.sflag_dot, n_sflag_dot) || !dalloc(&V.dpart, n_dpart) || !dalloc(&V.sflag_t, n_sflag_t) || !dalloc(&V.sflag_b, n_sflag_b)) return false;
-        {   // tagged solution entries of the segments' columns (indexed by column; + 64: a wavefront polls 64 entries from a link's first column)
-            const size_t nt = chl.empty() ? 1 : (size_t)Sy.n + 64;
-            n_tag = nt;
-            if (!dalloc(&V.ytag, nt) || !dalloc(&V.xtag, nt)) return false;
-        }
-        if (!upload(chl, &V.chlink) || !upload(chd, &V.chdesc)) return false;
-        std::vector<int> bigidx_of(Sy.num_sn, 0);
-        { int nbig = 0; for (int sn = 0; sn < Sy.num_sn; ++sn) if (Sy.sn_class[sn] == FC_BIG) bigidx_of[sn] = nbig++; }
-        // chain-group tables: for every BIG front the links of its group up to and including itself
-        std::vector<GroupLink> gt;
-        std::vector<int> gbase_of(Sy.num_sn, 0), gcols_of(Sy.num_sn, 0);
-        for (int sn = 0; sn < Sy.num_sn; ++sn) {
-            gcols_of[sn] = Sy.sn_colptr[sn + 1] - Sy.sn_colptr[sn];
-            if (Sy.sn_class[sn] != FC_BIG) continue;
-            std::vector<int> links(Sy.grp_pos[sn] + 1);
-            int cur = sn;
-            for (int j = Sy.grp_pos[sn]; j >= 0; --j) { links[j] = cur; if (j > 0) cur = Sy.alias_child[cur]; }
-            gbase_of[sn] = (int)gt.size(); gcols_of[sn] = 0;
-            for (int l : links) {
-                GroupLink G;
-                G.panel_off = PO(l); G.wb = Sy.wb_off[l]; G.minv_off = Sy.minv_off[l]; G.cv = Sy.cv_off[l]; G.tr = troff[l];
-                G.c0 = Sy.sn_colptr[l]; G.k = Sy.sn_colptr[l + 1] - G.c0; G.r0 = Sy.sn_rowptr[l]; G.m = Sy.sn_rowptr[l + 1] - G.r0;
-                G.ldp = Sy.sn_ldp[l]; G.ch0 = Sy.child_ptr[l]; G.ch1 = Sy.child_ptr[l + 1]; G.alias = Sy.alias_child[l] >= 0 ? 1 : 0;
-                G.t_off = CO(l); G.ldt = Sy.sn_ldt[l]; G.s = l; G.aq0 = Sy.acolptr[G.c0]; G.aq1 = Sy.acolptr[G.c0 + G.k]; G.bigidx = bigidx_of[l];
-                G.selfasm = ((!multi || aoff[l] < 0) && !knob_disabled("selfasm") && Sy.alias_child[l] >= 0 && Sy.child_ptr[l + 1] - Sy.child_ptr[l] == 1) ? 1 : 0;
-                gt.push_back(G); gcols_of[sn] += G.k;
-            }
-        }
-        // look-ahead candidates: group-last BIG fronts (>= la_min_nt = 8 tile rows; 12 before part 1 had its 64 x 64 tiles) whose chain continues with a PURE next group (links
-        // whose only child is the chain child: nothing but the chain itself writes into the front before the next full update)
-        std::vector<char> split_of(Sy.num_sn, 0);
-        la_tiles1.assign(Sy.num_levels, 0); la_tiles2.assign(Sy.num_levels, 0); la_full.assign(Sy.num_levels, 0);
-        {
-            std::vector<int> alias_parent(Sy.num_sn, -1);
-            for (int sn = 0; sn < Sy.num_sn; ++sn) if (Sy.alias_child[sn] >= 0) alias_parent[Sy.alias_child[sn]] = sn;
-            for (int sn = 0; sn < Sy.num_sn; ++sn) {
-                if (Sy.sn_class[sn] != FC_BIG || Sy.grp_rem[sn] != 0) continue;
-                const int lv = Sy.sn_level[sn];
-                la_full[lv] = 1;
-                const int mu = (Sy.sn_rowptr[sn + 1] - Sy.sn_rowptr[sn]) - (Sy.sn_colptr[sn + 1] - Sy.sn_colptr[sn]);
-                const int nt = (mu + 127) / 128;
-                bool ok = lookahead && !multi && nt >= la_min_nt && alias_parent[sn] >= 0;
-                for (int p = alias_parent[sn]; ok && p >= 0; p = alias_parent[p]) {
-                    if (Sy.child_ptr[p + 1] - Sy.child_ptr[p] != 1) ok = false;
-                    if (Sy.grp_rem[p] == 0) break;
-                }
-                split_of[sn] = ok ? 1 : 0;
-                la_tiles1[lv] = std::max(la_tiles1[lv], ok ? 2 * nt - 1 : tri_tiles(nt));
-                if (ok) la_tiles2[lv] = std::max(la_tiles2[lv], ((nt - 2) * (nt - 1) / 2 + 7) / 8 * 8);
-            }
-            for (int sn = 0; sn < Sy.num_sn; ++sn) if (Sy.sn_class[sn] == FC_BIG && Sy.grp_rem[sn] != 0)
-                la_tiles1[Sy.sn_level[sn]] = std::max(la_tiles1[Sy.sn_level[sn]], schur_tiles(Sy, sn));
-            if (opt.verbose) {
-                int nsplit = 0, nfull = 0, nimpure = 0, nsmall = 0, nend = 0; long long t2 = 0;
-                for (int sn = 0; sn < Sy.num_sn; ++sn) if (Sy.sn_class[sn] == FC_BIG && Sy.grp_rem[sn] == 0) {
-                    ++nfull; nsplit += split_of[sn];
-                    const int mu = (Sy.sn_rowptr[sn + 1] - Sy.sn_rowptr[sn]) - (Sy.sn_colptr[sn + 1] - Sy.sn_colptr[sn]);
-                    const int nt = (mu + 127) / 128;
-                    if (split_of[sn]) t2 += (long long)(nt - 2) * (nt - 1) / 2;
-                    else if (nt < la_min_nt) ++nsmall; else if (alias_parent[sn] < 0) ++nend; else ++nimpure;
-                }
-                fprintf(stderr, "[mi355x_kkt] look-ahead: %d of %d group-end updates split (%lld part-2 tiles); not split: %d small, %d chain ends, %d impure next group\n",
-                        nsplit, nfull, t2, nsmall, nend, nimpure);
-            }
-            // look-ahead costs the graph replay (see factor()): only worth it when a good part of the flops is in split updates
-            long long la_total = 0;
-            for (int sn = 0; sn < Sy.num_sn; ++sn) if (split_of[sn]) {
-                const int mu = (Sy.sn_rowptr[sn + 1] - Sy.sn_rowptr[sn]) - (Sy.sn_colptr[sn + 1] - Sy.sn_colptr[sn]);
-                const int nt = (mu + 127) / 128; la_total += (long long)(nt - 2) * (nt - 1) / 2;
-            }
-            const long long la_gate = knob_int("la_min_tiles", 4000);     // (tests force 0)
-            if (la_total < la_gate || la_total == 0) { std::fill(split_of.begin(), split_of.end(), 0); std::fill(la_tiles2.begin(), la_tiles2.end(), 0);
-                for (int lv = 0; lv < Sy.num_levels; ++lv) la_tiles1[lv] = 0; }
-            la_any = la_total >= la_gate && la_total > 0;
-            la_evA.assign(Sy.num_levels, nullptr); la_evB.assign(Sy.num_levels, nullptr);
-            for (int lv = 0; lv < Sy.num_levels; ++lv) if (la_tiles2[lv] > 0) {
-                HIPCHK(hipEventCreateWithFlags(&la_evA[lv], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&la_evB[lv], hipEventDisableTiming)); }
-        }
-        // XCD-aware tile orders for the large (>= 12 tile rows) full updates, one table per triangle size
-        std::vector<int> ttab_of(Sy.num_sn, -1), ttab2_of(Sy.num_sn, -1), tile_tab;
-        {
-            std::map<int, int> tab_at;
-            auto table_for = [&](int n) {
-                auto it = tab_at.find(n);
-                if (it != tab_at.end()) return it->second;
-                const int at = (int)tile_tab.size(), S8 = 8, nst = (n + S8 - 1) / S8;
-                for (int I = 0; I < nst; ++I) for (int J = 0; J <= I; ++J)
-                    for (int a = 0; a < S8; ++a) for (int b = 0; b < S8; ++b) {
-                        const int ti = I * S8 + a, tc = J * S8 + b;
-                        if (ti < n && tc <= ti) tile_tab.push_back((ti << 16) | tc);
-                    }
-                tab_at[n] = at; return at;
-            };
-            const bool xcd_aware = !knob_disabled("xcd_tiles");
-            for (int sn = 0; sn < Sy.num_sn; ++sn) if (xcd_aware && Sy.sn_class[sn] == FC_BIG && Sy.grp_rem[sn] == 0) {
-                const int mu = (Sy.sn_rowptr[sn + 1] - Sy.sn_rowptr[sn]) - (Sy.sn_colptr[sn + 1] - Sy.sn_colptr[sn]);
-                const int nt = (mu + 127) / 128;
-                if (nt < 12) continue;
-                ttab_of[sn] = table_for(nt);
-                if (split_of[sn]) ttab2_of[sn] = table_for(nt - 2);
-            }
-        }
-        if (!upload(tile_tab, &V.tile_tab)) return false;
-        const bool selfasm_on = !knob_disabled("selfasm");
-        lv_asm_skip.assign(Sy.num_levels, 0);
-        if (!multi && selfasm_on)
-            for (int lv = 0; lv < Sy.num_levels; ++lv) {
-                bool all = true; int cnt = 0;
-                for (int q = Sy.level_ptr[(size_t)lv * FC_COUNT + FC_BIG]; q < Sy.level_ptr[(size_t)lv * FC_COUNT + FC_BIG + 1]; ++q) {
-                    const int sn = Sy.level_sn[q]; ++cnt;
-                    if (!(Sy.alias_child[sn] >= 0 && Sy.child_ptr[sn + 1] - Sy.child_ptr[sn] == 1)) all = false;
-                }
-                lv_asm_skip[lv] = (cnt > 0 && all) ? 1 : 0;
-            }
-        // levels whose big fronts are ALL chain links that are not the last of their group: the (narrow) trailing updates ride in
-        // the fused pivot-block + panel-solve launch
-        lv_narrow_tiles.assign(Sy.num_levels, 0);
-        if (!multi && !knob_disabled("fuse_upd"))
-            for (int lv = 0; lv < Sy.num_levels; ++lv) {
-                bool all = true; int cnt = 0, tl = 0;
-                for (int q = Sy.level_ptr[(size_t)lv * FC_COUNT + FC_BIG]; q < Sy.level_ptr[(size_t)lv * FC_COUNT + FC_BIG + 1]; ++q) {
-                    const int sn = Sy.level_sn[q]; ++cnt;
-                    if (Sy.grp_rem[sn] <= 0) all = false;
-                    tl = std::max(tl, schur_tiles64(Sy, sn));
-                }
-                lv_narrow_tiles[lv] = (cnt > 0 && all) ? tl : 0;
-            }
-        // ---- grouped schedule: every chain group is factored at the level of its first link (k_grp_fused + update) ----
-        grouped = Sy.maxsupernode <= 64 && selfasm_on && !knob_disabled("grouped");
-        {
-            auto order_of = [&](int sn) { return Sy.sn_rowptr[sn + 1] - Sy.sn_rowptr[sn]; };
-            auto cols_of = [&](int sn) { return Sy.sn_colptr[sn + 1] - Sy.sn_colptr[sn]; };
-            // which: 0 = every front (one GPU), 1 = the rank's own subtrees, 2 + d = the replicated fronts of exchange step d held by this rank (an
-            // in-place chain never crosses an ownership boundary -- symbolic.cpp only aliases fronts of one owner and one range of ranks -- so neither does a group)
-            auto build_groups = [&](GrpSched& G, int which) -> bool {
-                for (auto* v : {&G.g0, &G.g1, &G.split, &G.nrb, &G.tiles64, &G.tiles, &G.la1, &G.la2, &G.p1t, &G.la3, &G.nsplit}) v->assign(Sy.num_levels, 0);
-                G.evA.assign(Sy.num_levels, nullptr); G.evB.assign(Sy.num_levels, nullptr);
-                if (!grouped) return true;
-                std::vector<std::vector<int>> at(Sy.num_levels);
-                for (int sn = 0; sn < Sy.num_sn; ++sn) if (Sy.sn_class[sn] == FC_BIG && Sy.grp_rem[sn] == 0) {
-                    if (which == 1 && Sy.sn_owner[sn] != opt.rank) continue;
-                    if (which >= 2 && !(Sy.sn_owner[sn] < 0 && Sy.sn_glo[sn] <= opt.rank && opt.rank < Sy.sn_glo[sn] + Sy.sn_gsz[sn] && Sy.sn_gdepth[sn] == which - 2)) continue;
-                    int first = sn;
-                    for (int j = Sy.grp_pos[sn]; j > 0; --j) first = Sy.alias_child[first];
-                    if (Sy.sn_level[first] >= Sy.grp_cut_level) at[Sy.sn_level[first]].push_back(sn);      // (groups do not straddle the cut: symbolic.cpp)
-                }
-                int ng = 0;
-                for (int lv = 0; lv < Sy.num_levels; ++lv) {
-                    std::stable_sort(at[lv].begin(), at[lv].end(), [&](int a, int b) { return order_of(a) < order_of(b); });
-                    G.g0[lv] = (int)lvl_list.size();
-                    int nsmall = 0;
-                    for (int sn : at[lv]) {
-                        lvl_list.push_back(sn); ++ng;
-                        const int mu = order_of(sn) - cols_of(sn), nt = (mu + 127) / 128;
-                        G.nrb[lv] = std::max(G.nrb[lv], (mu + 63) / 64);
-                        if (order_of(sn) <= 1024) { ++nsmall; G.tiles64[lv] = std::max(G.tiles64[lv], schur_tiles64(Sy, sn)); }
-                        else {
-                            G.tiles[lv] = std::max(G.tiles[lv], schur_tiles(Sy, sn));
-                            G.la1[lv] = std::max(G.la1[lv], split_of[sn] ? 2 * nt - 1 : tri_tiles(nt));
-                            if (split_of[sn]) G.la2[lv] = std::max(G.la2[lv], ((nt - 2) * (nt - 1) / 2 + 7) / 8 * 8);
-                            if (split_of[sn]) { const int n64 = (mu + 63) / 64; int c = 0; for (int tc = 0; tc < 4 && tc < n64; ++tc) c += n64 - tc; G.p1t[lv] = std::max(G.p1t[lv], c); ++G.nsplit[lv]; }
-                            else G.la3[lv] = std::max(G.la3[lv], tri_tiles(nt));
-                        }
-                    }
-                    G.split[lv] = nsmall; G.g1[lv] = (int)lvl_list.size();
-                    if (G.la2[lv] > 0) { HIPCHK(hipEventCreateWithFlags(&G.evA[lv], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&G.evB[lv], hipEventDisableTiming)); }
-                }
-                if (opt.verbose) fprintf(stderr, "[mi355x_kkt] grouped schedule%s: %d chain groups factored in one launch each (tree levels >= %d)\n",
-                                         which == 0 ? "" : (which == 1 ? " (own subtrees)" : " (replicated fronts of one exchange step)"), ng, Sy.grp_cut_level);
-                return true;
-            };
-            if (!multi) { if (!build_groups(gs_single, 0)) return false; }
-            else { if (!build_groups(gs_local, 1)) return false;
-                   gs_stage.assign(ndepth, GrpSched());
-                   for (int d = 0; d < ndepth; ++d) if (!build_groups(gs_stage[d], 2 + d)) return false; }
-        }
-        asm_fast_ok.assign(lvl_list.size(), 0); h_asmcut.assign(lvl_list.size(), 0);
-        for (size_t q = 0; q < lvl_list.size(); ++q) {
-            const int sn = lvl_list[q];
-            int nch = 0;
-            for (int c = Sy.child_ptr[sn]; c < Sy.child_ptr[sn + 1]; ++c) if (Sy.child_idx[c] != Sy.alias_child[sn]) ++nch;
-            const bool chain_only = Sy.alias_child[sn] >= 0 && nch == 0;      // (pure in-place link: nothing to assemble either way)
-            asm_fast_ok[q] = chain_only ? 1 : (Sy.alias_child[sn] < 0 ? (nch <= 6 ? std::max(nch, 1) : 0) : 0);      // (the number of children the front brings to k_big_assemble2's row maps -- a front with more than ASM_MAXCH falls back to the column routine inside the kernel; 0: not for that kernel)
-        }
-        // tfuse: the contribution block of a front is formed by its trailing update (T = sum of the children's contributions - L21 W21^T, written once) instead of
-        // being assembled, read back and written again.  A front that is a unit of its own -- assembled (not in place on a child), its update one launch of
-        // k_big_schur64 / k_big_schur -- or (round 5) a whole CHAIN GROUP whose first link is assembled: that link's assembly stops at the group's columns
-        // (asmcut: the panels of all the group's links), the trailing block of the LAST link is formed by the group-end update out of the FIRST link's children.
-        // MI355X_KKT_TFUSE_SMALL: the scope of round 4 (fronts of order <= 1024 below the grouped top that are no chain group).
-        std::vector<char> tfuse_of(Sy.num_sn, 0);
-        std::vector<int> asmcut_of(Sy.num_sn, 0);
-        ntfuse = 0;
-        if (!multi && !knob_disabled("tfuse")) {
-            const bool wide = true;
-            for (int sn = 0; sn < Sy.num_sn; ++sn) {
-                if (Sy.sn_class[sn] != FC_BIG || Sy.grp_rem[sn] != 0) continue;      // (the last link of its group, or a front of its own)
-                int first = sn;
-                for (int j = 0; j < Sy.grp_pos[sn]; ++j) first = Sy.alias_child[first];
-                const int m = Sy.sn_rowptr[sn + 1] - Sy.sn_rowptr[sn], k = Sy.sn_colptr[sn + 1] - Sy.sn_colptr[sn], nch = Sy.child_ptr[first + 1] - Sy.child_ptr[first];
-                if (Sy.alias_child[first] >= 0 || m <= k) continue;
-                if (!wide) {
-                    if (m > 1024 || nch > 16 || Sy.grp_pos[sn] != 0) continue;
-                    if (grouped && Sy.sn_level[sn] >= Sy.grp_cut_level) continue;
-                } else if (nch > 96) continue;
-                tfuse_of[sn] = 1; ++ntfuse;
-                asmcut_of[first] = (Sy.sn_rowptr[first + 1] - Sy.sn_rowptr[first]) - (m - k);      // (= k of a front of its own, the group's columns otherwise)
-            }
-        }
-        if (opt.verbose) fprintf(stderr, "[mi355x_kkt] contribution blocks formed by their update (not assembled): %d of %d big fronts\n", ntfuse, Sy.num_big);
-        std::vector<FrontMeta> fm(lvl_list.size());
-        for (size_t q = 0; q < lvl_list.size(); ++q) {
-            const int sn = lvl_list[q];
-            FrontMeta& M = fm[q];
-            M.tfuse = tfuse_of[sn]; M.asmcut = asmcut_of[sn]; h_asmcut[q] = M.asmcut;      // (-1 below: a pure in-place link, nothing to assemble)
-            M.s = sn; M.c0 = Sy.sn_colptr[sn]; M.k = Sy.sn_colptr[sn + 1] - M.c0; M.r0 = Sy.sn_rowptr[sn]; M.m = Sy.sn_rowptr[sn + 1] - M.r0;
-            M.aq0 = Sy.acolptr[M.c0]; M.aq1 = Sy.acolptr[M.c0 + M.k]; M.ch0 = Sy.child_ptr[sn]; M.ch1 = Sy.child_ptr[sn + 1]; M.alias = Sy.alias_child[sn] >= 0 ? 1 : 0;
-            M.ldp = Sy.sn_ldp[sn]; M.ldt = Sy.sn_ldt[sn];
-            M.panel_off = PO(sn); M.cb_off = CO(sn); M.minv_off = Sy.minv_off[sn];
-            M.cv = Sy.cv_off[sn]; M.wb = Sy.wb_off[sn]; M.gpart = Sy.gpart_off[sn];
-            M.gbase = gbase_of[sn]; M.gpos = Sy.grp_pos[sn]; M.grem = Sy.grp_rem[sn]; M.gcols = gcols_of[sn]; M.split = split_of[sn]; M.ttab = ttab_of[sn]; M.ttab2 = ttab2_of[sn];
-            // (multi-GPU: not for a front at a subtree join -- its square comes out of the all-reduced arena)
-            M.selfasm = ((!multi || aoff[sn] < 0) && selfasm_on && Sy.sn_class[sn] == FC_BIG && Sy.alias_child[sn] >= 0 && Sy.child_ptr[sn + 1] - Sy.child_ptr[sn] == 1) ? 1 : 0; M.bigidx = bigidx_of[sn];
-            {   // 1: in-place chain link whose only child is the chain child, 2: no children at all => the fused forward kernel applies
-                const int nch = Sy.child_ptr[sn + 1] - Sy.child_ptr[sn];
-                M.solo = (Sy.alias_child[sn] >= 0 && nch == 1) ? 1 : ((Sy.alias_child[sn] < 0 && nch == 0) ? 2 : 0);
-            }
-            if (M.selfasm && !M.asmcut) h_asmcut[q] = -1;
-            if (q < solve_entry.size() && solve_entry[q] && !Sy.solve_group) {     // per-link solves: every front is its own unit
-                M.gbase += M.gpos; M.gpos = 0; M.grem = 0; M.gcols = M.k;
-            }
-        }
-        // ChildMeta::owner as the kernels read it: -1 = assembled directly by the parent (same owner / same range of ranks); otherwise the child
-        // reaches its (replicated) parent through the arena and the value says who reports it and in which exchange step: reporting rank
-        // + nranks * (0 for an owned subtree root, 1 + depth for a front of a sub-range) -- the `who` of k_arena_assemble / k_top_rhs_assemble
-        auto child_code = [&](int ch) {
-            const int pa = Sy.sn_parent[ch], P = std::max(1, opt.nranks);
-            if (!multi || pa < 0 || Sy.sn_owner[pa] >= 0) return Sy.sn_owner[ch];
-            if (Sy.sn_owner[ch] >= 0) return Sy.sn_owner[ch];
-            if (Sy.sn_glo[ch] == Sy.sn_glo[pa] && Sy.sn_gsz[ch] == Sy.sn_gsz[pa]) return -1;
-            return Sy.sn_glo[ch] + P * (1 + Sy.sn_gdepth[ch]);
-        };
-        std::vector<ChildMeta> cm(Sy.child_idx.size());
-        for (size_t q = 0; q < cm.size(); ++q) {
-            const int ch = Sy.child_idx[q]; const int kc = Sy.sn_colptr[ch + 1] - Sy.sn_colptr[ch];
-            cm[q].ch = ch; cm[q].relbase = Sy.sn_rowptr[ch] + kc; cm[q].mc = Sy.sn_rowptr[ch + 1] - cm[q].relbase;
-            cm[q].owner = child_code(ch); cm[q].cb_off = CO(ch); cm[q].ldt = Sy.sn_ldt[ch]; cm[q].aliased = 0; cm[q].cvbase = Sy.cv_off[ch] + kc;
-            cm[q].rlo = cm[q].mc > 0 ? Sy.rel[cm[q].relbase] : (1 << 30); cm[q].rhi = cm[q].mc > 0 ? Sy.rel[cm[q].relbase + cm[q].mc - 1] : -1;      // (rel is ascending)
-        }
-        for (int sn = 0; sn < Sy.num_sn; ++sn) if (Sy.alias_child[sn] >= 0)
-            for (int q = Sy.child_ptr[sn]; q < Sy.child_ptr[sn + 1]; ++q) if (Sy.child_idx[q] == Sy.alias_child[sn]) cm[q].aliased = 1;
-        // inverse relative indices for the children of BIG parents (k_big_assemble: one load instead of a binary search per column)
-        std::vector<int> relinv;
-        for (int sn = 0; sn < Sy.num_sn; ++sn) {
-            for (int q = Sy.child_ptr[sn]; q < Sy.child_ptr[sn + 1]; ++q) cm[q].inv = 0;
-            if (Sy.sn_class[sn] != FC_BIG && !(sn < (int)in_seg.size() && in_seg[sn])) continue;
-            const int mp = Sy.sn_rowptr[sn + 1] - Sy.sn_rowptr[sn];
-            for (int q = Sy.child_ptr[sn]; q < Sy.child_ptr[sn + 1]; ++q) {
-                if (cm[q].aliased) continue;
-                cm[q].inv = (long long)relinv.size();
-                relinv.resize(relinv.size() + mp, -1);
-                int* inv = relinv.data() + cm[q].inv;
-                for (int a = 0; a < cm[q].mc; ++a) inv[Sy.rel[cm[q].relbase + a]] = a;
-            }
-        }
-        if (!upload(relinv, &V.relinv)) return false;
-        {   // per big front: room for the 16 x 16 diagonal-block inverses of its L11 (ISG_STRIDE doubles each, slot FrontMeta::bigidx)
-            long long nbig = 0;
-            for (int sn = 0; sn < Sy.num_sn; ++sn) if (Sy.sn_class[sn] == FC_BIG) ++nbig;
-            if (!dalloc(&V.isg, (size_t)std::max<long long>(nbig * ISG_STRIDE, 1)) || !dalloc(&V.hasis, Sy.num_sn)) return false;
+        // 3. the launch plan (launch_plan.cpp: host only)
+        knobs = in;
+        P = build_launch_plan(Sy, in);
+        if (!P.error.empty()) { err_ = P.error; return false; }
+        V.fastpiv = in.fastpiv ? 1 : 0; V.asm_pull = in.asm_pull ? 1 : 0; V.fastu = in.fastpiv_floor;
+        df_grid_cap = 0;
+        if (!P.df_runs.empty()) {
+            int per_cu = 0, ncu = 0;
+            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_front_df, 64, 0);
+            (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+            df_grid_cap = std::max(1, per_cu) * std::max(1, ncu);      // every workgroup of the launch must be resident (they wait for each other)
+            if (opt.verbose) { int nl = 0; for (auto& R : P.df_runs) nl += R.nlev; fprintf(stderr, "[mi355x_kkt] small fronts: %d runs covering %d of %d levels in one data-flow launch each (grid <= %d workgroups)\n", (int)P.df_runs.size(), nl, Sy.num_levels, df_grid_cap); }
         }
         lap("host-side schedules and tables");
-        if (!upload(fm, &V.fmeta) || !upload(cm, &V.cmeta) || !upload(gt, &V.gtab)) return false;
-        {   // leaf chains (k_leaf_chain): the levels below lc_levels hold nothing but fronts of order <= 16 with at most one child -- every such front is a
-            // link of the chain that starts at its leaf
-            lc_levels = 0; lc_nchains = 0;
-            std::vector<int> lcp, lcf; std::vector<LeafLink> lcl;
-            if (!multi && V.fastpiv && !knob_disabled("leafchain")) {
-                int L = 0;
-                for (; L < Sy.num_levels && L < 16; ++L) {
-                    bool okl = true; int cnt = 0;
-                    for (int fc = 0; fc < FC_COUNT && okl; ++fc) {
-                        const int b0 = Sy.level_ptr[(size_t)L * FC_COUNT + fc], b1 = Sy.level_ptr[(size_t)L * FC_COUNT + fc + 1];
-                        if (fc != FC_WAVE) { if (b1 > b0) okl = false; continue; }
-                        for (int q = b0; q < b1 && okl; ++q) {
-                            const int sn = lvl_list[q]; ++cnt;
-                            if (Sy.sn_rowptr[sn + 1] - Sy.sn_rowptr[sn] > 16 || Sy.child_ptr[sn + 1] - Sy.child_ptr[sn] > 1) okl = false;
-                        }
-                    }
-                    if (!okl || cnt == 0) break;
-                }
-                if (L >= 2) {
-                    lc_levels = L;
-                    std::vector<int> fmw(Sy.num_sn, -1);
-                    for (int lv = 0; lv < L; ++lv) for (int q = Sy.level_ptr[(size_t)lv * FC_COUNT + FC_WAVE]; q < Sy.level_ptr[(size_t)lv * FC_COUNT + FC_WAVE + 1]; ++q) fmw[lvl_list[q]] = q;
-                    lcp.push_back(0);
-                    for (int q = Sy.level_ptr[(size_t)0 * FC_COUNT + FC_WAVE]; q < Sy.level_ptr[(size_t)0 * FC_COUNT + FC_WAVE + 1]; ++q) {
-                        for (int cur = lvl_list[q]; cur >= 0 && Sy.sn_level[cur] < L; cur = Sy.sn_parent[cur]) lcf.push_back(fmw[cur]);
-                        lcp.push_back((int)lcf.size());
-                    }
-                    lc_nchains = (int)lcp.size() - 1;
-                    if ((int)lcf.size() != Sy.level_ptr[(size_t)(L - 1) * FC_COUNT + FC_WAVE + 1] - Sy.level_ptr[(size_t)0 * FC_COUNT + FC_WAVE]) { lc_levels = 0; lc_nchains = 0; }   // (cannot happen: every front below L is on exactly one chain)
-                    if (opt.verbose && lc_levels) fprintf(stderr, "[mi355x_kkt] leaf chains: %d chains over the bottom %d levels (%zu fronts) in one launch per sweep\n", lc_nchains, lc_levels, lcf.size());
-                }
-            }
-            if (lcp.empty()) lcp.push_back(0);
-            for (int q : lcf) {
-                const FrontMeta& M = fm[q]; LeafLink K;
-                K.s = M.s; K.c0 = M.c0; K.k = M.k; K.m = M.m; K.aq0 = M.aq0; K.aq1 = M.aq1; K.ldp = M.ldp; K.r0 = M.r0; K.pad = 0;
-                K.relbase = M.r0 + M.k;                                  // (V.rel + relbase: where the front's update rows sit in its parent)
-                K.panel_off = M.panel_off; K.minv_off = M.minv_off; K.cb_off = M.cb_off; K.cv = M.cv;
-                lcl.push_back(K);
-            }
-            if (lcl.empty()) lcl.push_back(LeafLink());
-            if (!upload(lcp, &V.lc_ptr) || !upload(lcl, &V.lc_link)) return false;
+        // 4. the plan's tables
+        if (!upload(P.wgf, &V.chwg_f) || !upload(P.wgb, &V.chwg_b) || !upload(P.chwait, &V.chwait)) return false;
+        V.strace = nullptr; V.strace_b = (int)P.wgf.size(); strace_n = 0;
+        if (knob_trace("solve") && !P.wgf.empty()) {
+            strace_n = 4 * (P.wgf.size() + P.wgb.size());
+            if (!dalloc(&V.strace, strace_n)) return false;
+            strace_desc.clear();
+            for (size_t i = 0; i < P.wgf.size(); ++i) { const ChainDesc& D = P.chd[P.wgf[i]]; strace_desc.push_back({P.wgf[i], (int)i - D.wg0f, D.nlinks, D.tail}); }
+            for (size_t i = 0; i < P.wgb.size(); ++i) { const ChainDesc& D = P.chd[P.wgb[i]]; strace_desc.push_back({P.wgb[i], (int)i - D.wg0b - D.nlinks * ((D.tail + 255) / 256), D.nlinks, D.tail}); }      // (dot workgroups: negative)
         }
-        {   // k_front_df: maximal runs of >= 2 consecutive levels (above the leaf chains) whose fronts are all one-wavefront fronts
-            df_runs.clear(); df_run_at.assign(Sy.num_levels, -1);
-            std::vector<DfLevel> tab; std::vector<long long> cto(std::max(Sy.num_sn, 1), -1); std::vector<int> run_of(std::max(Sy.num_sn, 1), -1); long long cbt_len = 0;
-            if (!multi && V.fastpiv && df_on) {
-                auto pure = [&](int lv) {
-                    const int w0 = Sy.level_ptr[(size_t)lv * FC_COUNT + FC_WAVE], w1 = Sy.level_ptr[(size_t)lv * FC_COUNT + FC_WAVE + 1];
-                    return w1 > w0 && w1 - w0 == Sy.level_ptr[(size_t)lv * FC_COUNT + FC_COUNT] - Sy.level_ptr[(size_t)lv * FC_COUNT];
-                };
-                for (int lv = lc_levels; lv < Sy.num_levels; ) {
-                    if (!pure(lv)) { ++lv; continue; }
-                    int e = lv; while (e + 1 < Sy.num_levels && pure(e + 1)) ++e;
-                    if (e > lv) {
-                        DfRun R{lv, e, (int)tab.size(), e - lv + 1, 0};
-                        for (int l = lv; l <= e; ++l) {
-                            const int w0 = Sy.level_ptr[(size_t)l * FC_COUNT + FC_WAVE], w1 = Sy.level_ptr[(size_t)l * FC_COUNT + FC_WAVE + 1];
-                            tab.push_back(DfLevel{w0, tiny16[l], w1 - w0, R.nq});
-                            R.nq += (tiny16[l] + 3) / 4 + (w1 - w0 - tiny16[l]);
-                            for (int q = w0; q < w1; ++q) run_of[lvl_list[q]] = (int)df_runs.size();
-                        }
-                        df_run_at[lv] = (int)df_runs.size(); df_runs.push_back(R);
-                    }
-                    lv = e + 1;
-                }
-                int per_cu = 0, ncu = 0;
-                (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_front_df, 64, 0);
-                (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-                df_grid_cap = std::max(1, per_cu) * std::max(1, ncu);      // every workgroup of the launch must be resident (they wait for each other)
-                if (opt.verbose && !df_runs.empty()) { int nl = 0; for (auto& R : df_runs) nl += R.nlev; fprintf(stderr, "[mi355x_kkt] small fronts: %d runs covering %d of %d levels in one data-flow launch each (grid <= %d workgroups)\n", (int)df_runs.size(), nl, Sy.num_levels, df_grid_cap); }
-            }
-            // tagged contribution blocks: for every front of a run whose PARENT is a front of the same run
-            for (int sn = 0; sn < Sy.num_sn; ++sn) {
-                const int pa = Sy.sn_parent[sn];
-                if (run_of[sn] < 0 || pa < 0 || run_of[pa] != run_of[sn]) continue;
-                const int mu = (Sy.sn_rowptr[sn + 1] - Sy.sn_rowptr[sn]) - (Sy.sn_colptr[sn + 1] - Sy.sn_colptr[sn]);
-                if (mu <= 0) continue;
-                cto[sn] = cbt_len; cbt_len += mu <= 16 ? 256 : 1024;
-            }
-            if (tab.empty()) tab.push_back(DfLevel{0, 0, 0, 0});
-            if (!upload(tab, &d_dftab)) return false;
-            if (!upload(cto, &V.cbt_off)) return false;
-            if (!dalloc(&V.cbt, (size_t)std::max<long long>(cbt_len, 1))) return false;
-        }
-        // the inertia / pivot counts are summed over the ranks: a replicated front is counted by the first rank of its range (-1 in this rank's view), -3 = not here
-        std::vector<int> stat_owner(Sy.sn_owner.begin(), Sy.sn_owner.end());
-        if (multi) for (int sn = 0; sn < Sy.num_sn; ++sn) if (Sy.sn_owner[sn] < 0) stat_owner[sn] = Sy.sn_glo[sn] == opt.rank ? -1 : -3;
+        n_sflag_dot = (size_t)std::max(P.ndots, 1) * FLAG_STRIDE; n_dpart = (size_t)std::max(P.ndots, 1) * 64; n_sflag_t = (size_t)std::max(P.ntailflags, 1) * FLAG_STRIDE; n_sflag_b = std::max<size_t>(P.chl.size(), 1) * FLAG_STRIDE;
+        if (!dalloc(&V.sflag_dot, n_sflag_dot) || !dalloc(&V.dpart, n_dpart) || !dalloc(&V.sflag_t, n_sflag_t) || !dalloc(&V.sflag_b, n_sflag_b)) return false;
+        n_tag = P.chl.empty() ? 1 : (size_t)Sy.n + 64;      // tagged solution entries of the segments' columns (indexed by column; + 64: a wavefront polls 64 entries from a link's first column)
+        if (!dalloc(&V.ytag, n_tag) || !dalloc(&V.xtag, n_tag)) return false;
+        if (!upload(P.chl, &V.chlink) || !upload(P.chd, &V.chdesc) || !upload(P.tile_tab, &V.tile_tab) || !upload(P.relinv, &V.relinv)) return false;
+        // per big front: room for the 16 x 16 diagonal-block inverses of its L11 (ISG_STRIDE doubles each, slot FrontMeta::bigidx)
+        if (!dalloc(&V.isg, (size_t)std::max<long long>((long long)P.nbig * ISG_STRIDE, 1)) || !dalloc(&V.hasis, Sy.num_sn)) return false;
+        if (!upload(P.fmeta, &V.fmeta) || !upload(P.cmeta, &V.cmeta) || !upload(P.gtab, &V.gtab) || !upload(P.lc_ptr, &V.lc_ptr) || !upload(P.lc_link, &V.lc_link) ||
+            !upload(P.df_tab, &d_dftab) || !upload(P.cbt_off, &V.cbt_off) || !dalloc(&V.cbt, (size_t)std::max<long long>(P.cbt_len, 1))) return false;
+        const std::vector<long long> moff(Sy.minv_off.begin(), Sy.minv_off.end());
         if (!upload(Sy.sn_colptr, &V.sn_colptr) || !upload(Sy.sn_rowptr, &V.sn_rowptr) || !upload(Sy.sn_rows, &V.sn_rows) ||
             !upload(Sy.rel, &V.rel) || !upload(Sy.child_ptr, &V.child_ptr) || !upload(Sy.child_idx, &V.child_idx) ||
-            !upload(stat_owner, &V.sn_owner) || !upload(poff, &V.panel_off) || !upload(coff, &V.cb_off) || !upload(moff, &V.minv_off) ||
+            !upload(P.stat_owner, &V.sn_owner) || !upload(P.panel_off, &V.panel_off) || !upload(P.cb_off, &V.cb_off) || !upload(moff, &V.minv_off) ||
             !upload(Sy.acolptr, &V.acolptr) || !upload(Sy.apos, &V.apos) || !upload(Sy.arow, &V.arow) || !upload(Sy.acol, &V.acol) ||
-            !upload(Sy.dup_ptr, &V.dup_ptr) || !upload(Sy.dup_src, &V.dup_src) || !upload(Sy.rslot_ptr, &V.rslot_ptr) || !upload(Sy.rslot_idx, &V.rslot_idx) || !upload(Sy.rslot_col, &V.rslot_col) || !upload(lvl_list, &V.level_sn) ||
-            !upload(Sy.sn_parent, &V.sn_parent) || !upload(colown, &V.col_owner) || !upload(aoff, &V.arena_off) || !upload(troff, &V.top_rhs_off) ||
+            !upload(Sy.dup_ptr, &V.dup_ptr) || !upload(Sy.dup_src, &V.dup_src) || !upload(Sy.rslot_ptr, &V.rslot_ptr) || !upload(Sy.rslot_idx, &V.rslot_idx) || !upload(Sy.rslot_col, &V.rslot_col) || !upload(P.lvl_list, &V.level_sn) ||
+            !upload(Sy.sn_parent, &V.sn_parent) || !upload(P.col_owner, &V.col_owner) || !upload(P.ex.aoff, &V.arena_off) || !upload(P.ex.troff, &V.top_rhs_off) ||
             !upload(Sy.perm, &V.perm)) return false;
         lap("uploads");
+        // 5. work arrays
         double* tv = keep ? keep_tvals : nullptr;
         if (!tv && !dalloc(&tv, Sy.nnz_in)) return false;
         V.tvals = tv;
@@ -1371,9 +671,17 @@ public:
         V.cb = V.L + Sy.l_doubles;          // one pool: panels of in-place chain fronts live inside the cb part
         V.arena = nullptr; V.top_rhs = nullptr; V.rank = opt.rank; V.dbg = nullptr;
         if (knob_trace("clocks")) { if (!dalloc(&V.dbg, 128)) return false; }
-        if (multi) { if (!dalloc(&V.arena, (size_t)arena_doubles) || !dalloc(&V.top_rhs, (size_t)toprhs_doubles)) return false; }
+        if (multi) { if (!dalloc(&V.arena, (size_t)P.ex.arena_doubles) || !dalloc(&V.top_rhs, (size_t)P.ex.toprhs_doubles)) return false; }
         V.pivtol = opt.pivtol; V.pivtol2 = std::max(opt.pivtol, opt.pivtolmax); V.small = opt.small; V.n = Sy.n; V.nnz_a = Sy.nnz_a; V.nsn = Sy.num_sn; V.xcd_affine = knob_disabled("xcd_affine") ? 0 : 1;
-        // allow the large dynamic LDS sizes
+        // 6. events: the look-ahead levels of the single-GPU schedule and of the grouped schedules
+        la_ev.assign(1 + P.grp.size(), LaEvents());
+        for (size_t i = 0; i < la_ev.size(); ++i) {
+            const std::vector<int>& la2 = i == 0 ? P.la_tiles2 : P.grp[i - 1].la2;
+            la_ev[i].A.assign(la2.size(), nullptr); la_ev[i].B.assign(la2.size(), nullptr);
+            for (size_t lv = 0; lv < la2.size(); ++lv) if (la2[lv] > 0) {
+                HIPCHK(hipEventCreateWithFlags(&la_ev[i].A[lv], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&la_ev[i].B[lv], hipEventDisableTiming)); }
+        }
+        // 7. kernel attributes: allow the large dynamic LDS sizes
         HIPCHK(hipFuncSetAttribute((const void*)k_big_diag_reg<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         HIPCHK(hipFuncSetAttribute((const void*)(k_big_diag_reg<4, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         HIPCHK(hipFuncSetAttribute((const void*)(k_front_reg<64, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -1383,30 +691,11 @@ public:
         HIPCHK(hipFuncSetAttribute((const void*)(k_front_reg<256, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         HIPCHK(hipFuncSetAttribute((const void*)(k_front_reg<256, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         HIPCHK(hipFuncSetAttribute((const void*)(k_front_reg<256, 6, true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        // exact LDS need of the register-tiled front kernel per (level, class) bucket
-        reg_lds.assign((size_t)Sy.num_levels * FC_COUNT, 0);
-        for (int s = 0; s < Sy.num_sn; ++s) {
-            const size_t m = Sy.sn_rowptr[s + 1] - Sy.sn_rowptr[s], k = Sy.sn_colptr[s + 1] - Sy.sn_colptr[s];
-            const size_t ld = m | 1, ldi = k | 1;
-            const size_t maxm = Sy.sn_class[s] == FC_WAVE ? 32 : (Sy.sn_class[s] == FC_LDS64 ? 64 : 128);
-            const size_t need = (std::max(m * (m + 1) / 2, k * ld + k * ldi) + 4 * maxm + 3 * k) * sizeof(double) + 2 * k * sizeof(int) + 64;
-            size_t& r = reg_lds[(size_t)Sy.sn_level[s] * FC_COUNT + Sy.sn_class[s]];
-            r = std::max(r, need);
-        }
         HIPCHK(hipFuncSetAttribute((const void*)k_big_trsm<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         HIPCHK(hipFuncSetAttribute((const void*)k_big_trsm<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         HIPCHK(hipFuncSetAttribute((const void*)k_big_diag_trsm, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         HIPCHK(hipFuncSetAttribute((const void*)k_grp_fused, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         HIPCHK(hipFuncSetAttribute((const void*)k_big_assemble2, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));      // (+ 1.3 KB of static LDS: the per-child tables)
-        // per (level, BIG) bucket: largest front order / pivot count (launch geometry)
-        big_maxm.assign(Sy.num_levels, 0); big_maxk.assign(Sy.num_levels, 0); big_tiles.assign(Sy.num_levels, 0); big_tiles64.assign(Sy.num_levels, 0);
-        for (int s = 0; s < Sy.num_sn; ++s) if (Sy.sn_class[s] == FC_BIG) {
-            const int lv = Sy.sn_level[s];
-            big_maxm[lv] = std::max(big_maxm[lv], Sy.sn_rowptr[s + 1] - Sy.sn_rowptr[s]);
-            big_maxk[lv] = std::max(big_maxk[lv], Sy.sn_colptr[s + 1] - Sy.sn_colptr[s]);
-            big_tiles[lv] = std::max(big_tiles[lv], schur_tiles(Sy, s));
-            big_tiles64[lv] = std::max(big_tiles64[lv], schur_tiles64(Sy, s));
-        }
         // hipMemset runs on the legacy default stream; the solver's streams are non-blocking, i.e. NOT ordered behind it: without this the first
         // sweeps of a small system could meet flags / tagged messages left in recycled device memory by an earlier handle (or process) before
         // the zero fill has landed
@@ -1417,19 +706,6 @@ public:
         return true;
     }
 
-    static int schur_tiles64(const Symbolic& Sy, int s) {
-        const int mu = (Sy.sn_rowptr[s + 1] - Sy.sn_rowptr[s]) - (Sy.sn_colptr[s + 1] - Sy.sn_colptr[s]);
-        const int nt = (mu + 63) / 64;
-        return Sy.grp_rem[s] > 0 ? nt * ((Sy.grp_rem[s] + 63) / 64) : nt * (nt + 1) / 2;
-    }
-    static int tri_tiles(int nt) { const int t = nt * (nt + 1) / 2; return nt >= 12 ? (t + 7) / 8 * 8 : t; }    // large ones: multiple of 8 (XCD-aware order)
-    // 128x128 tiles of the trailing update of front s: the whole lower triangle, or (not the last link of a chain group) only
-    // the tile columns of the group's remaining panels
-    static int schur_tiles(const Symbolic& Sy, int s) {
-        const int mu = (Sy.sn_rowptr[s + 1] - Sy.sn_rowptr[s]) - (Sy.sn_colptr[s + 1] - Sy.sn_colptr[s]);
-        const int nt = (mu + 127) / 128;
-        return Sy.grp_rem[s] > 0 ? nt * ((Sy.grp_rem[s] + 127) / 128) : tri_tiles(nt);
-    }
     static size_t trsm_lds(int kk) { return trsm_lds_bytes(kk, false); }
     static int schur_grid(int tiles) { return SCHUR_GM == 2 ? 16 * ((tiles + 7) / 8) : tiles; }      // workgroups of a k_big_schur launch over `tiles` 128 x 128 tiles (kernels_big.hip.inc: SCHUR_HALVES)
     int grid1d(long long n) const { long long g = (n + 255) / 256; return (int)std::min<long long>(std::max<long long>(g, 1), 2048); }
@@ -1438,13 +714,13 @@ public:
     // one (level, class) bucket of fronts
     bool launch_bucket(int lv, int fc, int b0, int b1, int top_mode, int mm, int kk, int tiles, int tiles64) {
         const int nb = b1 - b0;
-        const size_t rl = reg_lds[(size_t)lv * FC_COUNT + fc];
+        const size_t rl = P.reg_lds[(size_t)lv * FC_COUNT + fc];
         if (fc == FC_WAVE) {
             const bool sg = b0 == S->level_ptr[(size_t)lv * FC_COUNT + FC_WAVE];                            // single-GPU schedule: the bucket is sorted by order
-            const int nt = sg ? tiny_split[lv] : 0;
+            const int nt = sg ? P.tiny_split[lv] : 0;
             int fl = top_mode;
-            if (V.fastpiv && wave_mmin[lv] <= 16) {      // fronts of order <= 16: four per wavefront on the static-order path first; what it accepts is skipped below
-                const int n16 = sg ? tiny16[lv] : nb;
+            if (V.fastpiv && P.wave_mmin[lv] <= 16) {      // fronts of order <= 16: four per wavefront on the static-order path first; what it accepts is skipped below
+                const int n16 = sg ? P.tiny16[lv] : nb;
                 // (the kernel raises qstat[4] for a front it rejects only when NO strict launch follows -- optimistic && n16 == nb: behind a strict
                 // launch the rejected front is simply the strict kernel's, and raising the flag there made factor() repeat the whole factorisation
                 // with the full schedule and drop the optimistic one for the life of the handle: ADVICE r04)
@@ -1459,38 +735,39 @@ public:
         } else if (fc == FC_LDS64) {
             LAUNCH(KK_FRONT_LDS64, (k_front_reg<64, 8>), dim3(nb), dim3(64), rl, stream, V, b0, top_mode);
         } else if (fc == FC_LDS128) {
-            const int nm = (b0 == S->level_ptr[(size_t)lv * FC_COUNT + FC_LDS128]) ? mid_split[lv] : 0;    // single-GPU schedule only
+            const int nm = (b0 == S->level_ptr[(size_t)lv * FC_COUNT + FC_LDS128]) ? P.mid_split[lv] : 0;    // single-GPU schedule only
             const int fl = top_mode | (V.fastpiv ? 2 : 0);
             // (measured and not kept, r05: in the optimistic schedule the strict launch only on the fronts with > 16 pivots and on a device-built list of
             // the fronts the static-order launch rejected -- 342 of them on synth_1e6 -- instead of the whole bucket: 18.21 against 18.16 ms.  The
             // 60-150 us of the strict launches are those fronts' own latency chains, not the workgroups that find nothing to do.)
             if (V.fastpiv) {      // fronts with <= 16 pivots: static-order path first; what it accepts is skipped by the launch behind it
                 // (<256, 6, true> cut to 128 VGPRs = 4 workgroups per CU: 2.24 -> 2.13 ms of front_lds128 on synth_1e6; the same cut of <256, 8, true> gained nothing and is gone)
-                if (nm > 0) LAUNCH(KK_FRONT_LDS128, (k_front_reg<256, 6, true, 4>), dim3(nm), dim3(256), mid_lds[lv], stream, V, b0, top_mode);
+                if (nm > 0) LAUNCH(KK_FRONT_LDS128, (k_front_reg<256, 6, true, 4>), dim3(nm), dim3(256), P.mid_lds[lv], stream, V, b0, top_mode);
                 if (nb - nm > 0) LAUNCH(KK_FRONT_LDS128, (k_front_reg<256, 8, true>), dim3(nb - nm), dim3(256), rl, stream, V, b0 + nm, top_mode);
             }
-            if (nm > 0) LAUNCH(KK_FRONT_LDS128, (k_front_reg<256, 6>), dim3(nm), dim3(256), mid_lds[lv], stream, V, b0, fl);
+            if (nm > 0) LAUNCH(KK_FRONT_LDS128, (k_front_reg<256, 6>), dim3(nm), dim3(256), P.mid_lds[lv], stream, V, b0, fl);
             if (nb - nm > 0) LAUNCH(KK_FRONT_LDS128, (k_front_reg<256, 8>), dim3(nb - nm), dim3(256), rl, stream, V, b0 + nm, fl);
         } else {
             const bool single = (b0 == S->level_ptr[(size_t)lv * FC_COUNT + FC_BIG]) && !multi;       // the single-GPU schedule
-            if ((single || multi) && grouped && lv >= S->grp_cut_level) {
+            if ((single || multi) && P.grouped && lv >= S->grp_cut_level) {
                 // the chain groups whose first link sits on this level, one launch each (the multi-GPU schedules have their own group lists)
-                if (!(single && lv_asm_skip[lv])) launch_assemble(mm, nb, b0, top_mode);
-                return launch_groups(lv, single ? gs_single : (top_mode ? *gs_cur : gs_local));
+                if (!(single && P.lv_asm_skip[lv])) launch_assemble(mm, nb, b0, top_mode);
+                return launch_groups(lv, top_mode ? 1 + grp_step : 0);
             }
             if (!single) { const bool sm = mm <= 640; return launch_big(lv, b0, sm ? b1 : b0, b1, top_mode, mm, kk, sm ? tiles64 : 0, sm ? 0 : tiles, false); }
-            return launch_big(lv, b0, b0 + big_split[lv], b1, top_mode, mm, kk, part_tiles[0][lv], part_tiles[1][lv], true);
+            return launch_big(lv, b0, b0 + P.big_split[lv], b1, top_mode, mm, kk, P.part_tiles[0][lv], P.part_tiles[1][lv], true);
         }
         return true;
     }
     // the chain groups whose first link sits on level lv: pivot blocks + leading blocks, rows below, rank-(<= 256) updates
-    bool launch_groups(int lv, GrpSched& G) {
+    bool launch_groups(int lv, int gi) {      // gi: the grouped schedule P.grp[gi]
+        const GrpSched& G = P.grp[gi]; const LaEvents& E = la_ev[1 + gi];
         const int b0 = G.g0[lv], b1 = G.g1[lv], bs = b0 + G.split[lv];
         if (b1 == b0) return true;
         {
             // as many 64-row blocks per row-block workgroup as it takes for the launch to fit the chip (one workgroup per CU)
             int rbw = 1;
-            while (rbw < grp_rbw_max && (b1 - b0) * (4 + (G.nrb[lv] + rbw - 1) / rbw) > 256) rbw *= 2;
+            while (rbw < knobs.grp_rbw_max && (b1 - b0) * (4 + (G.nrb[lv] + rbw - 1) / rbw) > 256) rbw *= 2;
             const int nrbw = (G.nrb[lv] + rbw - 1) / rbw;
             const int st = ((b1 - b0) * (4 + nrbw) <= 256) ? 1 : 0;
             const size_t lds = std::max(diag_lds_bytes(64, 64), GRP_DB_BYTES + trsm_lds_bytes(64, st != 0));
@@ -1503,39 +780,30 @@ public:
         if (G.la2[lv] > 0) {      // (also while profile() records its events: the per-kernel times are those of the TIMED schedule, look-ahead stream included)
             // part 1 in 64 x 64 tiles where the 128 x 128 ones would leave most of the chip idle (k_big_schur_p1); the fronts of the list that are not split
             // get their whole update from a launch of their own then
-            if (p1_small_tiles && G.la1[lv] * nb <= 512) {
+            if (knobs.p1_small && G.la1[lv] * nb <= 512) {
                 LAUNCH(KK_BIG_SCHUR, k_big_schur_p1, dim3(G.p1t[lv], nb), dim3(1024), 0, stream, V, bs);
                 if (G.nsplit[lv] < nb) LAUNCH(KK_BIG_SCHUR, k_big_schur, dim3(schur_grid(G.la3[lv]), nb), dim3(SCHUR_NT), 0, stream, V, bs, 4, 0, 0);
             } else LAUNCH(KK_BIG_SCHUR, k_big_schur, dim3(schur_grid(G.la1[lv]), nb), dim3(SCHUR_NT), 0, stream, V, bs, 1, 0, 0);
-            HIPCHK(hipEventRecord(G.evA[lv], stream));
-            HIPCHK(hipStreamWaitEvent(stream2, G.evA[lv], 0));
+            HIPCHK(hipEventRecord(E.A[lv], stream));
+            HIPCHK(hipStreamWaitEvent(stream2, E.A[lv], 0));
             launch_part2(bs, nb, G.la2[lv]);
-            HIPCHK(hipEventRecord(G.evB[lv], stream2));
-            la_last = G.evB[lv]; la_pending = true;
+            HIPCHK(hipEventRecord(E.B[lv], stream2));
+            la_last = E.B[lv]; la_pending = true;
         } else if (G.tiles[lv] > 0) LAUNCH(KK_BIG_SCHUR, k_big_schur, dim3(schur_grid(G.tiles[lv]), nb), dim3(SCHUR_NT), 0, stream, V, bs, 0, 0, 0);
         return true;
     }
-    int grp_rbw_max = 8;
-    int ntfuse = 0;
     // A handful of small fronts on a level whose bulk is elsewhere (synth_1e6: 3 fronts of order <= 128 next to 2 045 big ones; one front of order <= 64
     // next to 943 of order <= 128) is a launch of 1-3 workgroups running their strict pivot loops for 40-90 us with the chip idle.  The buckets of one level
     // are independent: in the eager (multi-stream) schedule such a bucket goes to the third stream, next to the level's main launches.
     std::vector<hipEvent_t> side_evF, side_evJ; bool side_on = !knob_disabled("side_small"); static constexpr int SIDE_MAX_FRONTS = 16;
-    // runs of consecutive tree levels that hold nothing but one-wavefront fronts (order <= 32): one persistent data-flow launch each (k_front_df)
-    struct DfRun { int lv0, lv1, tab0, nlev, nq; };
-    std::vector<DfRun> df_runs; std::vector<int> df_run_at; const DfLevel* d_dftab = nullptr; int df_grid_cap = 0;
-    bool df_on = !knob_disabled("front_df");
-    int lc_levels = 0, lc_nchains = 0;      // leaf chains: the tree levels below lc_levels are lc_nchains chains of fronts of order <= 16 (k_leaf_chain)
-    bool p1_small_tiles = !knob_disabled("p1_small");
+    const DfLevel* d_dftab = nullptr; int df_grid_cap = 0;      // k_front_df: the levels of the runs (P.df_tab), the largest grid whose workgroups are all resident
     // part 2 of the split updates (second stream, next to the following group's pivot chain): 128 x 128 tiles on 16 wavefronts, or quarter tiles on 4
     // wavefronts that fit on the CUs a k_grp_fused workgroup occupies (kernels_big.hip.inc: k_big_schur_q / _w)
     void launch_part2(int b0, int nb, int ntiles) {
         const int nvirt = ((ntiles + 7) / 8) * 32;
-        const int wgs = (int)std::min<long long>(nvirt, 4ll * la_wgs);
+        const int wgs = (int)std::min<long long>(nvirt, 4ll * knobs.la_wgs);
         LAUNCH_ON(KK_BIG_SCHUR, stream2, k_big_schur_q, dim3(wgs, nb), dim3(256), 0, stream2, V, b0, ntiles);
     }
-    std::vector<char> asm_fast_ok;          // per launch-list entry: the front can take k_big_assemble2's fast path (the number of children it pulls; 0: it cannot)
-    std::vector<int> h_asmcut;              // per launch-list entry: FrontMeta::asmcut
     // The column-chunk kernel pays where a level is MANY fronts of a few hundred rows (short columns: the one-wavefront-per-column kernel runs at the
     // latency of its load chain there) and every front can take its fast path (at most ASM_MAXCH children to pull, not an in-place link with other
     // children, no arena): measured 4.1 -> 2.0 ms per factorisation on synth_1e6, but 3.4 -> 8.7 ms on MBndryCntrl_3D 30, whose levels are a
@@ -1549,7 +817,7 @@ public:
         // once only their panel columns are assembled -- the MBndryCntrl_3D family; measured slower there than the column kernel, 7.65 against 7.16 ms.)
         bool v2 = !top_mode;
         int maxch = 1, ncut = 0, cutmax = 0;
-        for (int q = b0; q < b0 + nfronts && v2; ++q) { v2 = asm_fast_ok[q] != 0; maxch = std::max(maxch, (int)asm_fast_ok[q]); if (h_asmcut[q]) { ++ncut; cutmax = std::max(cutmax, h_asmcut[q] > 0 ? h_asmcut[q] : 0); } }
+        for (int q = b0; q < b0 + nfronts && v2; ++q) { v2 = P.asm_fast_ok[q] != 0; maxch = std::max(maxch, (int)P.asm_fast_ok[q]); if (P.asmcut[q]) { ++ncut; cutmax = std::max(cutmax, P.asmcut[q] > 0 ? P.asmcut[q] : 0); } }
         v2 = v2 && (size_t)maxch * ldi * sizeof(int) <= (size_t)158 * 1024 && (nfronts >= 32 && maxch <= 6);
         if (!v2) { LAUNCH(KK_BIG_ASSEMBLE, k_big_assemble, dim3((mm + 3) / 4, nfronts), dim3(256), 0, stream, V, b0, top_mode); return; }
         const int ncols = (ncut == nfronts) ? std::min(mm, cutmax) : mm;      // (every front stops at its asmcut: no workgroups for the columns behind the largest of them)
@@ -1561,13 +829,13 @@ public:
     // 128 x 128 tiles / 1024 threads on [bs, b1)
     bool launch_big(int lv, int b0, int bs, int b1, int top_mode, int mm, int kk, int tiles_small, int tiles, bool single) {
         const int nball = b1 - b0;
-        if (!(single && lv_asm_skip[lv])) launch_assemble(mm, nball, b0, top_mode);
+        if (!(single && P.lv_asm_skip[lv])) launch_assemble(mm, nball, b0, top_mode);
         const int nrb = (mm + 63) / 64;
-        if (fuse_dt && (single || multi) && kk <= 64 && nball * (1 + nrb) <= fuse_dt_maxwg) {      // (multi-GPU: local subtrees and replicated top alike; the per-kernel profile books the fused launch under the pivot blocks)
+        if (knobs.fuse_dt && (single || multi) && kk <= 64 && nball * (1 + nrb) <= knobs.fuse_dt_maxwg) {      // (multi-GPU: local subtrees and replicated top alike; the per-kernel profile books the fused launch under the pivot blocks)
             // few fronts on the level: pivot block + panel solve in one flag-synchronised launch (k_big_diag_trsm)
             const size_t lds = std::max(diag_lds_bytes(kk, 64),
                                         trsm_lds_bytes(kk, true));
-            const int ntu = (lv_narrow_tiles[lv] > 0 && nball * (1 + nrb + lv_narrow_tiles[lv]) <= 256) ? lv_narrow_tiles[lv] : 0;      // (one workgroup per CU: the far part of a group-end update may own the rest of the chip)
+            const int ntu = (P.lv_narrow_tiles[lv] > 0 && nball * (1 + nrb + P.lv_narrow_tiles[lv]) <= 256) ? P.lv_narrow_tiles[lv] : 0;      // (one workgroup per CU: the far part of a group-end update may own the rest of the chip)
             LAUNCH(KK_BIG_DIAG, k_big_diag_trsm, dim3(nball, 1 + nrb + ntu), dim3(256), lds, stream, V, b0, nrb);
             if (ntu > 0) return true;         // ... and so did the narrow updates
             goto updates;
@@ -1581,16 +849,16 @@ public:
         if (b1 == bs) return true;
         const int nb = b1 - bs;
         b0 = bs;
-        if (single && la_full[lv] && la_pending) {       // a full update may touch what an earlier part 2 is still writing
+        if (single && P.la_full[lv] && la_pending) {       // a full update may touch what an earlier part 2 is still writing
             HIPCHK(hipStreamWaitEvent(stream, la_last, 0)); la_pending = false;
         }
-        if (single && la_tiles2[lv] > 0) {
-            LAUNCH(KK_BIG_SCHUR, k_big_schur, dim3(schur_grid(la_tiles1[lv]), nb), dim3(SCHUR_NT), 0, stream, V, b0, 1, 0, 0);
-            HIPCHK(hipEventRecord(la_evA[lv], stream));
-            HIPCHK(hipStreamWaitEvent(stream2, la_evA[lv], 0));
-            launch_part2(b0, nb, la_tiles2[lv]);
-            HIPCHK(hipEventRecord(la_evB[lv], stream2));
-            la_last = la_evB[lv]; la_pending = true;
+        if (single && P.la_tiles2[lv] > 0) {
+            LAUNCH(KK_BIG_SCHUR, k_big_schur, dim3(schur_grid(P.la_tiles1[lv]), nb), dim3(SCHUR_NT), 0, stream, V, b0, 1, 0, 0);
+            HIPCHK(hipEventRecord(la_ev[0].A[lv], stream));
+            HIPCHK(hipStreamWaitEvent(stream2, la_ev[0].A[lv], 0));
+            launch_part2(b0, nb, P.la_tiles2[lv]);
+            HIPCHK(hipEventRecord(la_ev[0].B[lv], stream2));
+            la_last = la_ev[0].B[lv]; la_pending = true;
         } else if (tiles > 0) LAUNCH(KK_BIG_SCHUR, k_big_schur, dim3(schur_grid(tiles), nb), dim3(SCHUR_NT), 0, stream, V, b0, 0, 0, 0);
         return true;
     }
@@ -1629,11 +897,11 @@ public:
         LAUNCH(KK_STATS, k_factor_prologue, dim3(grid1d(n)), dim3(256), 0, stream, V);
         LAUNCH(KK_GATHER_SCALE, k_gather_values, dim3(grid1d(Sy.nnz_a)), dim3(256), 0, stream, V);
         enqueue_scaling();
-        const int lc = (optimistic && lc_levels > 0) ? lc_levels : 0;      // the leaf chains: one launch for their levels (optimistic schedule only: no strict kernel behind it)
-        if (lc > 0) LAUNCH(KK_FRONT_WAVE, k_leaf_chain, dim3((lc_nchains + 3) / 4), dim3(64), 0, stream, V, lc_nchains);
+        const int lc = (optimistic && P.lc_levels > 0) ? P.lc_levels : 0;      // the leaf chains: one launch for their levels (optimistic schedule only: no strict kernel behind it)
+        if (lc > 0) LAUNCH(KK_FRONT_WAVE, k_leaf_chain, dim3((P.lc_nchains + 3) / 4), dim3(64), 0, stream, V, P.lc_nchains);
         for (int lv = lc; lv < Sy.num_levels; ++lv) {
-            if (optimistic && df_run_at[lv] >= 0) {      // a run of levels of one-wavefront fronts: one persistent data-flow launch (optimistic schedule only: no strict kernels behind it)
-                const DfRun& R = df_runs[df_run_at[lv]];
+            if (optimistic && P.df_run_at[lv] >= 0) {      // a run of levels of one-wavefront fronts: one persistent data-flow launch (optimistic schedule only: no strict kernels behind it)
+                const DfRun& R = P.df_runs[P.df_run_at[lv]];
                 LAUNCH(KK_FRONT_WAVE, k_front_df, dim3(std::min(R.nq, df_grid_cap)), dim3(64), 0, stream, V, d_dftab + R.tab0, R.nlev, R.nq);
                 lv = R.lv1; continue;
             }
@@ -1647,13 +915,13 @@ public:
                 const int b0 = Sy.level_ptr[(size_t)lv * FC_COUNT + fc], b1 = Sy.level_ptr[(size_t)lv * FC_COUNT + fc + 1];
                 if (b1 == b0) continue;
                 // (the eager schedule only: a multi-stream hipGraph is what factor_once() avoids; not next to the three-stream chain look-ahead)
-                const bool side = side_on && la_any && !multi && fc != FC_BIG && b1 - b0 <= SIDE_MAX_FRONTS && lvl_max >= 8 * (b1 - b0) && lvl_fronts > b1 - b0;
-                if (!side) { launch_bucket(lv, fc, b0, b1, 0, big_maxm[lv], big_maxk[lv], big_tiles[lv], big_tiles64[lv]); continue; }
+                const bool side = side_on && P.la_any && !multi && fc != FC_BIG && b1 - b0 <= SIDE_MAX_FRONTS && lvl_max >= 8 * (b1 - b0) && lvl_fronts > b1 - b0;
+                if (!side) { launch_bucket(lv, fc, b0, b1, 0, P.single.maxm[lv], P.single.maxk[lv], P.single.tiles[lv], P.single.tiles64[lv]); continue; }
                 if ((int)side_evF.size() < Sy.num_levels) { side_evF.resize(Sy.num_levels, nullptr); side_evJ.resize(Sy.num_levels, nullptr); }
                 if (!side_evF[lv]) { HIPCHK(hipEventCreateWithFlags(&side_evF[lv], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&side_evJ[lv], hipEventDisableTiming)); }
                 if (!side_open) { HIPCHK(hipEventRecord(side_evF[lv], stream)); HIPCHK(hipStreamWaitEvent(stream3, side_evF[lv], 0)); side_open = true; }      // behind the level below
                 std::swap(stream, stream3);
-                const bool ok = launch_bucket(lv, fc, b0, b1, 0, big_maxm[lv], big_maxk[lv], big_tiles[lv], big_tiles64[lv]);
+                const bool ok = launch_bucket(lv, fc, b0, b1, 0, P.single.maxm[lv], P.single.maxk[lv], P.single.tiles[lv], P.single.tiles64[lv]);
                 std::swap(stream, stream3);
                 if (!ok) return false;
             }
@@ -1702,7 +970,7 @@ public:
         // A factorisation with look-ahead forks onto the second stream: it is launched eagerly (measured equal to the graph
         // replay on these ~10^3-launch sequences, whose kernels are long), because a two-stream hipGraph replays up to 1.5x
         // slower once another solver's graphs have been created and destroyed in the same process (ROCm 7.2).
-        if (opt.use_graph && !la_any) {
+        if (opt.use_graph && !P.la_any) {
             if (graph_pivtol != V.pivtol || graph_pivtol2 != V.pivtol2) {      // (both schedules were captured with the old thresholds)
                 destroy_factor_graphs();
             }
@@ -1754,13 +1022,13 @@ public:
                 LAUNCH(KK_SOLVE_PERM, k_refine_spmv, dim3(grid1d(n)), dim3(256), 0, stream, V);
             }
             auto lds_solve = [](int mmax, int kmax) { return (size_t)(mmax + 3 * kmax) * sizeof(double) + 16; };
-            if (!chain_segs.empty()) LAUNCH(KK_SOLVE_PERM, k_bump_epoch, dim3(1), dim3(64), 0, stream, V.sepoch);
-            int lcs = (pair_solve && lc_levels > 0) ? lc_levels : 0;
-            for (int lv = 0; lv < lcs; ++lv) if (seg_at_lv0[lv] >= 0) { lcs = 0; break; }      // (a small tree: one data-flow sweep already covers these levels)
-            if (lcs > 0) LAUNCH(KK_FWD_WAVE, k_fwd_leafchain, dim3((lc_nchains + 3) / 4), dim3(64), 0, stream, V, lc_nchains);
+            if (!P.chain_segs.empty()) LAUNCH(KK_SOLVE_PERM, k_bump_epoch, dim3(1), dim3(64), 0, stream, V.sepoch);
+            int lcs = (P.pair_solve && P.lc_levels > 0) ? P.lc_levels : 0;
+            for (int lv = 0; lv < lcs; ++lv) if (P.seg_at_lv0[lv] >= 0) { lcs = 0; break; }      // (a small tree: one data-flow sweep already covers these levels)
+            if (lcs > 0) LAUNCH(KK_FWD_WAVE, k_fwd_leafchain, dim3((P.lc_nchains + 3) / 4), dim3(64), 0, stream, V, P.lc_nchains);
             for (int lv = lcs; lv < Sy.num_levels; ++lv) {
-                if (seg_at_lv0[lv] >= 0) {      // a run of pure chain levels: one sync-free launch for all of them
-                    const ChainSeg& sg = chain_segs[seg_at_lv0[lv]];
+                if (P.seg_at_lv0[lv] >= 0) {      // a run of pure chain levels: one sync-free launch for all of them
+                    const ChainSeg& sg = P.chain_segs[P.seg_at_lv0[lv]];
                     if (gate_on && !gate_entered) { if (gate_valid) HIPCHK(hipStreamWaitEvent(stream, gate_last, 0)); gate_entered = true; }      // (solve contexts: one chain section at a time)
                     LAUNCH(KK_FWD_BIG, k_fwd_chain, dim3(sg.nwg_f), dim3(320), 0, stream, V, sg.wgf0);
                     lv = sg.lv1; continue;
@@ -1768,23 +1036,23 @@ public:
                 for (int fc = 0; fc < FC_COUNT; ++fc) {
                     const int b0 = Sy.level_ptr[(size_t)lv * FC_COUNT + fc], b1 = Sy.level_ptr[(size_t)lv * FC_COUNT + fc + 1];
                     if (b1 == b0) continue;
-                    if (fc == FC_WAVE && pair_solve && wave_mmax[lv] <= 16) LAUNCH(KK_FWD_WAVE, (k_fwd_pair<16, 16>), dim3((b1 - b0 + 3) / 4), dim3(64), 0, stream, V, b0, b1 - b0);
-                    else if (fc == FC_WAVE && pair_solve && wave_kmax[lv] <= 16) LAUNCH(KK_FWD_WAVE, (k_fwd_pair<16>), dim3((b1 - b0 + 1) / 2), dim3(64), 0, stream, V, b0, b1 - b0);
-                    else if (fc == FC_WAVE && pair_solve)                   LAUNCH(KK_FWD_WAVE, (k_fwd_pair<32>), dim3((b1 - b0 + 1) / 2), dim3(64), 0, stream, V, b0, b1 - b0);
+                    if (fc == FC_WAVE && P.pair_solve && P.wave_mmax[lv] <= 16) LAUNCH(KK_FWD_WAVE, (k_fwd_pair<16, 16>), dim3((b1 - b0 + 3) / 4), dim3(64), 0, stream, V, b0, b1 - b0);
+                    else if (fc == FC_WAVE && P.pair_solve && P.wave_kmax[lv] <= 16) LAUNCH(KK_FWD_WAVE, (k_fwd_pair<16>), dim3((b1 - b0 + 1) / 2), dim3(64), 0, stream, V, b0, b1 - b0);
+                    else if (fc == FC_WAVE && P.pair_solve)                   LAUNCH(KK_FWD_WAVE, (k_fwd_pair<32>), dim3((b1 - b0 + 1) / 2), dim3(64), 0, stream, V, b0, b1 - b0);
                     else if (fc == FC_WAVE)   LAUNCH(KK_FWD_WAVE, (k_fwd<64>),  dim3(b1 - b0), dim3(64),  lds_solve(32, 32),   stream, V, b0, 0);
                     else if (fc == FC_LDS64)  LAUNCH(KK_FWD_LDS,  (k_fwd<64>),  dim3(b1 - b0), dim3(64),  lds_solve(64, 64),   stream, V, b0, 0);
                     else if (fc == FC_LDS128) LAUNCH(KK_FWD_LDS,  (k_fwd<256>), dim3(b1 - b0), dim3(256), lds_solve(128, 128), stream, V, b0, 0);
-                    else if (big_last1[lv] > big_last0[lv]) {
-                           const int g0 = big_last0[lv], ng = big_last1[lv] - g0;
-                           if (lv_allsolo[lv] && big_maxk[lv] <= 64) LAUNCH(KK_FWD_BIG, k_fwd_solo64, dim3((big_maxm[lv] + 63) / 64 + 1, ng), dim3(256), 0, stream, V, g0);
-                           else if (lv_allsolo[lv]) LAUNCH(KK_FWD_BIG, k_fwd_solo, dim3((big_maxm[lv] + 63) / 64 + 1, ng), dim3(256), 0, stream, V, g0);
+                    else if (P.single.last1[lv] > P.single.last0[lv]) {
+                           const int g0 = P.single.last0[lv], ng = P.single.last1[lv] - g0;
+                           if (P.single.allsolo[lv] && P.single.maxk[lv] <= 64) LAUNCH(KK_FWD_BIG, k_fwd_solo64, dim3((P.single.maxm[lv] + 63) / 64 + 1, ng), dim3(256), 0, stream, V, g0);
+                           else if (P.single.allsolo[lv]) LAUNCH(KK_FWD_BIG, k_fwd_solo, dim3((P.single.maxm[lv] + 63) / 64 + 1, ng), dim3(256), 0, stream, V, g0);
                            else { LAUNCH(KK_FWD_BIG, k_fwd_grp, dim3(ng), dim3(256), 0, stream, V, g0, 0);
-                                  LAUNCH(KK_FWD_BIG_UPD, k_fwd_grp_upd, dim3((big_maxm[lv] + 63) / 64, ng), dim3(256), 0, stream, V, g0); } }
+                                  LAUNCH(KK_FWD_BIG_UPD, k_fwd_grp_upd, dim3((P.single.maxm[lv] + 63) / 64, ng), dim3(256), 0, stream, V, g0); } }
                 }
             }
             for (int lv = Sy.num_levels - 1; lv >= lcs; --lv) {
-                if (seg_at_lv1[lv] >= 0) {
-                    const ChainSeg& sg = chain_segs[seg_at_lv1[lv]];
+                if (P.seg_at_lv1[lv] >= 0) {
+                    const ChainSeg& sg = P.chain_segs[P.seg_at_lv1[lv]];
                     LAUNCH(KK_BWD_BIG, k_bwd_chain, dim3(sg.nwg_b), dim3(320), 0, stream, V, sg.wgb0);
                     if (gate_on && gate_mine) { HIPCHK(hipEventRecord(gate_mine, stream)); gate_last = gate_mine; gate_valid = true; }
                     lv = sg.lv0; continue;
@@ -1792,23 +1060,23 @@ public:
                 for (int fc = 0; fc < FC_COUNT; ++fc) {
                     const int b0 = Sy.level_ptr[(size_t)lv * FC_COUNT + fc], b1 = Sy.level_ptr[(size_t)lv * FC_COUNT + fc + 1];
                     if (b1 == b0) continue;
-                    if (fc == FC_WAVE && pair_solve && wave_mmax[lv] <= 16) LAUNCH(KK_BWD_WAVE, (k_bwd_pair<16, 16>), dim3((b1 - b0 + 3) / 4), dim3(64), 0, stream, V, b0, b1 - b0);
-                    else if (fc == FC_WAVE && pair_solve && wave_kmax[lv] <= 16) LAUNCH(KK_BWD_WAVE, (k_bwd_pair<16>), dim3((b1 - b0 + 1) / 2), dim3(64), 0, stream, V, b0, b1 - b0);
-                    else if (fc == FC_WAVE && pair_solve)                   LAUNCH(KK_BWD_WAVE, (k_bwd_pair<32>), dim3((b1 - b0 + 1) / 2), dim3(64), 0, stream, V, b0, b1 - b0);
+                    if (fc == FC_WAVE && P.pair_solve && P.wave_mmax[lv] <= 16) LAUNCH(KK_BWD_WAVE, (k_bwd_pair<16, 16>), dim3((b1 - b0 + 3) / 4), dim3(64), 0, stream, V, b0, b1 - b0);
+                    else if (fc == FC_WAVE && P.pair_solve && P.wave_kmax[lv] <= 16) LAUNCH(KK_BWD_WAVE, (k_bwd_pair<16>), dim3((b1 - b0 + 1) / 2), dim3(64), 0, stream, V, b0, b1 - b0);
+                    else if (fc == FC_WAVE && P.pair_solve)                   LAUNCH(KK_BWD_WAVE, (k_bwd_pair<32>), dim3((b1 - b0 + 1) / 2), dim3(64), 0, stream, V, b0, b1 - b0);
                     else if (fc == FC_WAVE)   LAUNCH(KK_BWD_WAVE, (k_bwd<64>),  dim3(b1 - b0), dim3(64),  lds_solve(32, 32),   stream, V, b0);
                     else if (fc == FC_LDS64)  LAUNCH(KK_BWD_LDS,  (k_bwd<64>),  dim3(b1 - b0), dim3(64),  lds_solve(64, 64),   stream, V, b0);
                     else if (fc == FC_LDS128) LAUNCH(KK_BWD_LDS,  (k_bwd<256>), dim3(b1 - b0), dim3(256), lds_solve(128, 128), stream, V, b0);
-                    else if (big_last1[lv] > big_last0[lv]) {
-                           const int g0 = big_last0[lv], ng = big_last1[lv] - g0;
-                           if (!Sy.solve_group && big_maxk[lv] <= 64) {      // one link per unit: load-hoisted kernels
-                               LAUNCH(KK_BWD_BIG_DOT, k_bwd_dot64, dim3((big_maxm[lv] + 255) / 256, ng), dim3(256), 0, stream, V, g0);
+                    else if (P.single.last1[lv] > P.single.last0[lv]) {
+                           const int g0 = P.single.last0[lv], ng = P.single.last1[lv] - g0;
+                           if (!Sy.solve_group && P.single.maxk[lv] <= 64) {      // one link per unit: load-hoisted kernels
+                               LAUNCH(KK_BWD_BIG_DOT, k_bwd_dot64, dim3((P.single.maxm[lv] + 255) / 256, ng), dim3(256), 0, stream, V, g0);
                                LAUNCH(KK_BWD_BIG, k_bwd_fin64, dim3(ng), dim3(256), 0, stream, V, g0);
                            } else {
-                               LAUNCH(KK_BWD_BIG_DOT, k_bwd_grp_dot, dim3((big_maxm[lv] + 255) / 256, ng), dim3(256), 0, stream, V, g0);
+                               LAUNCH(KK_BWD_BIG_DOT, k_bwd_grp_dot, dim3((P.single.maxm[lv] + 255) / 256, ng), dim3(256), 0, stream, V, g0);
                                LAUNCH(KK_BWD_BIG, k_bwd_grp, dim3(ng), dim3(256), 0, stream, V, g0); } }
                 }
             }
-            if (lcs > 0) LAUNCH(KK_BWD_WAVE, k_bwd_leafchain, dim3((lc_nchains + 3) / 4), dim3(64), 0, stream, V, lc_nchains);
+            if (lcs > 0) LAUNCH(KK_BWD_WAVE, k_bwd_leafchain, dim3((P.lc_nchains + 3) / 4), dim3(64), 0, stream, V, P.lc_nchains);
         }
         if (nref > 0) LAUNCH(KK_SOLVE_PERM, k_refine_finish, dim3(grid1d(n)), dim3(256), 0, stream, V);
         HIPCHK(hipGetLastError());
@@ -1953,13 +1221,13 @@ public:
             if (!ok) return false;
             for (int c = 1; c < nctx; ++c) {
                 HIPCHK(hipEventRecord(sctx[c].done, sctx[c].strm)); HIPCHK(hipStreamWaitEvent(stream, sctx[c].done, 0));
-                if (!chain_segs.empty()) hipLaunchKernelGGL(k_merge_err, dim3(1), dim3(64), 0, stream, V.sepoch + 1, (const int*)(sctx[c].sepoch + 1));
+                if (!P.chain_segs.empty()) hipLaunchKernelGGL(k_merge_err, dim3(1), dim3(64), 0, stream, V.sepoch + 1, (const int*)(sctx[c].sepoch + 1));
             }
         } else
             for (int r = 0; r < nrhs; ++r) if (!solve_one(dsrc + (size_t)r * lds_, drhs + (size_t)r * ld)) return false;
         if (timed) {
             HIPCHK(hipEventRecord(ev1, stream));
-            if (!chain_segs.empty()) HIPCHK(hipMemcpyAsync(h_stats + 6, V.sepoch + 1, sizeof(int), hipMemcpyDeviceToHost, stream));
+            if (!P.chain_segs.empty()) HIPCHK(hipMemcpyAsync(h_stats + 6, V.sepoch + 1, sizeof(int), hipMemcpyDeviceToHost, stream));
             HIPCHK(hipStreamSynchronize(stream));
             float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev0, ev1)); solve_ms = ms;
             if (V.strace) {
@@ -1973,7 +1241,7 @@ public:
                     fclose(f);
                 }
             }
-            if (!chain_segs.empty() && h_stats[6] != 0) { err_ = "solve: a chain sweep timed out waiting for its predecessor (workgroups not co-resident?)"; return false; }
+            if (!P.chain_segs.empty() && h_stats[6] != 0) { err_ = "solve: a chain sweep timed out waiting for its predecessor (workgroups not co-resident?)"; return false; }
         }
         return true;
     }
@@ -2149,10 +1417,10 @@ public:
         auto lds_solve = [](int mmax, int kmax) { return (size_t)(mmax + 3 * kmax) * sizeof(double) + 16; };
         for (int q = 0; q < Sy.num_levels; ++q) {
             const int lv = forward ? q : Sy.num_levels - 1 - q;
-            if (top_mode && use_segs && !chain_segs.empty()) {      // runs of pure chain levels of the fronts every rank holds: the sync-free sweeps (pure links have no child from outside)
-                const int sgi = forward ? seg_at_lv0[lv] : seg_at_lv1[lv];
+            if (top_mode && use_segs && !P.chain_segs.empty()) {      // runs of pure chain levels of the fronts every rank holds: the sync-free sweeps (pure links have no child from outside)
+                const int sgi = forward ? P.seg_at_lv0[lv] : P.seg_at_lv1[lv];
                 if (sgi >= 0) {
-                    const ChainSeg& sg = chain_segs[sgi];
+                    const ChainSeg& sg = P.chain_segs[sgi];
                     if (forward) hipLaunchKernelGGL(k_fwd_chain, dim3(sg.nwg_f), dim3(320), 0, stream, V, sg.wgf0);
                     else hipLaunchKernelGGL(k_bwd_chain, dim3(sg.nwg_b), dim3(320), 0, stream, V, sg.wgb0);
                     q += sg.lv1 - sg.lv0; continue;
@@ -2186,7 +1454,7 @@ public:
     }
     // the phase entry points (the caller runs the collectives between them: ipopt_amd.multigpu.DistributedKKT) exist for the classic mapping,
     // ONE exchange step; with the subtree-to-subcube mapping the sequence runs behind the ordinary entry points (factor_dist / solve_dist)
-    bool one_step(const char* who) { if (ndepth != 1) { err_ = std::string(who) + ": the phase entry points serve one exchange step (subcube = 0); set a communicator and use factor / solve"; return false; } return true; }
+    bool one_step(const char* who) { if (P.ndepth != 1) { err_ = std::string(who) + ": the phase entry points serve one exchange step (subcube = 0); set a communicator and use factor / solve"; return false; } return true; }
     bool factor_local(const double* dvals) {
         DeviceGuard guard(dev);
         if (!one_step("factor_local")) return false;
@@ -2197,13 +1465,13 @@ public:
         return true;
     }
     bool report_to_arena(int kind) {
-        const JoinList& J = join[kind];
+        const JoinList& J = P.join[kind];
         if (J.count > 0) hipLaunchKernelGGL(k_arena_assemble, dim3((J.maxm + 3) / 4, J.count), dim3(256), 0, stream, V, J.base, J.who);
         HIPCHK(hipGetLastError());
         return true;
     }
     bool report_to_top_rhs(int kind) {
-        const JoinList& J = join[kind];
+        const JoinList& J = P.join[kind];
         if (J.count > 0) hipLaunchKernelGGL(k_top_rhs_assemble, dim3(J.count), dim3(256), 0, stream, V, J.base, J.who);
         HIPCHK(hipGetLastError());
         return true;
@@ -2223,15 +1491,15 @@ public:
         hipLaunchKernelGGL(k_factor_prologue, dim3(grid1d(n)), dim3(256), 0, stream, V);
         hipLaunchKernelGGL(k_gather_values, dim3(grid1d(Sy.nnz_a)), dim3(256), 0, stream, V);
         enqueue_scaling();
-        if (!launch_fronts(sch_local, 0)) return false;
-        HIPCHK(hipMemsetAsync(V.arena, 0, (size_t)arena_doubles * sizeof(double), stream));
+        if (!launch_fronts(P.local, 0)) return false;
+        HIPCHK(hipMemsetAsync(V.arena, 0, (size_t)P.ex.arena_doubles * sizeof(double), stream));
         return report_to_arena(0);
     }
     // replicated fronts of exchange step d held by this rank (their arena squares have been summed); afterwards the first rank of the range
     // reports what they contribute to the fronts of the wider ranges above
     bool enqueue_factor_step(int d) {
-        gs_cur = &gs_stage[d];
-        if (!launch_fronts(sch_stage[d], 1)) return false;
+        grp_step = d;
+        if (!launch_fronts(P.stage[d], 1)) return false;
         return d > 0 ? report_to_arena(1 + d) : true;
     }
     bool enqueue_stats() {
@@ -2249,7 +1517,7 @@ public:
     // (with zeros for the squares of ranges it is not in), in the same order: no sub-communicators, nothing to deadlock.
     bool factor_dist(const double* dvals, bool reuse, FactorStats& st) {
         if (!enqueue_factor_local(dvals, reuse)) return false;
-        for (int d = ndepth - 1; d >= 0; --d) {
+        for (int d = P.ndepth - 1; d >= 0; --d) {
             if (!exchange_step(d, 0)) return false;
             if (!enqueue_factor_step(d)) return false;
         }
@@ -2265,9 +1533,9 @@ public:
     }
     bool enqueue_fwd_local(const double* src) {
         hipLaunchKernelGGL(k_load_rhs, dim3(grid1d(S->n)), dim3(256), 0, stream, V, src);
-        if (!chain_segs.empty()) hipLaunchKernelGGL(k_bump_epoch, dim3(1), dim3(64), 0, stream, V.sepoch);
-        if (toprhs_doubles > 0) HIPCHK(hipMemsetAsync(V.top_rhs, 0, (size_t)toprhs_doubles * sizeof(double), stream));
-        if (!launch_solve_sweep(sch_local, true, 0)) return false;
+        if (!P.chain_segs.empty()) hipLaunchKernelGGL(k_bump_epoch, dim3(1), dim3(64), 0, stream, V.sepoch);
+        if (P.ex.toprhs_doubles > 0) HIPCHK(hipMemsetAsync(V.top_rhs, 0, (size_t)P.ex.toprhs_doubles * sizeof(double), stream));
+        if (!launch_solve_sweep(P.local, true, 0)) return false;
         return report_to_top_rhs(0);
     }
     // distributed solve of one right-hand side (identical on every rank), solution on every rank:
@@ -2279,22 +1547,22 @@ public:
         for (int r = 0; r < nrhs; ++r) {
             const double* src = dsrc + (size_t)r * lds_; double* col = drhs + (size_t)r * ld;
             if (!enqueue_fwd_local(src)) return false;
-            for (int d = ndepth - 1; d >= 0; --d) {
+            for (int d = P.ndepth - 1; d >= 0; --d) {
                 if (!exchange_step(d, 1)) return false;
-                if (!launch_solve_sweep(sch_stage[d], true, 1, d == 0)) return false;
+                if (!launch_solve_sweep(P.stage[d], true, 1, d == 0)) return false;
                 if (d > 0 && !report_to_top_rhs(1 + d)) return false;
             }
-            for (int d = 0; d < ndepth; ++d) if (!launch_solve_sweep(sch_stage[d], false, 1, d == 0)) return false;
-            if (!launch_solve_sweep(sch_local, false, 0)) return false;
+            for (int d = 0; d < P.ndepth; ++d) if (!launch_solve_sweep(P.stage[d], false, 1, d == 0)) return false;
+            if (!launch_solve_sweep(P.local, false, 0)) return false;
             hipLaunchKernelGGL(k_store_sol_mg, dim3(grid1d(S->n)), dim3(256), 0, stream, V, col);
             HIPCHK(hipGetLastError());
             if (!allreduce(col, S->n, 0)) return false;
         }
         HIPCHK(hipEventRecord(ev1, stream));
-        if (!chain_segs.empty()) HIPCHK(hipMemcpyAsync(h_stats + 6, V.sepoch + 1, sizeof(int), hipMemcpyDeviceToHost, stream));
+        if (!P.chain_segs.empty()) HIPCHK(hipMemcpyAsync(h_stats + 6, V.sepoch + 1, sizeof(int), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
         float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev0, ev1)); solve_ms = ms;
-        if (!chain_segs.empty() && h_stats[6] != 0) { err_ = "solve: a chain sweep timed out waiting for its predecessor on this rank (workgroups not co-resident: several ranks on one GPU?)"; return false; }
+        if (!P.chain_segs.empty() && h_stats[6] != 0) { err_ = "solve: a chain sweep timed out waiting for its predecessor on this rank (workgroups not co-resident: several ranks on one GPU?)"; return false; }
         return true;
     }
     bool factor_top(FactorStats& st) {
@@ -2324,9 +1592,9 @@ public:
         if (!ready || !multi) { err_ = "solve_top_and_bwd: not a multi-GPU handle"; return false; }
         if (!one_step("solve_top_and_bwd")) return false;
         HIPCHK(hipEventRecord(ev0, stream));
-        if (!launch_solve_sweep(sch_stage[0], true, 1)) return false;
-        if (!launch_solve_sweep(sch_stage[0], false, 1)) return false;
-        if (!launch_solve_sweep(sch_local, false, 0)) return false;
+        if (!launch_solve_sweep(P.stage[0], true, 1)) return false;
+        if (!launch_solve_sweep(P.stage[0], false, 1)) return false;
+        if (!launch_solve_sweep(P.local, false, 0)) return false;
         hipLaunchKernelGGL(k_store_sol_mg, dim3(grid1d(S->n)), dim3(256), 0, stream, V, drhs);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ev1, stream)); HIPCHK(hipStreamSynchronize(stream));
@@ -2474,10 +1742,10 @@ bool Numeric::profile(int reps, double* ms, int* launches) { return p_->profile(
 bool Numeric::debug_clocks(unsigned long long* out) { return p_->debug_clocks(out); }
 bool Numeric::debug_pivots(double* a, double* b, int* c, int* d) { return p_->debug_pivots(a, b, c, d); }
 bool Numeric::factor_local(const double* dvals) { return p_->factor_local(dvals); }
-bool Numeric::top_arena(double** d, int64_t* nd) { if (!p_->multi) { p_->err_ = "top_arena: not a multi-GPU handle"; return false; } *d = p_->V.arena; *nd = p_->arena_doubles; return true; }
+bool Numeric::top_arena(double** d, int64_t* nd) { if (!p_->multi) { p_->err_ = "top_arena: not a multi-GPU handle"; return false; } *d = p_->V.arena; *nd = p_->P.ex.arena_doubles; return true; }
 bool Numeric::factor_top(FactorStats& st) { return p_->factor_top(st); }
 bool Numeric::solve_fwd_local(double* drhs) { return p_->solve_fwd_local(drhs); }
-bool Numeric::top_rhs(double** d, int64_t* nd) { if (!p_->multi) { p_->err_ = "top_rhs: not a multi-GPU handle"; return false; } *d = p_->V.top_rhs; *nd = p_->toprhs_doubles; return true; }
+bool Numeric::top_rhs(double** d, int64_t* nd) { if (!p_->multi) { p_->err_ = "top_rhs: not a multi-GPU handle"; return false; } *d = p_->V.top_rhs; *nd = p_->P.ex.toprhs_doubles; return true; }
 bool Numeric::solve_top_and_bwd(double* drhs) { return p_->solve_top_and_bwd(drhs); }
 bool Numeric::set_scaling(int mode, const double* user) { return p_->set_scaling(mode, user); }
 bool Numeric::get_scaling(double* out) { return p_->get_scaling(out); }
@@ -2527,7 +1795,7 @@ bool Numeric::ruiz_triplet(int device, int n, int nnz, const int* irn, const int
 bool Numeric::set_comm_rccl(const void* unique_id128) { return p_->set_comm_rccl(unique_id128); }
 bool Numeric::set_comm_callback(int (*fn)(void*, void*, int64_t, int, void*), void* ctx) { return p_->set_comm_callback(fn, ctx); }
 bool Numeric::set_comm_range_callback(int (*fn)(void*, void*, int64_t, int, void*, int, int)) { return p_->set_comm_range_callback(fn); }
-void Numeric::comm_plan(const Symbolic& S, int nranks, int rank, bool range_local, std::vector<int>& out6) { NumericImpl::comm_plan(S, nranks, rank, range_local, S.n, out6); }
+void Numeric::comm_plan(const Symbolic& S, int nranks, int rank, bool range_local, std::vector<int>& out6) { mi355x::comm_plan(S, nranks, rank, range_local, out6); }
 void Numeric::comm_info(int* kind, int* ranks_seen, int* range_local, int* exchange_steps) const
 {
     int seen = p_->comm_kind == 0 ? 0 : p_->opt.nranks;
@@ -2535,9 +1803,9 @@ void Numeric::comm_info(int* kind, int* ranks_seen, int* range_local, int* excha
     if (kind) *kind = p_->comm_kind;
     if (ranks_seen) *ranks_seen = seen;
     if (range_local) *range_local = p_->range_local() ? 1 : 0;
-    if (exchange_steps) *exchange_steps = p_->ndepth;
+    if (exchange_steps) *exchange_steps = p_->P.ndepth;
 }
-long long Numeric::exchange_bytes(int what) const { long long b = 0; for (const auto& sg : p_->rsegs) b += 8 * (what == 0 ? sg.aend - sg.abeg : sg.tend - sg.tbeg); return b; }
+long long Numeric::exchange_bytes(int what) const { long long b = 0; for (const auto& sg : p_->P.ex.rsegs) b += 8 * (what == 0 ? sg.aend - sg.abeg : sg.tend - sg.tbeg); return b; }
 bool Numeric::rccl_unique_id(void* out128, std::string& err)
 {
     NumericImpl::Rccl R;

@@ -68,7 +68,7 @@ ABI_SYMBOLS = [
     "mi355x_kkt_values_buffer", "mi355x_kkt_factor", "mi355x_kkt_refactor", "mi355x_kkt_solve",
     "mi355x_kkt_solve_device", "mi355x_kkt_solve_device2", "mi355x_kkt_set_pivtol", "mi355x_kkt_set_pivtolmax", "mi355x_kkt_increase_quality",
     "mi355x_kkt_get_info", "mi355x_kkt_last_error",
-    "mi355x_kkt_get_symbolic", "mi355x_kkt_factor_local", "mi355x_kkt_top_arena", "mi355x_kkt_factor_top",
+    "mi355x_kkt_get_symbolic", "mi355x_kkt_get_launch_plan", "mi355x_kkt_factor_local", "mi355x_kkt_top_arena", "mi355x_kkt_factor_top",
     "mi355x_kkt_solve_fwd_local", "mi355x_kkt_top_rhs", "mi355x_kkt_solve_top_and_bwd", "mi355x_kkt_profile",
     "mi355x_kkt_comm_unique_id", "mi355x_kkt_set_comm_rccl", "mi355x_kkt_comm_shm_id", "mi355x_kkt_comm_shm_discard", "mi355x_kkt_set_comm_shm", "mi355x_kkt_set_comm_callbacks", "mi355x_kkt_set_comm_range_callback", "mi355x_kkt_exchange_bytes", "mi355x_kkt_comm_plan", "mi355x_kkt_comm_info",
     "mi355x_kkt_set_scaling", "mi355x_kkt_get_scaling", "mi355x_kkt_ruiz_scaling", "mi355x_kkt_matching_scaling", "mi355x_kkt_zero_pivots", "mi355x_kkt_failed_pivots", "mi355x_kkt_delay_columns", "mi355x_kkt_set_delay_rounds", "mi355x_kkt_assembly_define", "mi355x_kkt_assembly_buffer", "mi355x_kkt_assembly_upload", "mi355x_kkt_factor_assembled",
@@ -110,6 +110,7 @@ def load_library():
     lib.mi355x_kkt_last_error.argtypes = [vp]
     lib.mi355x_kkt_last_error.restype = C.c_char_p
     lib.mi355x_kkt_get_symbolic.argtypes = [vp, C.c_int, vp, C.c_int64]
+    lib.mi355x_kkt_get_launch_plan.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, vp, C.c_int64, C.POINTER(C.c_int64)]
     lib.mi355x_kkt_profile.argtypes = [vp, C.c_int, vp, vp, C.c_int]
     lib.mi355x_kkt_factor_local.argtypes = [vp, vp]
     lib.mi355x_kkt_top_arena.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
@@ -467,6 +468,16 @@ class KKTSolver:
         if self.lib.mi355x_kkt_profile(self._h, int(reps), ms.ctypes.data, ln.ctypes.data, len(KERNEL_KINDS)) != 0:
             raise KKTError("profile: " + self.last_error())
         return {k: (float(ms[i]), int(ln[i])) for i, k in enumerate(KERNEL_KINDS)}
+
+    def launch_plan(self, what: str, nranks: int = 1, rank: int = 0) -> np.ndarray:
+        """host only: array `what` of the launch plan rank `rank` of `nranks` would run (include/mi355x_kkt.h mi355x_kkt_get_launch_plan)."""
+        cnt = C.c_int64(0)
+        if self.lib.mi355x_kkt_get_launch_plan(self._h, int(nranks), int(rank), what.encode(), None, 0, C.byref(cnt)) != 0:
+            raise KKTError("get_launch_plan: " + self.last_error())
+        out = np.zeros(max(cnt.value, 1), dtype=np.int32)
+        if self.lib.mi355x_kkt_get_launch_plan(self._h, int(nranks), int(rank), what.encode(), out.ctypes.data, out.shape[0], C.byref(cnt)) != 0:
+            raise KKTError("get_launch_plan: " + self.last_error())
+        return out[:cnt.value]
 
     def symbolic(self, what: int, size: int) -> np.ndarray:
         out = np.empty(max(size, 1), dtype=np.int32)
