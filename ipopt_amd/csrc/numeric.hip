@@ -38,11 +38,9 @@
 #include "launch_plan.h"
 #include "env_knobs.h"
 #include "matching_scaling.h"
+#include "device_owner.h"      // DeviceOwner, HIPCHK
 
 namespace mi355x {
-
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
-    err_ = std::string(#call) + ": " + hipGetErrorString(e_); return false; } } while (0)
 
 // kernel kinds for the profiling entry point (order = include/mi355x_kkt.h MI355X_KKT_KERNEL_*)
 enum KernelKind { KK_GATHER_SCALE = 0, KK_FRONT_WAVE, KK_FRONT_LDS64, KK_FRONT_LDS128, KK_BIG_ASSEMBLE, KK_BIG_DIAG, KK_BIG_TRSM,
@@ -92,7 +90,13 @@ public:
     double factor_ms = 0, solve_ms = 0;
     double* h_vals = nullptr;     // pinned
     int* h_stats = nullptr;       // pinned, 4 ints
-    std::vector<void*> allocs;
+    // who owns what was taken from the HIP runtime (device_owner.h): the arena a buffer or an event comes from decides when it dies
+    DeviceOwner own_handle{err_};      // until release(false): h_vals, h_stats, ev0 / ev1, the profiling events, V.tvals, d_user_scale
+    DeviceOwner own_pool{err_};        // the one-piece L | cb pool, alone: a restructure keeps it unless the new layout does not fit (setup step 2)
+    DeviceOwner own_struct{err_};      // until any release(): what follows the elimination structure -- tables, work arrays, pool pieces, solve contexts, stream events, d_rhs
+    DeviceOwner own_match{err_};       // until any release() or a change of size: the buffers and events of the matching on the device
+    DeviceOwner own_asm{err_};         // until assembly_define or release(false): the assembly sources and their staging
+    DeviceOwner own_pd{err_};          // until pd_define or release(false): the primal-dual workspace
     DevView V{};
     int* d_stats = nullptr;
     double* d_rhs = nullptr; size_t d_rhs_cap = 0;
@@ -116,12 +120,11 @@ public:
         if (!ready) { err_ = "set_scaling: solver not set up"; return false; }
         if (mode < 0 || mode > 6 || (mode == 2 && !user)) { err_ = "set_scaling: mode 0 (none), 1 (ruiz), 2 (user factors, non-null), 3 (matching, host), 4 (matching, host, reused), 5 (matching, device) or 6 (matching, device, reused)"; return false; }
         match_valid = false;                                  // (mode 4: the factors of an earlier selection do not survive a new one)
+        if (mode >= 2 && !d_user_scale && !own_handle.raw(&d_user_scale, S->n)) return false;
         if (mode == 2) {
-            if (!d_user_scale) { HIPCHK(hipMalloc((void**)&d_user_scale, std::max<size_t>(S->n, 1) * sizeof(double))); allocs.push_back(d_user_scale); }
             HIPCHK(hipMemcpyAsync(d_user_scale, user, (size_t)S->n * sizeof(double), hipMemcpyHostToDevice, stream));
             HIPCHK(hipStreamSynchronize(stream));      // `user` is the caller's pageable memory
         }
-        if (mode >= 3 && !d_user_scale) { HIPCHK(hipMalloc((void**)&d_user_scale, std::max<size_t>(S->n, 1) * sizeof(double))); allocs.push_back(d_user_scale); }
         if (mode != opt.scaling) destroy_factor_graphs();      // the captured sequences differ
         scale_valid = false;
         opt.scaling = mode;
@@ -153,28 +156,23 @@ public:
     }
     // scaling modes 5 / 6: the same job on the DEVICE (kernels_match.hip.inc: Jacobi auction over the symmetric row view; specification
     // tests/support/auction_spec.py).  Nothing crosses PCIe but the free-column counts that steer the rounds.  Mode 6 = computed once and kept like mode 4.
-    std::vector<void*> match_allocs;
     MatchView MV{};
     int match_unmatched = 0, match_rounds = 0, match_launches = 0;
     float match_ms = 0.f;
     hipEvent_t match_e0 = nullptr, match_e1 = nullptr;
-    void match_free() { for (void* p : match_allocs) (void)hipFree(p); match_allocs.clear(); MV = MatchView{};
-                        if (match_e0) { (void)hipEventDestroy(match_e0); match_e0 = nullptr; } if (match_e1) { (void)hipEventDestroy(match_e1); match_e1 = nullptr; } }
-    template <class T> bool match_alloc(T** d, size_t count) { T* p = nullptr; HIPCHK(hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T))); match_allocs.push_back(p); *d = p; return true; }
     bool compute_matching_device() {
         const Symbolic& Sy = *S; const int n = Sy.n;
-        if (MV.n != n || MV.len != V.rslot_len || match_allocs.empty()) {
-            match_free();
+        if (MV.n != n || MV.len != V.rslot_len || own_match.empty()) {
+            DeviceOwner& M = own_match;
+            M.clear(); MV = MatchView{};
             const size_t len = (size_t)V.rslot_len;
-            if (!match_alloc(&MV.b, len) || !match_alloc(&MV.logcmax, n) || !match_alloc(&MV.price, n) || !match_alloc(&MV.bidval, n) || !match_alloc(&MV.owner, n) ||
-                !match_alloc(&MV.mrow, n) || !match_alloc(&MV.wcol, n) || !match_alloc(&MV.bidrow, n) || !match_alloc(&MV.bidkey, n) || !match_alloc(&MV.list0, n) ||
-                !match_alloc(&MV.list1, n) || !match_alloc(&MV.cnt, 8)) return false;
-            MV.n = n; MV.len = V.rslot_len;
+            if (!M.raw(&MV.b, len) || !M.raw(&MV.logcmax, n) || !M.raw(&MV.price, n) || !M.raw(&MV.bidval, n) || !M.raw(&MV.owner, n) ||
+                !M.raw(&MV.mrow, n) || !M.raw(&MV.wcol, n) || !M.raw(&MV.bidrow, n) || !M.raw(&MV.bidkey, n) || !M.raw(&MV.list0, n) ||
+                !M.raw(&MV.list1, n) || !M.raw(&MV.cnt, 8) || !M.event(&match_e0) || !M.event(&match_e1)) return false;
+            MV.n = n; MV.len = V.rslot_len;      // (set last: a set-up that failed half-way is taken again from the start)
         }
         MV.ptr = V.rslot_ptr; MV.col = V.rslot_col; MV.arv = V.arv; MV.perm = V.perm;       // (a structure edit for delayed pivots relabels the row view)
-        if (!match_e0) { HIPCHK(hipEventCreate(&match_e0)); HIPCHK(hipEventCreate(&match_e1)); }      // (members: an error return below must not leak them)
-        hipEvent_t e0 = match_e0, e1 = match_e1;
-        HIPCHK(hipEventRecord(e0, stream));
+        HIPCHK(hipEventRecord(match_e0, stream));
         hipLaunchKernelGGL(k_gather_values, dim3(grid1d(Sy.nnz_a)), dim3(256), 0, stream, V);
         hipLaunchKernelGGL(k_abs_rowview, dim3(grid1d(V.rslot_len)), dim3(256), 0, stream, V);
         hipLaunchKernelGGL(k_match_init, dim3(grid1d(8ll * n)), dim3(256), 0, stream, MV);
@@ -216,10 +214,10 @@ public:
         HIPCHK(hipMemsetAsync(MV.cnt, 0, 8 * sizeof(int), stream));
         hipLaunchKernelGGL(k_match_final, dim3(grid1d(8ll * n)), dim3(256), 0, stream, MV, d_user_scale);
         ++match_launches;
-        HIPCHK(hipEventRecord(e1, stream));
+        HIPCHK(hipEventRecord(match_e1, stream));
         if (!read_cnt()) return false;
         match_unmatched = hc[2];
-        (void)hipEventElapsedTime(&match_ms, e0, e1);
+        (void)hipEventElapsedTime(&match_ms, match_e0, match_e1);
         if (opt.verbose) fprintf(stderr, "[mi355x_kkt] matching scaling on the device: %d rounds, %d launches, %.3f ms, %d unmatched columns\n", match_rounds, match_launches, match_ms, match_unmatched);
         return true;
     }
@@ -248,7 +246,6 @@ public:
     // ---- device-side value assembly: per segment a device source buffer + a pinned staging buffer of the same length ----
     AsmSegs asm_{};
     std::vector<double*> asm_host;        // pinned staging per segment
-    double* asm_pool = nullptr; double* asm_hpool = nullptr;
     bool assembly_define(int nseg, const int64_t* off, const int64_t* len) {
         DeviceGuard guard(dev);
         if (!ready) { err_ = "assembly_define: analyse first (and a usable HIP device)"; return false; }
@@ -256,12 +253,11 @@ public:
         long long total = 0;
         for (int q = 0; q < nseg; ++q) { if (off[q] != total || len[q] < 0) { err_ = "assembly_define: segments must tile [0, nnz) in order"; return false; } total += len[q]; }
         if (total != S->nnz_in) { err_ = "assembly_define: segments do not cover the nnz triplet values"; return false; }
-        if (asm_pool) { (void)hipFree(asm_pool); asm_pool = nullptr; }
-        if (asm_hpool) { (void)hipHostFree(asm_hpool); asm_hpool = nullptr; }
-        HIPCHK(hipMalloc((void**)&asm_pool, std::max<long long>(total, 1) * sizeof(double)));
-        HIPCHK(hipMemset(asm_pool, 0, std::max<long long>(total, 1) * sizeof(double)));
+        own_asm.clear(); asm_.nseg = 0;
+        double *asm_pool = nullptr, *asm_hpool = nullptr;
+        if (!own_asm.zeroed(&asm_pool, (size_t)total)) return false;
         HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipHostMalloc((void**)&asm_hpool, std::max<long long>(total, 1) * sizeof(double), hipHostMallocDefault));
+        if (!own_asm.pinned(&asm_hpool, (size_t)total)) return false;
         asm_.nseg = nseg; asm_host.assign(nseg, nullptr);
         for (int q = 0; q < nseg; ++q) { asm_.off[q] = off[q]; asm_.len[q] = len[q]; asm_.src[q] = asm_pool + off[q]; asm_host[q] = asm_hpool + off[q]; asm_.scale[q] = 0.0; asm_.shift[q] = 0.0; }
         return true;
@@ -431,7 +427,7 @@ public:
     double prof_ms[KK_COUNT] = {0}; int prof_launches[KK_COUNT] = {0};
     void prof_begin(int kind, hipStream_t strm = nullptr) {
         if (!prof_on) return;
-        if (prof_used + 2 > prof_ev.size()) { size_t old = prof_ev.size(); prof_ev.resize(old + 64); for (size_t i = old; i < prof_ev.size(); ++i) (void)hipEventCreate(&prof_ev[i]); }
+        if (prof_used + 2 > prof_ev.size()) { size_t old = prof_ev.size(); prof_ev.resize(old + 64); for (size_t i = old; i < prof_ev.size(); ++i) (void)own_handle.event(&prof_ev[i]); }
         (void)hipEventRecord(prof_ev[prof_used], strm ? strm : stream); prof_kind.push_back(kind);
     }
     void prof_end(hipStream_t strm = nullptr) { if (!prof_on) return; (void)hipEventRecord(prof_ev[prof_used + 1], strm ? strm : stream); prof_used += 2; }
@@ -440,12 +436,10 @@ public:
         for (size_t i = 0; i < prof_used; i += 2) { float ms = 0; (void)hipEventElapsedTime(&ms, prof_ev[i], prof_ev[i + 1]); int kd = prof_kind[i / 2]; prof_ms[kd] += ms; prof_launches[kd]++; }
         prof_used = 0; prof_kind.clear();
     }
-    ~NumericImpl() { release(); for (auto e : prof_ev) (void)hipEventDestroy(e); }
-    // keep = true (restructure): what does not depend on the elimination structure survives -- the communicator, the streams, the pinned
-    // staging buffers handed out to the caller (values_buffer, assembly buffers), the device copy of the triplet values, the assembly
-    // sources, the primal-dual workspace (it reads the triplet values and calls solve), the caller's scaling factors (original numbering)
-    double* keep_tvals = nullptr;
-    double* kept_pool = nullptr; long long kept_pool_doubles = 0;      // the one-piece L | cb pool: survives a restructure (a delayed-pivot edit changes the layout by a fraction of a per cent: the 1 % of slack it is allocated with takes that), 40-80 ms of hipFree + hipMalloc at 9 GiB less per edit
+    ~NumericImpl() { release(); }
+    // keep = true (restructure): what does not depend on the elimination structure survives -- the communicator, the streams and the arenas
+    // own_handle, own_pool, own_asm, own_pd (see their declarations).  Order: graphs, then buffers and events, then streams.
+    double* kept_pool = nullptr; long long kept_pool_doubles = 0;      // the one-piece L | cb pool (own_pool): survives a restructure (a delayed-pivot edit changes the layout by a fraction of a per cent: the 1 % of slack it is allocated with takes that), 40-80 ms of hipFree + hipMalloc at 9 GiB less per edit
     void release(bool keep = false) {
         DeviceGuard guard(dev);
         destroy_subcomms();                      // (the ranges follow the structure: split again after a restructure)
@@ -454,34 +448,14 @@ public:
                      comm_kind = 0; comm_range_fn = nullptr; }
         destroy_factor_graphs(); scale_valid = false; asm_dirty = true;
         if (g_solve) { (void)hipGraphExecDestroy(g_solve); g_solve = nullptr; }
-        keep_tvals = nullptr;
-        for (void* p : allocs) {
-            if (keep && p == (void*)V.tvals) { keep_tvals = (double*)p; continue; }
-            if (keep && kept_pool && p == (void*)kept_pool) continue;      // (one-piece pool: handed to the next set-up, which reuses it if the new layout fits)
-            if (keep && p == (void*)d_user_scale) continue;
-            (void)hipFree(p);
-        }
-        allocs.clear();
-        if (!keep && kept_pool) { kept_pool = nullptr; kept_pool_doubles = 0; }      // (it was in allocs: freed above)
-        if (keep && keep_tvals) allocs.push_back(keep_tvals);
-        if (keep && d_user_scale) allocs.push_back(d_user_scale); else d_user_scale = nullptr;
-        if (d_rhs) { (void)hipFree(d_rhs); d_rhs = nullptr; d_rhs_cap = 0; }
-        match_free();
+        own_struct.clear(); d_rhs = nullptr; d_rhs_cap = 0;
+        la_ev.clear(); side_evF.clear(); side_evJ.clear(); la_last = nullptr; la_pending = false;
+        own_match.clear(); MV = MatchView{};
         if (!keep) {
-            if (asm_pool) { (void)hipFree(asm_pool); asm_pool = nullptr; }
-            if (asm_hpool) { (void)hipHostFree(asm_hpool); asm_hpool = nullptr; }
-            asm_.nseg = 0;
-            pd_free();
-            if (h_vals) { (void)hipHostFree(h_vals); h_vals = nullptr; }
-            if (h_stats) { (void)hipHostFree(h_stats); h_stats = nullptr; }
-            if (ev0) { (void)hipEventDestroy(ev0); ev0 = nullptr; }
-            if (ev1) { (void)hipEventDestroy(ev1); ev1 = nullptr; }
-        }
-        for (LaEvents& E : la_ev) for (auto* v : {&E.A, &E.B}) for (auto e : *v) if (e) (void)hipEventDestroy(e);
-        la_ev.clear();
-        for (auto* v : {&side_evF, &side_evJ}) { for (auto e : *v) if (e) (void)hipEventDestroy(e); v->clear(); }
-        la_last = nullptr; la_pending = false;
-        if (!keep) {
+            own_pool.clear(); kept_pool = nullptr; kept_pool_doubles = 0;
+            own_asm.clear(); asm_.nseg = 0;
+            own_pd.clear(); pd_ready = false;
+            own_handle.clear(); h_vals = nullptr; h_stats = nullptr; ev0 = ev1 = nullptr; V.tvals = nullptr; d_user_scale = nullptr; prof_ev.clear(); prof_used = 0; prof_kind.clear();
             if (stream3) { (void)hipStreamDestroy(stream3); stream3 = nullptr; }
             if (stream2) { (void)hipStreamDestroy(stream2); stream2 = nullptr; }
             if (stream) { (void)hipStreamDestroy(stream); stream = nullptr; }
@@ -489,17 +463,8 @@ public:
         P = LaunchPlan();
         ready = false;
     }
-    template <class T, class A> bool upload(const std::vector<T, A>& h, const T** d) {
-        T* p = nullptr; size_t bytes = std::max<size_t>(h.size(), 1) * sizeof(T);
-        HIPCHK(hipMalloc((void**)&p, bytes)); allocs.push_back(p);
-        if (!h.empty()) HIPCHK(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-        *d = p; return true;
-    }
-    template <class T> bool dalloc(T** d, size_t count) {
-        T* p = nullptr; HIPCHK(hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T))); allocs.push_back(p);
-        HIPCHK(hipMemset(p, 0, std::max<size_t>(count, 1) * sizeof(T)));
-        *d = p; return true;
-    }
+    template <class T, class A> bool upload(const std::vector<T, A>& h, const T** d) { return own_struct.upload(h, d); }
+    template <class T> bool dalloc(T** d, size_t count) { return own_struct.zeroed(d, count); }      // (zero fill on the default stream: setup step 7 / sctx_ensure synchronise)
 
     // Delayed pivots changed the structure (symbolic.cpp restructure_delays): everything derived from it is rebuilt, the rest (see release) stays
     bool restructure(const Symbolic& Sy) {
@@ -530,15 +495,13 @@ public:
             HIPCHK(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, phi));
             HIPCHK(hipStreamCreateWithPriority(&stream2, hipStreamNonBlocking, plo));
             HIPCHK(hipStreamCreateWithPriority(&stream3, hipStreamNonBlocking, (plo + phi) / 2));
-        }
-        if (!keep) {
-            HIPCHK(hipEventCreate(&ev0)); HIPCHK(hipEventCreate(&ev1));
-            if (opt.prewarmed_vals && opt.prewarmed_count >= std::max<size_t>(Sy.nnz_in, 1)) h_vals = (double*)opt.prewarmed_vals;       // (made while the analysis ran)
+            if (!own_handle.event(&ev0) || !own_handle.event(&ev1)) return false;
+            if (opt.prewarmed_vals && opt.prewarmed_count >= std::max<size_t>(Sy.nnz_in, 1)) { h_vals = (double*)opt.prewarmed_vals; own_handle.adopt_pinned(h_vals); }       // (made while the analysis ran)
             else {
-                if (opt.prewarmed_vals) (void)hipHostFree(opt.prewarmed_vals);
-                HIPCHK(hipHostMalloc((void**)&h_vals, std::max<size_t>(Sy.nnz_in, 1) * sizeof(double), hipHostMallocDefault));
+                if (opt.prewarmed_vals) Numeric::prewarm_discard(opt.prewarmed_vals);
+                if (!own_handle.pinned(&h_vals, Sy.nnz_in)) return false;
             }
-            HIPCHK(hipHostMalloc((void**)&h_stats, 12 * sizeof(int), hipHostMallocDefault));
+            if (!own_handle.pinned(&h_stats, 12)) return false;
         }
         opt.prewarmed_vals = nullptr;
         lap("device, streams, pinned buffer");
@@ -592,16 +555,16 @@ public:
                 last_ok = b;
             }
             std::vector<char*> base(pool_cut.size(), nullptr);
-            if (kept_pool && (pool_cut.size() != 1 || total > kept_pool_doubles)) { (void)hipFree(kept_pool); kept_pool = nullptr; kept_pool_doubles = 0; }
+            if (kept_pool && (pool_cut.size() != 1 || total > kept_pool_doubles)) { own_pool.clear(); kept_pool = nullptr; kept_pool_doubles = 0; }
             for (size_t i = 0; i < pool_cut.size(); ++i) {
                 const long long end = i + 1 < pool_cut.size() ? pool_cut[i + 1] : total;
                 double* pp = nullptr;
                 if (pool_cut.size() == 1 && kept_pool) {      // the pool of the structure before the edit: reused, zeroed like a fresh one
-                    pp = kept_pool; allocs.push_back(pp);
+                    pp = kept_pool;
                     HIPCHK(hipMemsetAsync(pp, 0, (size_t)std::max<long long>(total, 1) * sizeof(double), stream));
                 } else if (pool_cut.size() == 1) {
                     const long long cap = total + total / 100 + 1024;
-                    if (!dalloc(&pp, (size_t)cap)) return false;
+                    if (!own_pool.zeroed(&pp, (size_t)cap)) { own_pool.clear(); return false; }      // (the arena holds the pool kept_pool names, or nothing)
                     kept_pool = pp; kept_pool_doubles = cap;
                 } else if (!dalloc(&pp, (size_t)std::max<long long>(end - pool_cut[i], 1))) return false;
                 base[i] = (char*)pp;
@@ -654,9 +617,7 @@ public:
             !upload(Sy.perm, &V.perm)) return false;
         lap("uploads");
         // 5. work arrays
-        double* tv = keep ? keep_tvals : nullptr;
-        if (!tv && !dalloc(&tv, Sy.nnz_in)) return false;
-        V.tvals = tv;
+        if (!V.tvals) { double* tv = nullptr; if (!own_handle.zeroed(&tv, Sy.nnz_in)) return false; V.tvals = tv; }      // (nnz_in does not change across a restructure)
         V.rslot_len = (int)Sy.rslot_idx.size();
         if (!dalloc(&V.arv, Sy.rslot_idx.size()) || !dalloc(&V.aval, Sy.nnz_a) || !dalloc(&V.scale, Sy.n) || !dalloc(&V.scale2, Sy.n) || !dalloc(&V.rowmax, Sy.n) ||
             !dalloc(&V.wbuf, (size_t)Sy.wbuf_doubles) || !dalloc(&V.minv, (size_t)Sy.minv_doubles) ||
@@ -666,7 +627,7 @@ public:
             !dalloc(&V.sflag_d, Sy.num_sn) || !dalloc(&V.sflag_p, Sy.num_sn) || !dalloc(&V.sflag_s, 4 * (size_t)Sy.num_sn) || !dalloc(&V.tcnt, Sy.num_sn) || !dalloc(&V.apfail, Sy.num_sn) || !dalloc(&V.sepoch, 4)) return false;
         V.qstat = d_stats + 4;
         lap("device allocations");
-        if (opt.scaling >= 3 && !d_user_scale) { HIPCHK(hipMalloc((void**)&d_user_scale, std::max<size_t>(Sy.n, 1) * sizeof(double))); allocs.push_back(d_user_scale); }
+        if (opt.scaling >= 3 && !d_user_scale) { if (!own_handle.raw(&d_user_scale, Sy.n)) return false; }
         else if (opt.scaling == 2 && !d_user_scale) opt.scaling = 1;       // (user factors can only come through set_scaling)
         V.cb = V.L + Sy.l_doubles;          // one pool: panels of in-place chain fronts live inside the cb part
         V.arena = nullptr; V.top_rhs = nullptr; V.rank = opt.rank; V.dbg = nullptr;
@@ -678,8 +639,8 @@ public:
         for (size_t i = 0; i < la_ev.size(); ++i) {
             const std::vector<int>& la2 = i == 0 ? P.la_tiles2 : P.grp[i - 1].la2;
             la_ev[i].A.assign(la2.size(), nullptr); la_ev[i].B.assign(la2.size(), nullptr);
-            for (size_t lv = 0; lv < la2.size(); ++lv) if (la2[lv] > 0) {
-                HIPCHK(hipEventCreateWithFlags(&la_ev[i].A[lv], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&la_ev[i].B[lv], hipEventDisableTiming)); }
+            for (size_t lv = 0; lv < la2.size(); ++lv)
+                if (la2[lv] > 0 && (!own_struct.event(&la_ev[i].A[lv], hipEventDisableTiming) || !own_struct.event(&la_ev[i].B[lv], hipEventDisableTiming))) return false;
         }
         // 7. kernel attributes: allow the large dynamic LDS sizes
         HIPCHK(hipFuncSetAttribute((const void*)k_big_diag_reg<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -918,7 +879,7 @@ public:
                 const bool side = side_on && P.la_any && !multi && fc != FC_BIG && b1 - b0 <= SIDE_MAX_FRONTS && lvl_max >= 8 * (b1 - b0) && lvl_fronts > b1 - b0;
                 if (!side) { launch_bucket(lv, fc, b0, b1, 0, P.single.maxm[lv], P.single.maxk[lv], P.single.tiles[lv], P.single.tiles64[lv]); continue; }
                 if ((int)side_evF.size() < Sy.num_levels) { side_evF.resize(Sy.num_levels, nullptr); side_evJ.resize(Sy.num_levels, nullptr); }
-                if (!side_evF[lv]) { HIPCHK(hipEventCreateWithFlags(&side_evF[lv], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&side_evJ[lv], hipEventDisableTiming)); }
+                if (!side_evF[lv] && (!own_struct.event(&side_evF[lv], hipEventDisableTiming) || !own_struct.event(&side_evJ[lv], hipEventDisableTiming))) return false;
                 if (!side_open) { HIPCHK(hipEventRecord(side_evF[lv], stream)); HIPCHK(hipStreamWaitEvent(stream3, side_evF[lv], 0)); side_open = true; }      // behind the level below
                 std::swap(stream, stream3);
                 const bool ok = launch_bucket(lv, fc, b0, b1, 0, P.single.maxm[lv], P.single.maxk[lv], P.single.tiles[lv], P.single.tiles64[lv]);
@@ -1103,24 +1064,22 @@ public:
     // level launches of the bulk of the tree, which hold 2/3 of L) overlaps freely.  Needs eager launches: the gate is an event between streams.
     bool gate_on = false, gate_valid = false, gate_entered = false; hipEvent_t gate_last = nullptr, gate_mine = nullptr; hipEvent_t gate_ev[SOLVE_CTX] = {nullptr, nullptr, nullptr};
     size_t n_sflag_dot = 1, n_dpart = 1, n_sflag_t = 1, n_sflag_b = 1, n_tag = 1;      // element counts of the flag / tag arrays (set where they are allocated)
-    void sctx_release() {      // (the buffers are in `allocs`: release() frees them)
-        for (int c = 0; c < SOLVE_CTX; ++c) if (gate_ev[c]) { (void)hipEventDestroy(gate_ev[c]); gate_ev[c] = nullptr; }
+    void sctx_release() {      // (the contexts' buffers and every event here are own_struct's: release() clears it)
+        for (hipEvent_t& e : gate_ev) e = nullptr;
         gate_on = gate_valid = gate_entered = false; gate_last = gate_mine = nullptr; sctx_verdict = 0;
-        for (int c = 1; c < SOLVE_CTX; ++c) { if (sctx[c].graph) (void)hipGraphExecDestroy(sctx[c].graph); if (sctx[c].done) (void)hipEventDestroy(sctx[c].done);
-                                               if (sctx[c].strm) (void)hipStreamDestroy(sctx[c].strm); sctx[c] = SolveCtx(); }
-        if (sctx_fork) { (void)hipEventDestroy(sctx_fork); sctx_fork = nullptr; }
-        nsctx = 1;
+        for (int c = 1; c < SOLVE_CTX; ++c) { if (sctx[c].graph) (void)hipGraphExecDestroy(sctx[c].graph); if (sctx[c].strm) (void)hipStreamDestroy(sctx[c].strm); sctx[c] = SolveCtx(); }
+        sctx_fork = nullptr; nsctx = 1;
     }
     bool sctx_ensure(int want) {
         want = std::min(want, SOLVE_CTX);
         const Symbolic& Sy = *S;
-        if (!sctx_fork) HIPCHK(hipEventCreateWithFlags(&sctx_fork, hipEventDisableTiming));
-        for (int c = 0; c < want; ++c) if (!gate_ev[c]) HIPCHK(hipEventCreateWithFlags(&gate_ev[c], hipEventDisableTiming));
+        if (!sctx_fork && !own_struct.event(&sctx_fork, hipEventDisableTiming)) return false;
+        for (int c = 0; c < want; ++c) if (!gate_ev[c] && !own_struct.event(&gate_ev[c], hipEventDisableTiming)) return false;
         for (int c = nsctx; c < want; ++c) {
             SolveCtx& X = sctx[c];
             { int plo = 0, phi = 0; (void)hipDeviceGetStreamPriorityRange(&plo, &phi);      // (numerically lower = higher priority; the solver's own stream has phi)
               HIPCHK(hipStreamCreateWithPriority(&X.strm, hipStreamNonBlocking, c == 1 ? (plo + phi) / 2 : plo)); }
-            HIPCHK(hipEventCreateWithFlags(&X.done, hipEventDisableTiming));
+            if (!own_struct.event(&X.done, hipEventDisableTiming)) return false;
             if (!dalloc(&X.xw, Sy.n) || !dalloc(&X.ybuf, Sy.n) || !dalloc(&X.zb, Sy.n) || !dalloc(&X.bw, Sy.n) || !dalloc(&X.xacc, Sy.n) || !dalloc(&X.cvec, (size_t)Sy.cvec_doubles) ||
                 !dalloc(&X.gpart, (size_t)Sy.gpart_doubles) || !dalloc(&X.sflag_dot, n_sflag_dot) || !dalloc(&X.dpart, n_dpart) || !dalloc(&X.sflag_t, n_sflag_t) || !dalloc(&X.sflag_b, n_sflag_b) ||
                 !dalloc(&X.ytag, n_tag) || !dalloc(&X.xtag, n_tag) || !dalloc(&X.sepoch, 4)) return false;
@@ -1175,12 +1134,13 @@ public:
             // measured ONCE per structure, on scratch vectors: three right-hand sides one after the other against the same three through the contexts.  On a
             // tree whose chain sweeps fill the device (synth_1e6: 5 290 spinning workgroups) the level launches of a second context starve next to them and the
             // contexts LOSE (18.6 against 16.6 ms for eight right-hand sides); on a mid-size tree they win (grid_1e5: 2.2 against 3.5 ms).
+            DeviceOwner tune(err_);      // (an error return below frees what was taken)
             double* scratch = nullptr;
-            HIPCHK(hipMalloc((void**)&scratch, 6 * (size_t)std::max(S->n, 1) * sizeof(double)));
+            if (!tune.raw(&scratch, 6 * (size_t)std::max(S->n, 1))) return false;
             HIPCHK(hipMemsetAsync(scratch, 0, 6 * (size_t)std::max(S->n, 1) * sizeof(double), stream));
             sctx_tuning = true;
             float t_seq = 0, t_ctx = 0; bool ok = true;
-            hipEvent_t e0 = nullptr, e1 = nullptr; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+            hipEvent_t e0 = nullptr, e1 = nullptr; if (!tune.event(&e0) || !tune.event(&e1)) return false;
             for (int mode = 0; mode < 2 && ok; ++mode) {
                 sctx_verdict = mode == 0 ? 2 : 1;
                 float best = 1e30f;
@@ -1193,7 +1153,7 @@ public:
                 }
                 (mode == 0 ? t_seq : t_ctx) = best;
             }
-            (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(scratch);
+            tune.clear();
             sctx_tuning = false;
             if (!ok) { sctx_verdict = 0; return false; }
             sctx_verdict = t_ctx < 0.95f * t_seq ? 1 : 2;
@@ -1266,25 +1226,14 @@ public:
     PdView pd_{}; bool pd_ready = false; long long pd_len8 = 0; int pd_dim4 = 0;
     static constexpr int PD_NVEC = 4;                      // RHS, RES, RESID, and one spare (the caller's copy)
     double* pd_vec[PD_NVEC] = {nullptr, nullptr, nullptr, nullptr};
-    double* pd_aug = nullptr; double* pd_data = nullptr; int* pd_idx = nullptr; int* pd_rv = nullptr; double* pd_stage = nullptr;
+    double* pd_aug = nullptr; double* pd_data = nullptr; int* pd_idx = nullptr; const int* pd_rv = nullptr; double* pd_stage = nullptr;
     unsigned long long* pd_norms_d = nullptr; unsigned long long* pd_norms_h = nullptr;
-    void pd_free() {
-        for (int q = 0; q < PD_NVEC; ++q) if (pd_vec[q]) { (void)hipFree(pd_vec[q]); pd_vec[q] = nullptr; }
-        if (pd_aug) { (void)hipFree(pd_aug); pd_aug = nullptr; }
-        if (pd_data) { (void)hipFree(pd_data); pd_data = nullptr; }
-        if (pd_idx) { (void)hipFree(pd_idx); pd_idx = nullptr; }
-        if (pd_rv) { (void)hipFree(pd_rv); pd_rv = nullptr; }
-        if (pd_stage) { (void)hipHostFree(pd_stage); pd_stage = nullptr; }
-        if (pd_norms_d) { (void)hipFree(pd_norms_d); pd_norms_d = nullptr; }
-        if (pd_norms_h) { (void)hipHostFree(pd_norms_h); pd_norms_h = nullptr; }
-        pd_ready = false;
-    }
     // dims = {nx, ns, nc, nd, nxl, nxu, nsl, nsu}; idx*: 0-based positions of the bounded entries; (irn, jcn): the 1-based triplets of
     // analyse(); segs: the assembly segments that hold W, J_c, J_d (everything else -- diagonals, -I -- is explicit in the kernels)
     bool pd_define(const int* dims, const int* ixl, const int* ixu, const int* isl, const int* isu, const int* irn, const int* jcn, const int* segs, int nsegs) {
         DeviceGuard guard(dev);
         if (!ready || asm_.nseg == 0) { err_ = "pd_define: analyse() and assembly_define() first"; return false; }
-        pd_free();
+        own_pd.clear(); pd_ready = false;      // (every pd_* pointer below is own_pd's, and is read only while pd_ready)
         PdView& P = pd_;
         P.nx = dims[0]; P.ns = dims[1]; P.nc = dims[2]; P.nd = dims[3]; P.nxl = dims[4]; P.nxu = dims[5]; P.nsl = dims[6]; P.nsu = dims[7];
         pd_dim4 = P.nx + P.ns + P.nc + P.nd;
@@ -1314,12 +1263,10 @@ public:
                 rcol[fill[r]] = c; rslot[fill[r]++] = (int)t;
                 if (r != c) { rcol[fill[c]] = r; rslot[fill[c]++] = (int)t; }
             }
-        HIPCHK(hipMalloc((void**)&pd_rv, rv.size() * sizeof(int)));
-        HIPCHK(hipMemcpy(pd_rv, rv.data(), rv.size() * sizeof(int), hipMemcpyHostToDevice));
+        if (!own_pd.upload(rv, &pd_rv)) return false;
         P.rptr = pd_rv; P.rcol = pd_rv + pd_dim4 + 1; P.rslot = P.rcol + nent;
         const long long nb = (long long)P.nxl + P.nxu + P.nsl + P.nsu;
-        HIPCHK(hipMalloc((void**)&pd_idx, std::max<long long>(nb, 1) * sizeof(int)));
-        HIPCHK(hipMalloc((void**)&pd_data, std::max<long long>(2 * nb, 1) * sizeof(double)));
+        if (!own_pd.raw(&pd_idx, (size_t)nb) || !own_pd.raw(&pd_data, 2 * (size_t)nb)) return false;
         {
             int* d = pd_idx;
             P.ixl = d; if (P.nxl) HIPCHK(hipMemcpy(d, ixl, P.nxl * sizeof(int), hipMemcpyHostToDevice)); d += P.nxl;
@@ -1330,11 +1277,8 @@ public:
             P.zl = f; f += P.nxl; P.zu = f; f += P.nxu; P.vl = f; f += P.nsl; P.vu = f; f += P.nsu;
             P.sxl = f; f += P.nxl; P.sxu = f; f += P.nxu; P.ssl = f; f += P.nsl; P.ssu = f;
         }
-        for (int q = 0; q < PD_NVEC; ++q) { HIPCHK(hipMalloc((void**)&pd_vec[q], std::max<long long>(pd_len8, 1) * sizeof(double))); HIPCHK(hipMemset(pd_vec[q], 0, std::max<long long>(pd_len8, 1) * sizeof(double))); }
-        HIPCHK(hipMalloc((void**)&pd_aug, std::max(pd_dim4, 1) * sizeof(double)));
-        HIPCHK(hipHostMalloc((void**)&pd_stage, std::max<long long>(std::max<long long>(pd_len8, 2 * nb), 1) * sizeof(double), hipHostMallocDefault));
-        HIPCHK(hipMalloc((void**)&pd_norms_d, 4 * sizeof(unsigned long long)));
-        HIPCHK(hipHostMalloc((void**)&pd_norms_h, 4 * sizeof(unsigned long long), hipHostMallocDefault));
+        for (int q = 0; q < PD_NVEC; ++q) if (!own_pd.zeroed(&pd_vec[q], (size_t)pd_len8)) return false;
+        if (!own_pd.raw(&pd_aug, pd_dim4) || !own_pd.pinned(&pd_stage, (size_t)std::max<long long>(pd_len8, 2 * nb)) || !own_pd.raw(&pd_norms_d, 4) || !own_pd.pinned(&pd_norms_h, 4)) return false;
         P.norms = pd_norms_d; P.tvals = V.tvals;
         HIPCHK(hipDeviceSynchronize());          // (the zero fills above ran on the default stream)
         pd_ready = true;
@@ -1661,13 +1605,19 @@ public:
 #endif
         return true;
     }
+    bool ensure_rhs(size_t count) {      // room for `count` doubles in d_rhs: it only grows, and the solve graph does not outlive the buffer it was captured next to
+        if (d_rhs_cap >= count) return true;
+        own_struct.free_device(d_rhs); d_rhs = nullptr; d_rhs_cap = 0;
+        if (g_solve) { (void)hipGraphExecDestroy(g_solve); g_solve = nullptr; }
+        if (!own_struct.raw(&d_rhs, count)) return false;
+        d_rhs_cap = count; return true;
+    }
     // eager (graph-less) factor + one solve with hip events around every launch; accumulates over `reps`
     bool profile(int reps, double* ms, int* launches) {
         DeviceGuard guard(dev);
         if (!ready || !have_values) { err_ = "profile: factor() must have been called once"; return false; }
         for (int q = 0; q < KK_COUNT; ++q) { prof_ms[q] = 0; prof_launches[q] = 0; }
-        if (d_rhs_cap < (size_t)S->n) { if (d_rhs) (void)hipFree(d_rhs); d_rhs = nullptr; HIPCHK(hipMalloc((void**)&d_rhs, std::max<size_t>(S->n, 1) * sizeof(double))); d_rhs_cap = S->n; HIPCHK(hipMemset(d_rhs, 0, S->n * sizeof(double))); HIPCHK(hipDeviceSynchronize());
-                                        if (g_solve) { (void)hipGraphExecDestroy(g_solve); g_solve = nullptr; } }
+        if (d_rhs_cap < (size_t)S->n) { if (!ensure_rhs(S->n)) return false; HIPCHK(hipMemset(d_rhs, 0, S->n * sizeof(double))); HIPCHK(hipDeviceSynchronize()); }
         prof_on = true;
         for (int r = 0; r < reps; ++r) {
             if (!enqueue_factor() || !enqueue_solve(d_rhs, d_rhs)) { prof_on = false; return false; }
@@ -1686,8 +1636,7 @@ public:
         // call instead of one per column (round 4: upload, solve, download, synchronise per column).  L is still streamed once per column: the sweeps are
         // written for one vector (panel rows in registers, 16-lane DPP rows); a blocked multi-vector version of them is not built.
         const size_t need = n * (size_t)std::max(nrhs, 1);
-        if (d_rhs_cap < need) { if (d_rhs) (void)hipFree(d_rhs); d_rhs = nullptr; HIPCHK(hipMalloc((void**)&d_rhs, std::max<size_t>(need, 1) * sizeof(double))); d_rhs_cap = need;
-                                if (g_solve) { (void)hipGraphExecDestroy(g_solve); g_solve = nullptr; } }
+        if (!ensure_rhs(need)) return false;
         if ((size_t)ld == n || nrhs == 1) HIPCHK(hipMemcpyAsync(d_rhs, rhs, n * (size_t)nrhs * sizeof(double), hipMemcpyHostToDevice, stream));
         else for (int r = 0; r < nrhs; ++r) HIPCHK(hipMemcpyAsync(d_rhs + (size_t)r * n, rhs + (size_t)r * ld, n * sizeof(double), hipMemcpyHostToDevice, stream));
         if (!solve_device(nrhs, d_rhs, (int)n, d_rhs, (int)n, true)) return false;          // (synchronises once, behind the last column; solve_ms = all columns)
@@ -1769,28 +1718,20 @@ bool Numeric::ruiz_triplet(int device, int n, int nnz, const int* irn, const int
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { err = "no HIP device available (no CPU fallback)"; return false; }
     int dev = device; if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
     DeviceGuard guard(dev);
-#define RCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(e_); ok = false; break; } } while (0)
+    DeviceOwner tmp(err); std::string& err_ = err;      // (an error return frees what was taken; err_: the name HIPCHK reports into)
     int *di = nullptr, *dj = nullptr; double *da = nullptr, *ds = nullptr; unsigned long long* dm = nullptr;
-    bool ok = true;
-    do {
-        RCHK(hipMalloc((void**)&di, std::max(nnz, 1) * sizeof(int))); RCHK(hipMalloc((void**)&dj, std::max(nnz, 1) * sizeof(int)));
-        RCHK(hipMalloc((void**)&da, std::max(nnz, 1) * sizeof(double))); RCHK(hipMalloc((void**)&ds, std::max(n, 1) * sizeof(double)));
-        RCHK(hipMalloc((void**)&dm, std::max(n, 1) * sizeof(unsigned long long)));
-        RCHK(hipMemcpy(di, irn, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice)); RCHK(hipMemcpy(dj, jcn, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
-        RCHK(hipMemcpy(da, a, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
-        RCHK(hipMemset(dm, 0, std::max(n, 1) * sizeof(unsigned long long)));
-        const int g1 = std::max(1, std::min(2048, (n + 255) / 256)), g2 = std::max(1, std::min(2048, (nnz + 255) / 256));
-        hipLaunchKernelGGL(k_fill, dim3(g1), dim3(256), 0, 0, ds, 1.0, (long long)n);
-        for (int it = 0; it < sweeps; ++it) {
-            hipLaunchKernelGGL(k_trip_rowmax, dim3(g2), dim3(256), 0, 0, nnz, (const int*)di, (const int*)dj, (const double*)da, (const double*)ds, dm, base);
-            hipLaunchKernelGGL(k_trip_rescale, dim3(g1), dim3(256), 0, 0, n, ds, dm);
-        }
-        RCHK(hipGetLastError());
-        RCHK(hipMemcpy(out, ds, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    } while (false);
-#undef RCHK
-    (void)hipFree(di); (void)hipFree(dj); (void)hipFree(da); (void)hipFree(ds); (void)hipFree(dm);
-    return ok;
+    if (!tmp.raw(&di, nnz) || !tmp.raw(&dj, nnz) || !tmp.raw(&da, nnz) || !tmp.raw(&ds, n) || !tmp.zeroed(&dm, n)) return false;
+    HIPCHK(hipMemcpy(di, irn, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dj, jcn, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(da, a, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
+    const int g1 = std::max(1, std::min(2048, (n + 255) / 256)), g2 = std::max(1, std::min(2048, (nnz + 255) / 256));
+    hipLaunchKernelGGL(k_fill, dim3(g1), dim3(256), 0, 0, ds, 1.0, (long long)n);
+    for (int it = 0; it < sweeps; ++it) {
+        hipLaunchKernelGGL(k_trip_rowmax, dim3(g2), dim3(256), 0, 0, nnz, (const int*)di, (const int*)dj, (const double*)da, (const double*)ds, dm, base);
+        hipLaunchKernelGGL(k_trip_rescale, dim3(g1), dim3(256), 0, 0, n, ds, dm);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, ds, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return true;
 }
 bool Numeric::set_comm_rccl(const void* unique_id128) { return p_->set_comm_rccl(unique_id128); }
 bool Numeric::set_comm_callback(int (*fn)(void*, void*, int64_t, int, void*), void* ctx) { return p_->set_comm_callback(fn, ctx); }

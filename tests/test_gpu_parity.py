@@ -14,6 +14,7 @@ import os
 
 import numpy as np
 import pytest
+import torch      # (before the library is loaded: torch brings its own HIP runtime, and finds no GPU when the library's has been initialised first)
 
 import ipopt_amd
 from ipopt_amd import kkt
@@ -155,6 +156,55 @@ def test_a_pool_that_does_not_fit_the_device_is_refused_with_the_numbers(monkeyp
     monkeypatch.delenv("MI355X_KKT_POOL_LIMIT_GIB")
     s2, st, x = gpu_factor_solve(n, r, c, v, np.ones(n), check=True, required=neg)      # the same structure without the cap
     assert st == 0
+
+
+def test_a_refused_restructure_gives_the_kept_pool_back(monkeypatch):
+    """A delayed-pivot edit keeps the one-piece pool L | cb of the structure before it for the set-up of the edited one.  When that set-up is refused
+    (here: MI355X_KKT_POOL_LIMIT_GIB set between the factorisation and the edit) the pool still has its owner and goes with the handle: the device's
+    free memory is back to within a quarter of the "needed" figure of the refusal -- a pool that stayed behind is most of that figure.
+    The structure is the smallest of a ladder of grids whose set-up needs at least 64 MiB by a count made on the host from the analysis (a lower bound
+    of the figure in the message: 8 (nnz_l + cb_doubles) + 12 nnz_a + 16 nnz_in + 200 n), far above the allocator's 2 MiB granularity.
+    The same lifecycle with an edit that is NOT refused is the control, under the same bound: if it fails, free memory moved for another reason
+    than this code (a device shared with other processes).  One lifecycle runs before the two that are measured, because the runtime keeps part
+    of what the first handles of a process freed.  Measured on an MI355X with the 60 x 50 grid (250 MiB taken by a factored handle, 92 MiB "needed"
+    by the edited structure): 120-130 MiB stay taken after the first close, with or without an edit; every later lifecycle ends where it began
+    (0.0 MiB) -- and 66.0 MiB, the pool, above it after a refused edit before the pool had an owner."""
+    import re
+    torch.zeros(1, device="cuda"); torch.cuda.synchronize()      # torch's context
+    for nx, ny in [(40, 40), (50, 50), (60, 50), (60, 60), (70, 60), (80, 70)]:
+        n, r, c, v, neg = kktgen.grid_kkt(nx, ny, dof=3, ncon=2, seed=3)
+        s = ipopt_amd.KKTSolver(); s.initialize_structure(n, r, c, vals=v)
+        I = s.info(); s.close()
+        if 8 * (I.nnz_l + I.cb_doubles) + 12 * I.nnz_a + 16 * I.nnz_in + 200 * n >= 64 * 2 ** 20: break
+    else:
+        raise AssertionError("no grid of the ladder needs 64 MiB")
+    cols = np.random.default_rng(7).choice(n, size=8, replace=False) + 1
+
+    def lifecycle(refused):
+        free_before = torch.cuda.mem_get_info()[0]
+        s, st, _ = gpu_factor_solve(n, r, c, v, np.ones(n))
+        assert st == 0
+        message = ""
+        if refused:
+            monkeypatch.setenv("MI355X_KKT_POOL_LIMIT_GIB", "0.01")
+            with pytest.raises(kkt.KKTError, match="does not fit the device") as e:
+                s.delay_columns(cols)
+            monkeypatch.delenv("MI355X_KKT_POOL_LIMIT_GIB")
+            message = str(e.value)
+        else:
+            assert s.delay_columns(cols) > 0
+        s.close()
+        torch.cuda.synchronize()
+        return free_before - torch.cuda.mem_get_info()[0], message
+
+    lifecycle(False)
+    held_control, _ = lifecycle(False)
+    held_refused, message = lifecycle(True)
+    needed = float(re.search(r"([0-9.]+) GiB needed", message).group(1)) * 2 ** 30
+    print(f"needed {needed / 2 ** 20:.1f} MiB; still held after close: {held_control / 2 ** 20:.1f} MiB (edit accepted), {held_refused / 2 ** 20:.1f} MiB (edit refused)")
+    assert needed >= 64 * 2 ** 20
+    assert held_control <= needed / 4, "the control: free memory moved without a refusal"
+    assert held_refused <= needed / 4, "the pool kept for the refused set-up was not freed with the handle"
 
 
 @pytest.mark.parametrize("mode", ["measured-choice", "contexts", "one-after-the-other"])
