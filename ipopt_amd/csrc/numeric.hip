@@ -106,7 +106,9 @@ public:
     // + apply (synth_1e6: 0.93 -> ~0.25 ms of a 16.7 ms factorisation, LukVlE1 10^6: 0.23 -> 0.07 of 0.69).  The reference's MA97 adapter keeps
     // its scaling factors until asked too (IpMa97SolverInterface.cpp:725-771,824-840); they are recomputed here on new W / J / Sigma values, on
     // IncreaseQuality (set_pivtol), after a structure edit and when the scaling mode changes.  Separate graph replays (g_factor_keep*).
-    bool scale_valid = false, keep_scale_now = false, asm_dirty = true;
+    // The kept factors must be those of the LAST factor_assembled: a factorisation of values that k_assemble_segments did not write (factor / refactor)
+    // and assembly_define mark the assembly dirty; scale_valid is set where the equilibrating sequence is LAUNCHED (a graph replay captures it once).
+    bool scale_valid = false, keep_scale_now = false, asm_dirty = true, from_assembly = false;
     double asm_prev_scale[16] = {0};
     hipGraphExec_t g_factor_keep = nullptr, g_factor_full_keep = nullptr;
     void destroy_factor_graphs() {
@@ -254,6 +256,7 @@ public:
         for (int q = 0; q < nseg; ++q) { if (off[q] != total || len[q] < 0) { err_ = "assembly_define: segments must tile [0, nnz) in order"; return false; } total += len[q]; }
         if (total != S->nnz_in) { err_ = "assembly_define: segments do not cover the nnz triplet values"; return false; }
         own_asm.clear(); asm_.nseg = 0;
+        asm_dirty = true; scale_valid = false;      // the sources are zero again: whatever was equilibrated last is another matrix
         double *asm_pool = nullptr, *asm_hpool = nullptr;
         if (!own_asm.zeroed(&asm_pool, (size_t)total)) return false;
         HIPCHK(hipDeviceSynchronize());
@@ -284,8 +287,9 @@ public:
             HIPCHK(hipGetLastError());
             have_values = true;
         }
+        from_assembly = true;
         const bool ok = factor(nullptr, true, st);       // the values are on the device: the "refactor" path, no host buffer involved
-        keep_scale_now = false;
+        from_assembly = false; keep_scale_now = false;
         return ok;
     }
 
@@ -903,6 +907,7 @@ public:
     bool factor(const double* dvals, bool reuse, FactorStats& st) {
         DeviceGuard guard(dev);
         if (!ready) { if (err_.empty()) err_ = "factor: solver not set up (no device?)"; return false; }
+        if (!from_assembly) { asm_dirty = true; scale_valid = false; }      // other values than the assembled ones are equilibrated now: the next factor_assembled starts afresh
         if (multi) return factor_dist(dvals, reuse, st);          // needs a communicator (set_comm_*), fails loudly otherwise
         static const bool opt_off = knob_disabled("optimistic");
         if (!optimistic_ok && opt_wait > 0 && --opt_wait == 0) optimistic_ok = true;   // (one rejection early in an Ipopt run must not cost the optimistic schedule for the life of the structure)
@@ -953,6 +958,7 @@ public:
         } else {
             if (!enqueue_factor()) return false;
         }
+        if (!keep_scale_now && opt.scaling == 1) scale_valid = true;      // V.scale now holds the Ruiz factors of these values, captured sequence or not
         HIPCHK(hipEventRecord(ev1, stream));
         HIPCHK(hipMemcpyAsync(h_stats, d_stats, 12 * sizeof(int), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
