@@ -676,12 +676,17 @@ public:
     int grid1d(long long n) const { long long g = (n + 255) / 256; return (int)std::min<long long>(std::max<long long>(g, 1), 2048); }
 
 
+    // A schedule is a Sched of the plan (P.single, P.local, P.stage[d]) handed to a walker; what only the single-GPU schedule takes -- buckets
+    // sorted by order and their splits, pair kernels, leaf chains -- is asked of the Sched, in the walker (DESIGN.md "Where a launch is decided")
+    bool is_single(const Sched& sc) const { return &sc == &P.single; }
+    static int bucket0(const Sched& sc, int lv, int fc) { return sc.base + sc.ptr[(size_t)lv * FC_COUNT + fc]; }      // bucket (lv, fc) of sc is [bucket0(lv, fc), bucket0(lv, fc + 1)) of the launch list
     // one (level, class) bucket of fronts
-    bool launch_bucket(int lv, int fc, int b0, int b1, int top_mode, int mm, int kk, int tiles, int tiles64) {
-        const int nb = b1 - b0;
+    bool launch_bucket(const Sched& sc, int lv, int fc, int top_mode) {
+        const int b0 = bucket0(sc, lv, fc), b1 = bucket0(sc, lv, fc + 1), nb = b1 - b0;
+        if (nb == 0) return true;
+        const bool sg = is_single(sc);                            // single-GPU schedule: the buckets are sorted by order
         const size_t rl = P.reg_lds[(size_t)lv * FC_COUNT + fc];
         if (fc == FC_WAVE) {
-            const bool sg = b0 == S->level_ptr[(size_t)lv * FC_COUNT + FC_WAVE];                            // single-GPU schedule: the bucket is sorted by order
             const int nt = sg ? P.tiny_split[lv] : 0;
             int fl = top_mode;
             if (V.fastpiv && P.wave_mmin[lv] <= 16) {      // fronts of order <= 16: four per wavefront on the static-order path first; what it accepts is skipped below
@@ -700,7 +705,7 @@ public:
         } else if (fc == FC_LDS64) {
             LAUNCH(KK_FRONT_LDS64, (k_front_reg<64, 8>), dim3(nb), dim3(64), rl, stream, V, b0, top_mode);
         } else if (fc == FC_LDS128) {
-            const int nm = (b0 == S->level_ptr[(size_t)lv * FC_COUNT + FC_LDS128]) ? P.mid_split[lv] : 0;    // single-GPU schedule only
+            const int nm = sg ? P.mid_split[lv] : 0;
             const int fl = top_mode | (V.fastpiv ? 2 : 0);
             // (measured and not kept, r05: in the optimistic schedule the strict launch only on the fronts with > 16 pivots and on a device-built list of
             // the fronts the static-order launch rejected -- 342 of them on synth_1e6 -- instead of the whole bucket: 18.21 against 18.16 ms.  The
@@ -713,13 +718,14 @@ public:
             if (nm > 0) LAUNCH(KK_FRONT_LDS128, (k_front_reg<256, 6>), dim3(nm), dim3(256), P.mid_lds[lv], stream, V, b0, fl);
             if (nb - nm > 0) LAUNCH(KK_FRONT_LDS128, (k_front_reg<256, 8>), dim3(nb - nm), dim3(256), rl, stream, V, b0 + nm, fl);
         } else {
-            const bool single = (b0 == S->level_ptr[(size_t)lv * FC_COUNT + FC_BIG]) && !multi;       // the single-GPU schedule
+            const bool single = sg && !multi;
+            const int mm = sc.maxm[lv], kk = sc.maxk[lv];
             if ((single || multi) && P.grouped && lv >= S->grp_cut_level) {
                 // the chain groups whose first link sits on this level, one launch each (the multi-GPU schedules have their own group lists)
                 if (!(single && P.lv_asm_skip[lv])) launch_assemble(mm, nb, b0, top_mode);
                 return launch_groups(lv, top_mode ? 1 + grp_step : 0);
             }
-            if (!single) { const bool sm = mm <= 640; return launch_big(lv, b0, sm ? b1 : b0, b1, top_mode, mm, kk, sm ? tiles64 : 0, sm ? 0 : tiles, false); }
+            if (!single) { const bool sm = mm <= 640; return launch_big(lv, b0, sm ? b1 : b0, b1, top_mode, mm, kk, sm ? sc.tiles64[lv] : 0, sm ? 0 : sc.tiles[lv], false); }
             return launch_big(lv, b0, b0 + P.big_split[lv], b1, top_mode, mm, kk, P.part_tiles[0][lv], P.part_tiles[1][lv], true);
         }
         return true;
@@ -741,7 +747,7 @@ public:
         if (bs > b0 && G.tiles64[lv] > 0) LAUNCH(KK_BIG_SCHUR, k_big_schur64, dim3(G.tiles64[lv], bs - b0), dim3(256), 0, stream, V, b0, 0);
         if (b1 == bs) return true;
         const int nb = b1 - bs;
-        if (la_pending) { HIPCHK(hipStreamWaitEvent(stream, la_last, 0)); la_pending = false; }      // a full update may touch what an earlier part 2 is still writing
+        if (!la_join()) return false;      // a full update may touch what an earlier part 2 is still writing
         if (G.la2[lv] > 0) {      // (also while profile() records its events: the per-kernel times are those of the TIMED schedule, look-ahead stream included)
             // part 1 in 64 x 64 tiles where the 128 x 128 ones would leave most of the chip idle (k_big_schur_p1); the fronts of the list that are not split
             // get their whole update from a launch of their own then
@@ -749,11 +755,7 @@ public:
                 LAUNCH(KK_BIG_SCHUR, k_big_schur_p1, dim3(G.p1t[lv], nb), dim3(1024), 0, stream, V, bs);
                 if (G.nsplit[lv] < nb) LAUNCH(KK_BIG_SCHUR, k_big_schur, dim3(schur_grid(G.la3[lv]), nb), dim3(SCHUR_NT), 0, stream, V, bs, 4, 0, 0);
             } else LAUNCH(KK_BIG_SCHUR, k_big_schur, dim3(schur_grid(G.la1[lv]), nb), dim3(SCHUR_NT), 0, stream, V, bs, 1, 0, 0);
-            HIPCHK(hipEventRecord(E.A[lv], stream));
-            HIPCHK(hipStreamWaitEvent(stream2, E.A[lv], 0));
-            launch_part2(bs, nb, G.la2[lv]);
-            HIPCHK(hipEventRecord(E.B[lv], stream2));
-            la_last = E.B[lv]; la_pending = true;
+            return la_fork(E.A[lv], E.B[lv], bs, nb, G.la2[lv]);
         } else if (G.tiles[lv] > 0) LAUNCH(KK_BIG_SCHUR, k_big_schur, dim3(schur_grid(G.tiles[lv]), nb), dim3(SCHUR_NT), 0, stream, V, bs, 0, 0, 0);
         return true;
     }
@@ -764,11 +766,19 @@ public:
     const DfLevel* d_dftab = nullptr; int df_grid_cap = 0;      // k_front_df: the levels of the runs (P.df_tab), the largest grid whose workgroups are all resident
     // part 2 of the split updates (second stream, next to the following group's pivot chain): 128 x 128 tiles on 16 wavefronts, or quarter tiles on 4
     // wavefronts that fit on the CUs a k_grp_fused workgroup occupies (kernels_big.hip.inc: k_big_schur_q / _w)
-    void launch_part2(int b0, int nb, int ntiles) {
+    // The look-ahead fork, behind part 1 on the main stream: A recorded there, part 2 of the fronts [b0, b0 + nb) on the second stream behind A, B recorded
+    // behind it -- what la_join() makes the main stream wait for before a later launch may touch what part 2 reads or writes
+    bool la_fork(hipEvent_t A, hipEvent_t B, int b0, int nb, int ntiles) {
         const int nvirt = ((ntiles + 7) / 8) * 32;
         const int wgs = (int)std::min<long long>(nvirt, 4ll * knobs.la_wgs);
+        HIPCHK(hipEventRecord(A, stream));
+        HIPCHK(hipStreamWaitEvent(stream2, A, 0));
         LAUNCH_ON(KK_BIG_SCHUR, stream2, k_big_schur_q, dim3(wgs, nb), dim3(256), 0, stream2, V, b0, ntiles);
+        HIPCHK(hipEventRecord(B, stream2));
+        la_last = B; la_pending = true;
+        return true;
     }
+    bool la_join() { if (la_pending) { HIPCHK(hipStreamWaitEvent(stream, la_last, 0)); la_pending = false; } return true; }
     // The column-chunk kernel pays where a level is MANY fronts of a few hundred rows (short columns: the one-wavefront-per-column kernel runs at the
     // latency of its load chain there) and every front can take its fast path (at most ASM_MAXCH children to pull, not an in-place link with other
     // children, no arena): measured 4.1 -> 2.0 ms per factorisation on synth_1e6, but 3.4 -> 8.7 ms on MBndryCntrl_3D 30, whose levels are a
@@ -814,16 +824,10 @@ public:
         if (b1 == bs) return true;
         const int nb = b1 - bs;
         b0 = bs;
-        if (single && P.la_full[lv] && la_pending) {       // a full update may touch what an earlier part 2 is still writing
-            HIPCHK(hipStreamWaitEvent(stream, la_last, 0)); la_pending = false;
-        }
+        if (single && P.la_full[lv] && !la_join()) return false;       // a full update may touch what an earlier part 2 is still writing
         if (single && P.la_tiles2[lv] > 0) {
             LAUNCH(KK_BIG_SCHUR, k_big_schur, dim3(schur_grid(P.la_tiles1[lv]), nb), dim3(SCHUR_NT), 0, stream, V, b0, 1, 0, 0);
-            HIPCHK(hipEventRecord(la_ev[0].A[lv], stream));
-            HIPCHK(hipStreamWaitEvent(stream2, la_ev[0].A[lv], 0));
-            launch_part2(b0, nb, P.la_tiles2[lv]);
-            HIPCHK(hipEventRecord(la_ev[0].B[lv], stream2));
-            la_last = la_ev[0].B[lv]; la_pending = true;
+            return la_fork(la_ev[0].A[lv], la_ev[0].B[lv], b0, nb, P.la_tiles2[lv]);
         } else if (tiles > 0) LAUNCH(KK_BIG_SCHUR, k_big_schur, dim3(schur_grid(tiles), nb), dim3(SCHUR_NT), 0, stream, V, b0, 0, 0, 0);
         return true;
     }
@@ -870,29 +874,30 @@ public:
                 LAUNCH(KK_FRONT_WAVE, k_front_df, dim3(std::min(R.nq, df_grid_cap)), dim3(64), 0, stream, V, d_dftab + R.tab0, R.nlev, R.nq);
                 lv = R.lv1; continue;
             }
-            if (Sy.cb_window > 0 && lv % Sy.cb_window == 0) {      // recycled contribution blocks (symbolic.cpp step 12a): whatever earlier levels put on the look-ahead streams is
-                if (la_pending) { HIPCHK(hipStreamWaitEvent(stream, la_last, 0)); la_pending = false; }      // through before a level >= lv may write into the space of a block they read
-            }
+            // recycled contribution blocks (symbolic.cpp step 12a): whatever earlier levels put on the look-ahead streams is through before a level >= lv may
+            // write into the space of a block they read.  (The runs above and the leaf-chain prefix skip this join: ADVICE.md item 1.)
+            if (Sy.cb_window > 0 && lv % Sy.cb_window == 0 && !la_join()) return false;
             int lvl_fronts = 0, lvl_max = 0;
-            for (int fc = 0; fc < FC_COUNT; ++fc) { const int nb = Sy.level_ptr[(size_t)lv * FC_COUNT + fc + 1] - Sy.level_ptr[(size_t)lv * FC_COUNT + fc]; lvl_fronts += nb; lvl_max = std::max(lvl_max, nb); }
+            for (int fc = 0; fc < FC_COUNT; ++fc) { const int nb = bucket0(P.single, lv, fc + 1) - bucket0(P.single, lv, fc); lvl_fronts += nb; lvl_max = std::max(lvl_max, nb); }
             bool side_open = false;
             for (int fc = 0; fc < FC_COUNT; ++fc) {
-                const int b0 = Sy.level_ptr[(size_t)lv * FC_COUNT + fc], b1 = Sy.level_ptr[(size_t)lv * FC_COUNT + fc + 1];
-                if (b1 == b0) continue;
+                const int nb = bucket0(P.single, lv, fc + 1) - bucket0(P.single, lv, fc);
+                if (nb == 0) continue;
                 // (the eager schedule only: a multi-stream hipGraph is what factor_once() avoids; not next to the three-stream chain look-ahead)
-                const bool side = side_on && P.la_any && !multi && fc != FC_BIG && b1 - b0 <= SIDE_MAX_FRONTS && lvl_max >= 8 * (b1 - b0) && lvl_fronts > b1 - b0;
-                if (!side) { launch_bucket(lv, fc, b0, b1, 0, P.single.maxm[lv], P.single.maxk[lv], P.single.tiles[lv], P.single.tiles64[lv]); continue; }
-                if ((int)side_evF.size() < Sy.num_levels) { side_evF.resize(Sy.num_levels, nullptr); side_evJ.resize(Sy.num_levels, nullptr); }
-                if (!side_evF[lv] && (!own_struct.event(&side_evF[lv], hipEventDisableTiming) || !own_struct.event(&side_evJ[lv], hipEventDisableTiming))) return false;
-                if (!side_open) { HIPCHK(hipEventRecord(side_evF[lv], stream)); HIPCHK(hipStreamWaitEvent(stream3, side_evF[lv], 0)); side_open = true; }      // behind the level below
-                std::swap(stream, stream3);
-                const bool ok = launch_bucket(lv, fc, b0, b1, 0, P.single.maxm[lv], P.single.maxk[lv], P.single.tiles[lv], P.single.tiles64[lv]);
-                std::swap(stream, stream3);
+                const bool side = side_on && P.la_any && !multi && fc != FC_BIG && nb <= SIDE_MAX_FRONTS && lvl_max >= 8 * nb && lvl_fronts > nb;
+                if (side) {      // the bucket goes to the third stream: the same call with the streams swapped around it
+                    if ((int)side_evF.size() < Sy.num_levels) { side_evF.resize(Sy.num_levels, nullptr); side_evJ.resize(Sy.num_levels, nullptr); }
+                    if (!side_evF[lv] && (!own_struct.event(&side_evF[lv], hipEventDisableTiming) || !own_struct.event(&side_evJ[lv], hipEventDisableTiming))) return false;
+                    if (!side_open) { HIPCHK(hipEventRecord(side_evF[lv], stream)); HIPCHK(hipStreamWaitEvent(stream3, side_evF[lv], 0)); side_open = true; }      // behind the level below
+                    std::swap(stream, stream3);
+                }
+                const bool ok = launch_bucket(P.single, lv, fc, 0);
+                if (side) std::swap(stream, stream3);
                 if (!ok) return false;
             }
             if (side_open) { HIPCHK(hipEventRecord(side_evJ[lv], stream3)); HIPCHK(hipStreamWaitEvent(stream, side_evJ[lv], 0)); }      // the level above reads what they wrote
         }
-        if (la_pending) { HIPCHK(hipStreamWaitEvent(stream, la_last, 0)); la_pending = false; }
+        if (!la_join()) return false;
         LAUNCH(KK_STATS, k_zero_i32, dim3(1), dim3(64), 0, stream, d_stats, 4);
         LAUNCH(KK_STATS, k_reduce_stats, dim3(std::min(64, (Sy.num_sn + 255) / 256)), dim3(256), 0, stream, V.fstat, V.apfail, V.sn_owner, Sy.num_sn, -2, d_stats);
         HIPCHK(hipGetLastError());
@@ -922,17 +927,43 @@ public:
         }
         return true;
     }
-    bool factor_once(const double* dvals, bool reuse, FactorStats& st) {
-        const Symbolic& Sy = *S;
+    // the prelude of a factorisation: thresholds into V, the values onto the device (unless they are there), the matching if one is due, ev0
+    bool stage_values(const double* dvals, bool reuse) {
         V.pivtol = opt.pivtol; V.pivtol2 = std::max(opt.pivtol, opt.pivtolmax); V.small = opt.small;
-        V.norestore = (optimistic && norestore_on) ? 1 : 0;
         if (!reuse) {
-            if (dvals) HIPCHK(hipMemcpyAsync((void*)V.tvals, dvals, Sy.nnz_in * sizeof(double), hipMemcpyDeviceToDevice, stream));
-            else       HIPCHK(hipMemcpyAsync((void*)V.tvals, h_vals, Sy.nnz_in * sizeof(double), hipMemcpyHostToDevice, stream));
+            if (dvals) HIPCHK(hipMemcpyAsync((void*)V.tvals, dvals, S->nnz_in * sizeof(double), hipMemcpyDeviceToDevice, stream));
+            else       HIPCHK(hipMemcpyAsync((void*)V.tvals, h_vals, S->nnz_in * sizeof(double), hipMemcpyHostToDevice, stream));
             have_values = true;
         } else if (!have_values) { err_ = "refactor: no values on the device yet"; return false; }
-        if (want_matching() && Sy.n > 0) { if (!run_matching()) return false; match_valid = true; }
+        if (want_matching() && S->n > 0) { if (!run_matching()) return false; match_valid = true; }
         HIPCHK(hipEventRecord(ev0, stream));
+        return true;
+    }
+    // the tail of a timed entry point: ev1 behind its last launch, an optional read-back behind that, ONE host synchronisation, ev0 -> ev1 into (add: onto) the timer
+    bool finish_timed(double& timer, bool add = false, void* hdst = nullptr, const void* dsrc = nullptr, size_t bytes = 0) {
+        HIPCHK(hipEventRecord(ev1, stream));
+        if (bytes) HIPCHK(hipMemcpyAsync(hdst, dsrc, bytes, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev0, ev1)); timer = add ? timer + ms : ms;
+        return true;
+    }
+    void read_factor_stats(FactorStats& st) const {      // (u_sensitive: a flag on one rank, a sum of flags over several)
+        st.num_neg = h_stats[0]; st.num_zero = h_stats[1]; st.num_two = h_stats[2]; st.num_small = h_stats[3]; st.u_sensitive = h_stats[4] != 0; st.num_fast = h_stats[7];
+    }
+    template <class F> bool capture_into(hipGraphExec_t& exec, F enqueue) {      // the launches of enqueue() as an executable graph
+        hipGraph_t g = nullptr;
+        HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+        const bool ok = enqueue();
+        const hipError_t e = hipStreamEndCapture(stream, &g);
+        if (!ok) return false;
+        if (e != hipSuccess) { err_ = std::string("hipStreamEndCapture: ") + hipGetErrorString(e); return false; }
+        HIPCHK(hipGraphInstantiate(&exec, g, nullptr, nullptr, 0));
+        (void)hipGraphDestroy(g);
+        return true;
+    }
+    bool factor_once(const double* dvals, bool reuse, FactorStats& st) {
+        V.norestore = (optimistic && norestore_on) ? 1 : 0;
+        if (!stage_values(dvals, reuse)) return false;
         // A factorisation with look-ahead forks onto the second stream: it is launched eagerly (measured equal to the graph
         // replay on these ~10^3-launch sequences, whose kernels are long), because a two-stream hipGraph replays up to 1.5x
         // slower once another solver's graphs have been created and destroyed in the same process (ROCm 7.2).
@@ -942,14 +973,7 @@ public:
             }
             hipGraphExec_t& g_factor = keep_scale_now ? (optimistic ? g_factor_keep : g_factor_full_keep) : (optimistic ? this->g_factor : g_factor_full);
             if (!g_factor) {
-                hipGraph_t g = nullptr;
-                HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-                bool ok = enqueue_factor();
-                hipError_t e = hipStreamEndCapture(stream, &g);
-                if (!ok) return false;
-                if (e != hipSuccess) { err_ = std::string("hipStreamEndCapture: ") + hipGetErrorString(e); return false; }
-                HIPCHK(hipGraphInstantiate(&g_factor, g, nullptr, nullptr, 0));
-                (void)hipGraphDestroy(g);
+                if (!capture_into(g_factor, [&] { return enqueue_factor(); })) return false;
                 graph_pivtol = V.pivtol; graph_pivtol2 = V.pivtol2;
                 // the events recorded before capture are still valid; re-record for timing accuracy
                 HIPCHK(hipEventRecord(ev0, stream));
@@ -959,15 +983,77 @@ public:
             if (!enqueue_factor()) return false;
         }
         if (!keep_scale_now && opt.scaling == 1) scale_valid = true;      // V.scale now holds the Ruiz factors of these values, captured sequence or not
-        HIPCHK(hipEventRecord(ev1, stream));
-        HIPCHK(hipMemcpyAsync(h_stats, d_stats, 12 * sizeof(int), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev0, ev1)); factor_ms = ms;
-        st.num_neg = h_stats[0]; st.num_zero = h_stats[1]; st.num_two = h_stats[2]; st.num_small = h_stats[3]; st.u_sensitive = h_stats[4]; st.num_fast = h_stats[7];
+        if (!finish_timed(factor_ms, false, h_stats, d_stats, 12 * sizeof(int))) return false;
+        read_factor_stats(st);
         if (h_stats[5] != 0) { err_ = "factor: a panel workgroup timed out waiting for its pivot block"; return false; }
         return true;
     }
     double graph_pivtol = -1.0, graph_pivtol2 = -1.0;
+
+    // ---- the solve walkers: solve_level holds the only copy of the per-class launch choice, solve_sweep the chain segments, the gate of the solve
+    //      contexts and the leaf chains.  What the single-GPU schedule alone takes is a condition on `single` here ----
+    static size_t lds_solve(int mmax, int kmax) { return (size_t)(mmax + 3 * kmax) * sizeof(double) + 16; }
+    void solve_level(const Sched& sc, int lv, bool forward, int top_mode) {
+        const bool single = is_single(sc), pair = single && P.pair_solve;
+        for (int fc = 0; fc < FC_COUNT; ++fc) {
+            const int b0 = bucket0(sc, lv, fc), nb = bucket0(sc, lv, fc + 1) - b0;
+            if (nb == 0) continue;
+            const int g0 = sc.last0[lv], ng = sc.last1[lv] - g0, mm = sc.maxm[lv];      // FC_BIG: the solve units of the level
+            if (forward) {
+                if (fc == FC_WAVE && pair && P.wave_mmax[lv] <= 16) LAUNCH(KK_FWD_WAVE, (k_fwd_pair<16, 16>), dim3((nb + 3) / 4), dim3(64), 0, stream, V, b0, nb);
+                else if (fc == FC_WAVE && pair && P.wave_kmax[lv] <= 16) LAUNCH(KK_FWD_WAVE, (k_fwd_pair<16>), dim3((nb + 1) / 2), dim3(64), 0, stream, V, b0, nb);
+                else if (fc == FC_WAVE && pair) LAUNCH(KK_FWD_WAVE, (k_fwd_pair<32>), dim3((nb + 1) / 2), dim3(64), 0, stream, V, b0, nb);
+                else if (fc == FC_WAVE)   LAUNCH(KK_FWD_WAVE, (k_fwd<64>),  dim3(nb), dim3(64),  lds_solve(32, 32),   stream, V, b0, top_mode);
+                else if (fc == FC_LDS64)  LAUNCH(KK_FWD_LDS,  (k_fwd<64>),  dim3(nb), dim3(64),  lds_solve(64, 64),   stream, V, b0, top_mode);
+                else if (fc == FC_LDS128) LAUNCH(KK_FWD_LDS,  (k_fwd<256>), dim3(nb), dim3(256), lds_solve(128, 128), stream, V, b0, top_mode);
+                else if (ng <= 0) continue;
+                else if (single && sc.allsolo[lv] && sc.maxk[lv] <= 64) LAUNCH(KK_FWD_BIG, k_fwd_solo64, dim3((mm + 63) / 64 + 1, ng), dim3(256), 0, stream, V, g0);
+                else if ((single || !top_mode) && sc.allsolo[lv]) LAUNCH(KK_FWD_BIG, k_fwd_solo, dim3((mm + 63) / 64 + 1, ng), dim3(256), 0, stream, V, g0);
+                else { LAUNCH(KK_FWD_BIG, k_fwd_grp, dim3(ng), dim3(256), 0, stream, V, g0, top_mode);
+                       LAUNCH(KK_FWD_BIG_UPD, k_fwd_grp_upd, dim3((mm + 63) / 64, ng), dim3(256), 0, stream, V, g0); }
+            } else {
+                if (fc == FC_WAVE && pair && P.wave_mmax[lv] <= 16) LAUNCH(KK_BWD_WAVE, (k_bwd_pair<16, 16>), dim3((nb + 3) / 4), dim3(64), 0, stream, V, b0, nb);
+                else if (fc == FC_WAVE && pair && P.wave_kmax[lv] <= 16) LAUNCH(KK_BWD_WAVE, (k_bwd_pair<16>), dim3((nb + 1) / 2), dim3(64), 0, stream, V, b0, nb);
+                else if (fc == FC_WAVE && pair) LAUNCH(KK_BWD_WAVE, (k_bwd_pair<32>), dim3((nb + 1) / 2), dim3(64), 0, stream, V, b0, nb);
+                else if (fc == FC_WAVE)   LAUNCH(KK_BWD_WAVE, (k_bwd<64>),  dim3(nb), dim3(64),  lds_solve(32, 32),   stream, V, b0);
+                else if (fc == FC_LDS64)  LAUNCH(KK_BWD_LDS,  (k_bwd<64>),  dim3(nb), dim3(64),  lds_solve(64, 64),   stream, V, b0);
+                else if (fc == FC_LDS128) LAUNCH(KK_BWD_LDS,  (k_bwd<256>), dim3(nb), dim3(256), lds_solve(128, 128), stream, V, b0);
+                else if (ng <= 0) continue;
+                else if (single && !S->solve_group && sc.maxk[lv] <= 64) {      // one link per unit: load-hoisted kernels
+                    LAUNCH(KK_BWD_BIG_DOT, k_bwd_dot64, dim3((mm + 255) / 256, ng), dim3(256), 0, stream, V, g0);
+                    LAUNCH(KK_BWD_BIG, k_bwd_fin64, dim3(ng), dim3(256), 0, stream, V, g0);
+                } else {
+                    LAUNCH(KK_BWD_BIG_DOT, k_bwd_grp_dot, dim3((mm + 255) / 256, ng), dim3(256), 0, stream, V, g0);
+                    LAUNCH(KK_BWD_BIG, k_bwd_grp, dim3(ng), dim3(256), 0, stream, V, g0); }
+            }
+        }
+    }
+    // one sweep over the levels of a schedule.  Multi-rank schedules take the chain segments only over the fronts every rank holds (top_mode; use_segs:
+    // the widest exchange step -- pure links have no child from outside), and neither the leaf chains nor the gate
+    bool solve_sweep(const Sched& sc, bool forward, int top_mode, bool use_segs = true) {
+        const int NL = S->num_levels;
+        const bool single = is_single(sc), segs = single || (top_mode && use_segs);
+        int lcs = (single && P.pair_solve && P.lc_levels > 0) ? P.lc_levels : 0;
+        for (int lv = 0; lv < lcs; ++lv) if (P.seg_at_lv0[lv] >= 0) { lcs = 0; break; }      // (a small tree: one data-flow sweep already covers these levels)
+        if (forward && lcs > 0) LAUNCH(KK_FWD_WAVE, k_fwd_leafchain, dim3((P.lc_nchains + 3) / 4), dim3(64), 0, stream, V, P.lc_nchains);
+        for (int q = lcs; q < NL; ++q) {
+            const int lv = forward ? q : NL - 1 + lcs - q;
+            const int sgi = !segs ? -1 : forward ? P.seg_at_lv0[lv] : P.seg_at_lv1[lv];
+            if (sgi < 0) { solve_level(sc, lv, forward, top_mode); continue; }
+            const ChainSeg& sg = P.chain_segs[sgi];      // a run of pure chain levels: one sync-free launch for all of them
+            if (forward) {
+                if (single && gate_on && !gate_entered) { if (gate_valid) HIPCHK(hipStreamWaitEvent(stream, gate_last, 0)); gate_entered = true; }      // (solve contexts: one chain section at a time)
+                LAUNCH(KK_FWD_BIG, k_fwd_chain, dim3(sg.nwg_f), dim3(320), 0, stream, V, sg.wgf0);
+            } else {
+                LAUNCH(KK_BWD_BIG, k_bwd_chain, dim3(sg.nwg_b), dim3(320), 0, stream, V, sg.wgb0);
+                if (single && gate_on && gate_mine) { HIPCHK(hipEventRecord(gate_mine, stream)); gate_last = gate_mine; gate_valid = true; }
+            }
+            q += sg.lv1 - sg.lv0;
+        }
+        if (!forward && lcs > 0) LAUNCH(KK_BWD_WAVE, k_bwd_leafchain, dim3((P.lc_nchains + 3) / 4), dim3(64), 0, stream, V, P.lc_nchains);
+        HIPCHK(hipGetLastError());
+        return true;
+    }
 
     // The sweeps only touch the solver's own buffers, so ONE captured graph serves every right-hand side: the two kernels
     // that see the caller's pointers (k_load_rhs / k_store_sol) are launched eagerly around the replay.
@@ -979,8 +1065,7 @@ public:
         return true;
     }
     bool enqueue_solve_core() {
-        const Symbolic& Sy = *S;
-        const int n = Sy.n;
+        const int n = S->n;
         const int nref = opt.refine_steps > 0 ? opt.refine_steps : 0;
         if (nref > 0) LAUNCH(KK_SOLVE_PERM, k_save_rhs, dim3(grid1d(n)), dim3(256), 0, stream, V);
         for (int pass = 0; pass <= nref; ++pass) {
@@ -988,62 +1073,8 @@ public:
                 LAUNCH(KK_SOLVE_PERM, k_refine_residual, dim3(grid1d(n)), dim3(256), 0, stream, V, pass == 1 ? 1 : 0);
                 LAUNCH(KK_SOLVE_PERM, k_refine_spmv, dim3(grid1d(n)), dim3(256), 0, stream, V);
             }
-            auto lds_solve = [](int mmax, int kmax) { return (size_t)(mmax + 3 * kmax) * sizeof(double) + 16; };
             if (!P.chain_segs.empty()) LAUNCH(KK_SOLVE_PERM, k_bump_epoch, dim3(1), dim3(64), 0, stream, V.sepoch);
-            int lcs = (P.pair_solve && P.lc_levels > 0) ? P.lc_levels : 0;
-            for (int lv = 0; lv < lcs; ++lv) if (P.seg_at_lv0[lv] >= 0) { lcs = 0; break; }      // (a small tree: one data-flow sweep already covers these levels)
-            if (lcs > 0) LAUNCH(KK_FWD_WAVE, k_fwd_leafchain, dim3((P.lc_nchains + 3) / 4), dim3(64), 0, stream, V, P.lc_nchains);
-            for (int lv = lcs; lv < Sy.num_levels; ++lv) {
-                if (P.seg_at_lv0[lv] >= 0) {      // a run of pure chain levels: one sync-free launch for all of them
-                    const ChainSeg& sg = P.chain_segs[P.seg_at_lv0[lv]];
-                    if (gate_on && !gate_entered) { if (gate_valid) HIPCHK(hipStreamWaitEvent(stream, gate_last, 0)); gate_entered = true; }      // (solve contexts: one chain section at a time)
-                    LAUNCH(KK_FWD_BIG, k_fwd_chain, dim3(sg.nwg_f), dim3(320), 0, stream, V, sg.wgf0);
-                    lv = sg.lv1; continue;
-                }
-                for (int fc = 0; fc < FC_COUNT; ++fc) {
-                    const int b0 = Sy.level_ptr[(size_t)lv * FC_COUNT + fc], b1 = Sy.level_ptr[(size_t)lv * FC_COUNT + fc + 1];
-                    if (b1 == b0) continue;
-                    if (fc == FC_WAVE && P.pair_solve && P.wave_mmax[lv] <= 16) LAUNCH(KK_FWD_WAVE, (k_fwd_pair<16, 16>), dim3((b1 - b0 + 3) / 4), dim3(64), 0, stream, V, b0, b1 - b0);
-                    else if (fc == FC_WAVE && P.pair_solve && P.wave_kmax[lv] <= 16) LAUNCH(KK_FWD_WAVE, (k_fwd_pair<16>), dim3((b1 - b0 + 1) / 2), dim3(64), 0, stream, V, b0, b1 - b0);
-                    else if (fc == FC_WAVE && P.pair_solve)                   LAUNCH(KK_FWD_WAVE, (k_fwd_pair<32>), dim3((b1 - b0 + 1) / 2), dim3(64), 0, stream, V, b0, b1 - b0);
-                    else if (fc == FC_WAVE)   LAUNCH(KK_FWD_WAVE, (k_fwd<64>),  dim3(b1 - b0), dim3(64),  lds_solve(32, 32),   stream, V, b0, 0);
-                    else if (fc == FC_LDS64)  LAUNCH(KK_FWD_LDS,  (k_fwd<64>),  dim3(b1 - b0), dim3(64),  lds_solve(64, 64),   stream, V, b0, 0);
-                    else if (fc == FC_LDS128) LAUNCH(KK_FWD_LDS,  (k_fwd<256>), dim3(b1 - b0), dim3(256), lds_solve(128, 128), stream, V, b0, 0);
-                    else if (P.single.last1[lv] > P.single.last0[lv]) {
-                           const int g0 = P.single.last0[lv], ng = P.single.last1[lv] - g0;
-                           if (P.single.allsolo[lv] && P.single.maxk[lv] <= 64) LAUNCH(KK_FWD_BIG, k_fwd_solo64, dim3((P.single.maxm[lv] + 63) / 64 + 1, ng), dim3(256), 0, stream, V, g0);
-                           else if (P.single.allsolo[lv]) LAUNCH(KK_FWD_BIG, k_fwd_solo, dim3((P.single.maxm[lv] + 63) / 64 + 1, ng), dim3(256), 0, stream, V, g0);
-                           else { LAUNCH(KK_FWD_BIG, k_fwd_grp, dim3(ng), dim3(256), 0, stream, V, g0, 0);
-                                  LAUNCH(KK_FWD_BIG_UPD, k_fwd_grp_upd, dim3((P.single.maxm[lv] + 63) / 64, ng), dim3(256), 0, stream, V, g0); } }
-                }
-            }
-            for (int lv = Sy.num_levels - 1; lv >= lcs; --lv) {
-                if (P.seg_at_lv1[lv] >= 0) {
-                    const ChainSeg& sg = P.chain_segs[P.seg_at_lv1[lv]];
-                    LAUNCH(KK_BWD_BIG, k_bwd_chain, dim3(sg.nwg_b), dim3(320), 0, stream, V, sg.wgb0);
-                    if (gate_on && gate_mine) { HIPCHK(hipEventRecord(gate_mine, stream)); gate_last = gate_mine; gate_valid = true; }
-                    lv = sg.lv0; continue;
-                }
-                for (int fc = 0; fc < FC_COUNT; ++fc) {
-                    const int b0 = Sy.level_ptr[(size_t)lv * FC_COUNT + fc], b1 = Sy.level_ptr[(size_t)lv * FC_COUNT + fc + 1];
-                    if (b1 == b0) continue;
-                    if (fc == FC_WAVE && P.pair_solve && P.wave_mmax[lv] <= 16) LAUNCH(KK_BWD_WAVE, (k_bwd_pair<16, 16>), dim3((b1 - b0 + 3) / 4), dim3(64), 0, stream, V, b0, b1 - b0);
-                    else if (fc == FC_WAVE && P.pair_solve && P.wave_kmax[lv] <= 16) LAUNCH(KK_BWD_WAVE, (k_bwd_pair<16>), dim3((b1 - b0 + 1) / 2), dim3(64), 0, stream, V, b0, b1 - b0);
-                    else if (fc == FC_WAVE && P.pair_solve)                   LAUNCH(KK_BWD_WAVE, (k_bwd_pair<32>), dim3((b1 - b0 + 1) / 2), dim3(64), 0, stream, V, b0, b1 - b0);
-                    else if (fc == FC_WAVE)   LAUNCH(KK_BWD_WAVE, (k_bwd<64>),  dim3(b1 - b0), dim3(64),  lds_solve(32, 32),   stream, V, b0);
-                    else if (fc == FC_LDS64)  LAUNCH(KK_BWD_LDS,  (k_bwd<64>),  dim3(b1 - b0), dim3(64),  lds_solve(64, 64),   stream, V, b0);
-                    else if (fc == FC_LDS128) LAUNCH(KK_BWD_LDS,  (k_bwd<256>), dim3(b1 - b0), dim3(256), lds_solve(128, 128), stream, V, b0);
-                    else if (P.single.last1[lv] > P.single.last0[lv]) {
-                           const int g0 = P.single.last0[lv], ng = P.single.last1[lv] - g0;
-                           if (!Sy.solve_group && P.single.maxk[lv] <= 64) {      // one link per unit: load-hoisted kernels
-                               LAUNCH(KK_BWD_BIG_DOT, k_bwd_dot64, dim3((P.single.maxm[lv] + 255) / 256, ng), dim3(256), 0, stream, V, g0);
-                               LAUNCH(KK_BWD_BIG, k_bwd_fin64, dim3(ng), dim3(256), 0, stream, V, g0);
-                           } else {
-                               LAUNCH(KK_BWD_BIG_DOT, k_bwd_grp_dot, dim3((P.single.maxm[lv] + 255) / 256, ng), dim3(256), 0, stream, V, g0);
-                               LAUNCH(KK_BWD_BIG, k_bwd_grp, dim3(ng), dim3(256), 0, stream, V, g0); } }
-                }
-            }
-            if (lcs > 0) LAUNCH(KK_BWD_WAVE, k_bwd_leafchain, dim3((P.lc_nchains + 3) / 4), dim3(64), 0, stream, V, P.lc_nchains);
+            if (!solve_sweep(P.single, true, 0) || !solve_sweep(P.single, false, 0)) return false;
         }
         if (nref > 0) LAUNCH(KK_SOLVE_PERM, k_refine_finish, dim3(grid1d(n)), dim3(256), 0, stream, V);
         HIPCHK(hipGetLastError());
@@ -1094,35 +1125,18 @@ public:
         }
         return true;
     }
-    // the solver works in context c from here on (c = 0: back to its own workspace and stream); `saved` keeps what context 0 owns
-    struct SctxSaved { hipStream_t strm; hipGraphExec_t graph; SolveCtx w; };
-    void sctx_enter(int c, SctxSaved& sv) {
-        sv.strm = stream; sv.graph = g_solve;
-        sv.w.xw = V.xw; sv.w.cvec = V.cvec; sv.w.bw = V.bw; sv.w.xacc = V.xacc; sv.w.gpart = V.gpart; sv.w.zb = V.zb; sv.w.ybuf = V.ybuf; sv.w.dpart = V.dpart;
-        sv.w.sflag_t = V.sflag_t; sv.w.sflag_dot = V.sflag_dot; sv.w.sflag_b = V.sflag_b; sv.w.sepoch = V.sepoch; sv.w.ytag = V.ytag; sv.w.xtag = V.xtag;
-        const SolveCtx& X = sctx[c];
-        stream = X.strm; g_solve = X.graph;
-        V.xw = X.xw; V.cvec = X.cvec; V.bw = X.bw; V.xacc = X.xacc; V.gpart = X.gpart; V.zb = X.zb; V.ybuf = X.ybuf; V.dpart = X.dpart;
-        V.sflag_t = X.sflag_t; V.sflag_dot = X.sflag_dot; V.sflag_b = X.sflag_b; V.sepoch = X.sepoch; V.ytag = X.ytag; V.xtag = X.xtag;
-    }
-    void sctx_leave(int c, const SctxSaved& sv) {
-        sctx[c].graph = g_solve;          // (captured on first use)
-        stream = sv.strm; g_solve = sv.graph;
-        V.xw = sv.w.xw; V.cvec = sv.w.cvec; V.bw = sv.w.bw; V.xacc = sv.w.xacc; V.gpart = sv.w.gpart; V.zb = sv.w.zb; V.ybuf = sv.w.ybuf; V.dpart = sv.w.dpart;
-        V.sflag_t = sv.w.sflag_t; V.sflag_dot = sv.w.sflag_dot; V.sflag_b = sv.w.sflag_b; V.sepoch = sv.w.sepoch; V.ytag = sv.w.ytag; V.xtag = sv.w.xtag;
+    // the solver's stream, solve graph and work pointers change places with those of context c: from the first call to the second it works in that
+    // context (a graph captured in between is the context's), the second restores its own
+    void sctx_swap(int c) {
+        SolveCtx& X = sctx[c];
+        std::swap(stream, X.strm); std::swap(g_solve, X.graph);
+        std::swap(V.xw, X.xw); std::swap(V.cvec, X.cvec); std::swap(V.bw, X.bw); std::swap(V.xacc, X.xacc); std::swap(V.gpart, X.gpart); std::swap(V.zb, X.zb); std::swap(V.ybuf, X.ybuf);
+        std::swap(V.dpart, X.dpart); std::swap(V.sflag_t, X.sflag_t); std::swap(V.sflag_dot, X.sflag_dot); std::swap(V.sflag_b, X.sflag_b); std::swap(V.sepoch, X.sepoch);
+        std::swap(V.ytag, X.ytag); std::swap(V.xtag, X.xtag);
     }
     bool solve_one(const double* src, double* col) {      // one right-hand side in the CURRENT context (stream, V's work vectors, g_solve)
         if (opt.use_graph) {
-            if (!g_solve) {
-                hipGraph_t g = nullptr;
-                HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-                bool ok = enqueue_solve_core();
-                hipError_t e = hipStreamEndCapture(stream, &g);
-                if (!ok) return false;
-                if (e != hipSuccess) { err_ = std::string("hipStreamEndCapture: ") + hipGetErrorString(e); return false; }
-                HIPCHK(hipGraphInstantiate(&g_solve, g, nullptr, nullptr, 0));
-                (void)hipGraphDestroy(g);
-            }
+            if (!g_solve && !capture_into(g_solve, [&] { return enqueue_solve_core(); })) return false;
             hipLaunchKernelGGL(k_load_rhs, dim3(grid1d(S->n)), dim3(256), 0, stream, V, src);
             HIPCHK(hipGraphLaunch(g_solve, stream));
             hipLaunchKernelGGL(k_store_sol, dim3(grid1d(S->n)), dim3(256), 0, stream, V, col);
@@ -1178,10 +1192,9 @@ public:
                 double* col = drhs + (size_t)r * ld;
                 const double* src = dsrc + (size_t)r * lds_;
                 gate_mine = gate_ev[c]; gate_entered = false;
-                SctxSaved sv;
-                if (c > 0) sctx_enter(c, sv);
+                if (c > 0) sctx_swap(c);
                 ok = enqueue_solve(src, col);          // eager: the gate of the chain sections is an event between the contexts' streams
-                if (c > 0) sctx_leave(c, sv);
+                if (c > 0) sctx_swap(c);
             }
             gate_on = false; gate_mine = nullptr;
             if (!ok) return false;
@@ -1192,10 +1205,7 @@ public:
         } else
             for (int r = 0; r < nrhs; ++r) if (!solve_one(dsrc + (size_t)r * lds_, drhs + (size_t)r * ld)) return false;
         if (timed) {
-            HIPCHK(hipEventRecord(ev1, stream));
-            if (!P.chain_segs.empty()) HIPCHK(hipMemcpyAsync(h_stats + 6, V.sepoch + 1, sizeof(int), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev0, ev1)); solve_ms = ms;
+            if (!finish_timed(solve_ms, false, h_stats + 6, V.sepoch + 1, P.chain_segs.empty() ? 0 : sizeof(int))) return false;
             if (V.strace) {
                 std::vector<unsigned long long> h(strace_n);
                 HIPCHK(hipMemcpy(h.data(), V.strace, strace_n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
@@ -1352,53 +1362,8 @@ public:
 
     // ---------------- multi-GPU orchestration (eager launches) ----------------
     bool launch_fronts(const Sched& sc, int top_mode) {
-        const Symbolic& Sy = *S;
-        for (int lv = 0; lv < Sy.num_levels; ++lv)
-            for (int fc = 0; fc < FC_COUNT; ++fc) {
-                const int b0 = sc.base + sc.ptr[(size_t)lv * FC_COUNT + fc], b1 = sc.base + sc.ptr[(size_t)lv * FC_COUNT + fc + 1];
-                if (b1 == b0) continue;
-                launch_bucket(lv, fc, b0, b1, top_mode, sc.maxm[lv], sc.maxk[lv], sc.tiles[lv], sc.tiles64[lv]);
-            }
-        HIPCHK(hipGetLastError());
-        return true;
-    }
-    bool launch_solve_sweep(const Sched& sc, bool forward, int top_mode, bool use_segs = true) {
-        const Symbolic& Sy = *S;
-        auto lds_solve = [](int mmax, int kmax) { return (size_t)(mmax + 3 * kmax) * sizeof(double) + 16; };
-        for (int q = 0; q < Sy.num_levels; ++q) {
-            const int lv = forward ? q : Sy.num_levels - 1 - q;
-            if (top_mode && use_segs && !P.chain_segs.empty()) {      // runs of pure chain levels of the fronts every rank holds: the sync-free sweeps (pure links have no child from outside)
-                const int sgi = forward ? P.seg_at_lv0[lv] : P.seg_at_lv1[lv];
-                if (sgi >= 0) {
-                    const ChainSeg& sg = P.chain_segs[sgi];
-                    if (forward) hipLaunchKernelGGL(k_fwd_chain, dim3(sg.nwg_f), dim3(320), 0, stream, V, sg.wgf0);
-                    else hipLaunchKernelGGL(k_bwd_chain, dim3(sg.nwg_b), dim3(320), 0, stream, V, sg.wgb0);
-                    q += sg.lv1 - sg.lv0; continue;
-                }
-            }
-            for (int fc = 0; fc < FC_COUNT; ++fc) {
-                const int b0 = sc.base + sc.ptr[(size_t)lv * FC_COUNT + fc], b1 = sc.base + sc.ptr[(size_t)lv * FC_COUNT + fc + 1];
-                if (b1 == b0) continue;
-                if (forward) {
-                    if (fc == FC_WAVE)        hipLaunchKernelGGL((k_fwd<64>),  dim3(b1 - b0), dim3(64),  lds_solve(32, 32),   stream, V, b0, top_mode);
-                    else if (fc == FC_LDS64)  hipLaunchKernelGGL((k_fwd<64>),  dim3(b1 - b0), dim3(64),  lds_solve(64, 64),   stream, V, b0, top_mode);
-                    else if (fc == FC_LDS128) hipLaunchKernelGGL((k_fwd<256>), dim3(b1 - b0), dim3(256), lds_solve(128, 128), stream, V, b0, top_mode);
-                    else if (sc.last1[lv] > sc.last0[lv]) {
-                           const int g0 = sc.last0[lv], ng = sc.last1[lv] - g0;
-                           if (!top_mode && sc.allsolo[lv]) hipLaunchKernelGGL(k_fwd_solo, dim3((sc.maxm[lv] + 63) / 64 + 1, ng), dim3(256), 0, stream, V, g0);
-                           else { hipLaunchKernelGGL(k_fwd_grp, dim3(ng), dim3(256), 0, stream, V, g0, top_mode);
-                                  hipLaunchKernelGGL(k_fwd_grp_upd, dim3((sc.maxm[lv] + 63) / 64, ng), dim3(256), 0, stream, V, g0); } }
-                } else {
-                    if (fc == FC_WAVE)        hipLaunchKernelGGL((k_bwd<64>),  dim3(b1 - b0), dim3(64),  lds_solve(32, 32),   stream, V, b0);
-                    else if (fc == FC_LDS64)  hipLaunchKernelGGL((k_bwd<64>),  dim3(b1 - b0), dim3(64),  lds_solve(64, 64),   stream, V, b0);
-                    else if (fc == FC_LDS128) hipLaunchKernelGGL((k_bwd<256>), dim3(b1 - b0), dim3(256), lds_solve(128, 128), stream, V, b0);
-                    else if (sc.last1[lv] > sc.last0[lv]) {
-                           const int g0 = sc.last0[lv], ng = sc.last1[lv] - g0;
-                           hipLaunchKernelGGL(k_bwd_grp_dot, dim3((sc.maxm[lv] + 255) / 256, ng), dim3(256), 0, stream, V, g0);
-                           hipLaunchKernelGGL(k_bwd_grp, dim3(ng), dim3(256), 0, stream, V, g0); }
-                }
-            }
-        }
+        for (int lv = 0; lv < S->num_levels; ++lv)
+            for (int fc = 0; fc < FC_COUNT; ++fc) if (!launch_bucket(sc, lv, fc, top_mode)) return false;
         HIPCHK(hipGetLastError());
         return true;
     }
@@ -1408,11 +1373,7 @@ public:
     bool factor_local(const double* dvals) {
         DeviceGuard guard(dev);
         if (!one_step("factor_local")) return false;
-        if (!enqueue_factor_local(dvals, false)) return false;
-        HIPCHK(hipEventRecord(ev1, stream));
-        HIPCHK(hipStreamSynchronize(stream));       // the caller's collective runs on another stream
-        float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev0, ev1)); factor_ms = ms;
-        return true;
+        return enqueue_factor_local(dvals, false) && finish_timed(factor_ms);       // (synchronised: the caller's collective runs on another stream)
     }
     bool report_to_arena(int kind) {
         const JoinList& J = P.join[kind];
@@ -1429,17 +1390,9 @@ public:
     // own subtrees + own contributions to the arena squares above them, enqueued on the solver's stream (no host synchronisation)
     bool enqueue_factor_local(const double* dvals, bool reuse) {
         if (!ready || !multi) { err_ = "factor_local: not a multi-GPU handle (nranks must be > 1 at create)"; return false; }
-        const Symbolic& Sy = *S; const int n = Sy.n;
-        V.pivtol = opt.pivtol; V.pivtol2 = std::max(opt.pivtol, opt.pivtolmax); V.small = opt.small;
-        if (!reuse) {
-            if (dvals) HIPCHK(hipMemcpyAsync((void*)V.tvals, dvals, Sy.nnz_in * sizeof(double), hipMemcpyDeviceToDevice, stream));
-            else       HIPCHK(hipMemcpyAsync((void*)V.tvals, h_vals, Sy.nnz_in * sizeof(double), hipMemcpyHostToDevice, stream));
-            have_values = true;
-        } else if (!have_values) { err_ = "refactor: no values on the device yet"; return false; }
-        if (want_matching() && n > 0) { if (!run_matching()) return false; match_valid = true; }
-        HIPCHK(hipEventRecord(ev0, stream));
-        hipLaunchKernelGGL(k_factor_prologue, dim3(grid1d(n)), dim3(256), 0, stream, V);
-        hipLaunchKernelGGL(k_gather_values, dim3(grid1d(Sy.nnz_a)), dim3(256), 0, stream, V);
+        if (!stage_values(dvals, reuse)) return false;
+        hipLaunchKernelGGL(k_factor_prologue, dim3(grid1d(S->n)), dim3(256), 0, stream, V);
+        hipLaunchKernelGGL(k_gather_values, dim3(grid1d(S->nnz_a)), dim3(256), 0, stream, V);
         enqueue_scaling();
         if (!launch_fronts(P.local, 0)) return false;
         HIPCHK(hipMemsetAsync(V.arena, 0, (size_t)P.ex.arena_doubles * sizeof(double), stream));
@@ -1473,11 +1426,8 @@ public:
         }
         if (!enqueue_stats()) return false;
         if (!allreduce(d_stats, 8, 1)) return false;
-        HIPCHK(hipEventRecord(ev1, stream));
-        HIPCHK(hipMemcpyAsync(h_stats, d_stats, 8 * sizeof(int), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev0, ev1)); factor_ms = ms;
-        st.num_neg = h_stats[0]; st.num_zero = h_stats[1]; st.num_two = h_stats[2]; st.num_small = h_stats[3]; st.u_sensitive = h_stats[4] != 0; st.num_fast = h_stats[7];
+        if (!finish_timed(factor_ms, false, h_stats, d_stats, 8 * sizeof(int))) return false;
+        read_factor_stats(st);
         if (h_stats[5] != 0) { err_ = "factor: a panel workgroup timed out waiting for its pivot block on some rank (workgroups not co-resident?)"; return false; }      // (a sum over the ranks)
         return true;
     }
@@ -1485,8 +1435,7 @@ public:
         hipLaunchKernelGGL(k_load_rhs, dim3(grid1d(S->n)), dim3(256), 0, stream, V, src);
         if (!P.chain_segs.empty()) hipLaunchKernelGGL(k_bump_epoch, dim3(1), dim3(64), 0, stream, V.sepoch);
         if (P.ex.toprhs_doubles > 0) HIPCHK(hipMemsetAsync(V.top_rhs, 0, (size_t)P.ex.toprhs_doubles * sizeof(double), stream));
-        if (!launch_solve_sweep(P.local, true, 0)) return false;
-        return report_to_top_rhs(0);
+        return solve_sweep(P.local, true, 0) && report_to_top_rhs(0);
     }
     // distributed solve of one right-hand side (identical on every rank), solution on every rank:
     //   local forward -> per exchange step, deepest first: all-reduce(that step's top right-hand sides) -> forward on the step's fronts ->
@@ -1499,19 +1448,16 @@ public:
             if (!enqueue_fwd_local(src)) return false;
             for (int d = P.ndepth - 1; d >= 0; --d) {
                 if (!exchange_step(d, 1)) return false;
-                if (!launch_solve_sweep(P.stage[d], true, 1, d == 0)) return false;
+                if (!solve_sweep(P.stage[d], true, 1, d == 0)) return false;
                 if (d > 0 && !report_to_top_rhs(1 + d)) return false;
             }
-            for (int d = 0; d < P.ndepth; ++d) if (!launch_solve_sweep(P.stage[d], false, 1, d == 0)) return false;
-            if (!launch_solve_sweep(P.local, false, 0)) return false;
+            for (int d = 0; d < P.ndepth; ++d) if (!solve_sweep(P.stage[d], false, 1, d == 0)) return false;
+            if (!solve_sweep(P.local, false, 0)) return false;
             hipLaunchKernelGGL(k_store_sol_mg, dim3(grid1d(S->n)), dim3(256), 0, stream, V, col);
             HIPCHK(hipGetLastError());
             if (!allreduce(col, S->n, 0)) return false;
         }
-        HIPCHK(hipEventRecord(ev1, stream));
-        if (!P.chain_segs.empty()) HIPCHK(hipMemcpyAsync(h_stats + 6, V.sepoch + 1, sizeof(int), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev0, ev1)); solve_ms = ms;
+        if (!finish_timed(solve_ms, false, h_stats + 6, V.sepoch + 1, P.chain_segs.empty() ? 0 : sizeof(int))) return false;
         if (!P.chain_segs.empty() && h_stats[6] != 0) { err_ = "solve: a chain sweep timed out waiting for its predecessor on this rank (workgroups not co-resident: several ranks on one GPU?)"; return false; }
         return true;
     }
@@ -1522,9 +1468,8 @@ public:
         HIPCHK(hipEventRecord(ev0, stream));
         if (!enqueue_factor_step(0) || !enqueue_stats()) return false;
         HIPCHK(hipMemcpyAsync(h_stats, d_stats, 8 * sizeof(int), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipEventRecord(ev1, stream)); HIPCHK(hipStreamSynchronize(stream));
-        st.num_neg = h_stats[0]; st.num_zero = h_stats[1]; st.num_two = h_stats[2]; st.num_small = h_stats[3]; st.u_sensitive = h_stats[4]; st.num_fast = h_stats[7];
-        float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev0, ev1)); factor_ms += ms;
+        if (!finish_timed(factor_ms, true)) return false;      // (added to factor_local's time)
+        read_factor_stats(st);
         return true;
     }
     bool solve_fwd_local(double* drhs) {
@@ -1532,24 +1477,17 @@ public:
         if (!ready || !multi) { err_ = "solve_fwd_local: not a multi-GPU handle"; return false; }
         if (!one_step("solve_fwd_local")) return false;
         HIPCHK(hipEventRecord(ev0, stream));
-        if (!enqueue_fwd_local((const double*)drhs)) return false;
-        HIPCHK(hipEventRecord(ev1, stream)); HIPCHK(hipStreamSynchronize(stream));
-        float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev0, ev1)); solve_ms = ms;
-        return true;
+        return enqueue_fwd_local((const double*)drhs) && finish_timed(solve_ms);
     }
     bool solve_top_and_bwd(double* drhs) {
         DeviceGuard guard(dev);
         if (!ready || !multi) { err_ = "solve_top_and_bwd: not a multi-GPU handle"; return false; }
         if (!one_step("solve_top_and_bwd")) return false;
         HIPCHK(hipEventRecord(ev0, stream));
-        if (!launch_solve_sweep(P.stage[0], true, 1)) return false;
-        if (!launch_solve_sweep(P.stage[0], false, 1)) return false;
-        if (!launch_solve_sweep(P.local, false, 0)) return false;
+        if (!solve_sweep(P.stage[0], true, 1) || !solve_sweep(P.stage[0], false, 1) || !solve_sweep(P.local, false, 0)) return false;
         hipLaunchKernelGGL(k_store_sol_mg, dim3(grid1d(S->n)), dim3(256), 0, stream, V, drhs);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev1, stream)); HIPCHK(hipStreamSynchronize(stream));
-        float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev0, ev1)); solve_ms += ms;
-        return true;
+        return finish_timed(solve_ms, true);      // (added to solve_fwd_local's time)
     }
 
     // indices (original numbering, 0-based) of the columns whose pivot was (numerically) zero in the last factorisation
