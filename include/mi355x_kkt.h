@@ -209,6 +209,32 @@ int  mi355x_kkt_solve_device(mi355x_kkt_handle h, int nrhs, double* d_rhs_inout,
  * stream that produced them). */
 int  mi355x_kkt_solve_device2(mi355x_kkt_handle h, int nrhs, const double* d_b, int ldb, double* d_x, int ldx);
 
+/* ---- low-rank update of the factored system: solve with K~ = K + V V^T - U U^T -------------------------------------------------------
+ * What the reference's LowRankAugSystemSolver does around an augmented-system solver when `hessian_approximation limited-memory` hands it
+ * W = B0 + V V^T - U U^T (IpLowRankAugSystemSolver.cpp): factor K with W = diag(B0), solve for the columns of the update and factor two small
+ * dense matrices (UpdateFactorization, :299-396), correct every later solve by Sherman-Morrison (Solve, :195-228) -- with the tall-skinny
+ * algebra on the device instead of host MultiVectorMatrix products (HighRankUpdateTranspose :319,:367,:383; AddRightMultMatrix :370).
+ * V is rows x nv, U is rows x nu; they act on the FIRST `rows` indices of the caller's numbering (Ipopt's x block; zero rows below):
+ *   update:  Z1 = K^-1 V,  M1 = I + sym(V^T Z1),  W1 = K^-1 U,  C = M1^-1 (Z1^T U),  Z2 = W1 - Z1 C,  M2 = I - sym(U^T Z2),  sym(G) = (G + G^T) / 2
+ *   solve:   x0 = K^-1 b,  x1 = x0 - Z1 M1^-1 (V^T x0),  x = x1 + Z2 M2^-1 (U^T x1)      (the reference's Z^T b taken from the running solution: in place)
+ * M1 and M2 positive definite <=> K~ has K's inertia; a Cholesky failure is the reference's "wrong inertia" answer (ComputeCholeskyFactor :323, :387 -> SYMSOLVER_WRONG_INERTIA :330, :392).
+ *   _lowrank_set     V, U: HOST memory, column-major V[j*ldv + i]; copied and kept on the device across refactorisations and delayed-pivot structure
+ *                    edits, until the next _lowrank_set or _lowrank_clear.  Marks the update not current.
+ *   _lowrank_update  after a factorisation: SUCCESS, or WRONG_INERTIA with *which_failed (may be NULL) = 1 (M1) / 2 (M2) -- then no update is in force
+ *   _lowrank_solve / _lowrank_solve_device2   the contracts of _solve / _solve_device2 with K~ in the place of K.  They need a CURRENT update: one
+ *                    that _lowrank_update completed on the factorisation now in the handle (every factor / refactor / factor_assembled ends it); FATAL otherwise
+ *   _lowrank_clear   removes the update;  _lowrank_info   what is set, whether it is current, host ms of the last _lowrank_update (outputs may be NULL)
+ * While an update is set, _pd_solve_once applies the correction to the 4-block solution (it needs a current update) and _pd_residual adds
+ * V (V^T res_x) - U (U^T res_x) to the x rows, so the W segment of the assembly carries B0 only; both need rows <= n_x.
+ * Arguments are checked before the device is touched; single-GPU handles only (nranks > 1: FATAL). */
+#define MI355X_KKT_LOWRANK_MAX 32                       /* columns of V, and of U */
+int  mi355x_kkt_lowrank_set(mi355x_kkt_handle h, int rows, int nv, const double* V, int ldv, int nu, const double* U, int ldu);
+int  mi355x_kkt_lowrank_update(mi355x_kkt_handle h, int* which_failed);
+int  mi355x_kkt_lowrank_solve(mi355x_kkt_handle h, int nrhs, double* rhs_inout, int ld);
+int  mi355x_kkt_lowrank_solve_device2(mi355x_kkt_handle h, int nrhs, const double* d_b, int ldb, double* d_x, int ldx);
+int  mi355x_kkt_lowrank_clear(mi355x_kkt_handle h);
+int  mi355x_kkt_lowrank_info(mi355x_kkt_handle h, int* rows, int* nv, int* nu, int* current, double* update_ms);
+
 int  mi355x_kkt_set_pivtol(mi355x_kkt_handle h, double u);
 int  mi355x_kkt_set_pivtolmax(mi355x_kkt_handle h, double umax);
 /* IncreaseQuality (IpSparseSymLinearSolverInterface.hpp:220): raises u <- min(pivtolmax, u^0.75) (the rule of

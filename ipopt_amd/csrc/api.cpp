@@ -380,6 +380,101 @@ int mi355x_kkt_pd_residual(mi355x_kkt_handle h, int rhs, int res, int resid, con
 { PD_CALL("pd_residual", deltas4 && norms3, pd_residual(rhs, res, resid, deltas4, norms3)) }
 #undef PD_CALL
 
+// ---- low-rank update of the factored system (IpLowRankAugSystemSolver.cpp): K + V V^T - U U^T ----
+// Every argument is checked before the device is touched (the checks answer on a machine without one); then the multi-GPU refusal, then the device.
+#define LR_FAIL(msg) do { h->err = std::string(name) + ": " + (msg); return MI355X_KKT_FATAL; } while (0)
+static int lowrank_gate(mi355x_kkt_handle h, const char* name)
+{
+    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
+    if (h->opts.nranks > 1) LR_FAIL("not supported on a multi-GPU handle");
+    return MI355X_KKT_SUCCESS;
+}
+static int lowrank_device(mi355x_kkt_handle h, const char* name)
+{
+    if (!h->numeric_ready) LR_FAIL("no usable HIP device (no CPU fallback)" + (h->setup_err.empty() ? std::string() : ": " + h->setup_err));
+    return MI355X_KKT_SUCCESS;
+}
+int mi355x_kkt_lowrank_set(mi355x_kkt_handle h, int rows, int nv, const double* V, int ldv, int nu, const double* U, int ldu)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "lowrank_set";
+    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
+    if (rows < 0 || rows > h->sym.n) LR_FAIL("rows must be in [0, n]");
+    if (nv < 0 || nv > MI355X_KKT_LOWRANK_MAX) LR_FAIL("nv must be in [0, 32]");
+    if (nu < 0 || nu > MI355X_KKT_LOWRANK_MAX) LR_FAIL("nu must be in [0, 32]");
+    if (nv > 0 && ldv < rows) LR_FAIL("ldv must be >= rows");
+    if (nu > 0 && ldu < rows) LR_FAIL("ldu must be >= rows");
+    if (nv > 0 && rows > 0 && !V) LR_FAIL("V is null with nv > 0");
+    if (nu > 0 && rows > 0 && !U) LR_FAIL("U is null with nu > 0");
+    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
+    try { if (!h->num->lowrank_set(rows, nv, V, ldv, nu, U, ldu)) { h->err = h->num->error(); return MI355X_KKT_FATAL; } return MI355X_KKT_SUCCESS; }
+    catch (...) { h->err = "lowrank_set: unexpected exception"; return MI355X_KKT_FATAL; }
+}
+int mi355x_kkt_lowrank_update(mi355x_kkt_handle h, int* which_failed)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "lowrank_update";
+    if (which_failed) *which_failed = 0;
+    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
+    if (!h->factored) LR_FAIL("no factorisation available");
+    try {
+        int which = 0;
+        if (!h->num->lowrank_update(&which)) { h->err = h->num->error(); return MI355X_KKT_FATAL; }
+        if (which_failed) *which_failed = which;
+        if (which != 0) { h->err = std::string("lowrank_update: ") + (which == 1 ? "M1 = I + V^T K^-1 V" : "M2 = I - U^T (K + V V^T)^-1 U") + " is not positive definite (wrong inertia)"; return MI355X_KKT_WRONG_INERTIA; }
+        return MI355X_KKT_SUCCESS;
+    } catch (...) { h->err = "lowrank_update: unexpected exception"; return MI355X_KKT_FATAL; }
+}
+int mi355x_kkt_lowrank_solve(mi355x_kkt_handle h, int nrhs, double* rhs, int ld)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "lowrank_solve";
+    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
+    if (nrhs < 0) LR_FAIL("nrhs must be >= 0");
+    if (nrhs > 0 && h->sym.n > 0 && !rhs) LR_FAIL("rhs_inout is null with nrhs > 0");
+    if (nrhs > 1 && ld < h->sym.n) LR_FAIL("ld must be >= n");
+    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
+    if (!h->factored) LR_FAIL("no factorisation available");
+    try {
+        if (h->sym.n == 0 || nrhs == 0) return MI355X_KKT_SUCCESS;
+        if (!h->num->lowrank_solve_host(nrhs, rhs, ld)) { h->err = h->num->error(); return MI355X_KKT_FATAL; } return MI355X_KKT_SUCCESS;
+    } catch (...) { h->err = "lowrank_solve: unexpected exception"; return MI355X_KKT_FATAL; }
+}
+int mi355x_kkt_lowrank_solve_device2(mi355x_kkt_handle h, int nrhs, const double* db, int ldb, double* dx, int ldx)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "lowrank_solve_device2";
+    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
+    if (nrhs < 0) LR_FAIL("nrhs must be >= 0");
+    if (nrhs > 0 && h->sym.n > 0 && !db) LR_FAIL("d_b is null with nrhs > 0");
+    if (nrhs > 0 && h->sym.n > 0 && !dx) LR_FAIL("d_x is null with nrhs > 0");
+    if (nrhs > 1 && ldb < h->sym.n) LR_FAIL("ldb must be >= n");
+    if (nrhs > 1 && ldx < h->sym.n) LR_FAIL("ldx must be >= n");
+    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
+    if (!h->factored) LR_FAIL("no factorisation available");
+    try {
+        if (h->sym.n == 0 || nrhs == 0) return MI355X_KKT_SUCCESS;
+        if (!h->num->lowrank_solve_device2(nrhs, db, ldb, dx, ldx)) { h->err = h->num->error(); return MI355X_KKT_FATAL; } return MI355X_KKT_SUCCESS;
+    } catch (...) { h->err = "lowrank_solve_device2: unexpected exception"; return MI355X_KKT_FATAL; }
+}
+int mi355x_kkt_lowrank_clear(mi355x_kkt_handle h)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "lowrank_clear";
+    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
+    try { h->num->lowrank_clear(); return MI355X_KKT_SUCCESS; } catch (...) { h->err = "lowrank_clear: unexpected exception"; return MI355X_KKT_FATAL; }
+}
+int mi355x_kkt_lowrank_info(mi355x_kkt_handle h, int* rows, int* nv, int* nu, int* current, double* update_ms)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "lowrank_info";
+    if (rows) *rows = 0; if (nv) *nv = 0; if (nu) *nu = 0; if (current) *current = 0; if (update_ms) *update_ms = 0.0;
+    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
+    h->num->lowrank_info(rows, nv, nu, current, update_ms);
+    return MI355X_KKT_SUCCESS;
+}
+#undef LR_FAIL
+
 int mi355x_kkt_solve(mi355x_kkt_handle h, int nrhs, double* rhs, int ld)
 {
     if (!h) return MI355X_KKT_FATAL;

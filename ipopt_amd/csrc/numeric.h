@@ -84,6 +84,17 @@ public:
     bool   pd_get(int vec, double* const* blocks8);
     bool   pd_solve_once(int rhs, int res, double alpha, double beta);
     bool   pd_residual(int rhs, int res, int resid, const double* deltas4, double* norms3);
+    // low-rank update K + V V^T - U U^T of the factored system (IpLowRankAugSystemSolver.cpp): V (rows x nv), U (rows x nu), host, column-major, on the
+    // first `rows` indices of the caller's numbering; kept on the device across refactorisations and structure edits.  lowrank_update runs after a
+    // factorisation (*which: 0 in force, 1 / 2 = M1 / M2 not positive definite); the solves refuse an update that is not current (factor_count).
+    // While one is set, pd_solve_once corrects the 4-block solution and pd_residual adds V (V^T res_x) - U (U^T res_x) to the x rows.
+    bool   lowrank_set(int rows, int nv, const double* V, int ldv, int nu, const double* U, int ldu);
+    bool   lowrank_update(int* which);
+    bool   lowrank_solve_host(int nrhs, double* rhs, int ld);
+    bool   lowrank_solve_device2(int nrhs, const double* db, int ldb, double* dx, int ldx);
+    bool   lowrank_clear();
+    void   lowrank_info(int* rows, int* nv, int* nu, int* current, double* update_ms) const;
+    long long factor_count() const;                  // bumped by every factorisation (the refactorisations of a delayed-pivot loop included) and every structure edit
     // communicator of a multi-GPU handle: with one set, factor()/solve_*() run the whole distributed sequence themselves
     bool   set_comm_rccl(const void* unique_id128);                                   // RCCL (dlopen'ed), ncclCommInitRank(nranks, id, rank)
     bool   set_comm_callback(int (*allreduce)(void* ctx, void* dptr, int64_t count, int dtype, void* hip_stream), void* ctx);

@@ -39,6 +39,7 @@
 #include "env_knobs.h"
 #include "matching_scaling.h"
 #include "device_owner.h"      // DeviceOwner, HIPCHK
+#include "lowrank_host.h"      // the host Cholesky of the low-rank update
 
 namespace mi355x {
 
@@ -67,6 +68,7 @@ static constexpr double ZERO_REL = 1e-14;                // zero-pivot test rela
 #include "kernels_big.hip.inc"
 #include "kernels_pd_multigpu.hip.inc"
 #include "kernels_match.hip.inc"
+#include "kernels_lowrank.hip.inc"
 // ------------------------------------------------------------------------------------------------
 // host-side orchestration
 // ------------------------------------------------------------------------------------------------
@@ -97,6 +99,7 @@ public:
     DeviceOwner own_match{err_};       // until any release() or a change of size: the buffers and events of the matching on the device
     DeviceOwner own_asm{err_};         // until assembly_define or release(false): the assembly sources and their staging
     DeviceOwner own_pd{err_};          // until pd_define or release(false): the primal-dual workspace
+    DeviceOwner own_lr{err_};          // until lowrank_set / lowrank_clear or release(false): the low-rank update (caller's numbering: survives a restructure, like own_pd)
     DevView V{};
     int* d_stats = nullptr;
     double* d_rhs = nullptr; size_t d_rhs_cap = 0;
@@ -459,6 +462,7 @@ public:
             own_pool.clear(); kept_pool = nullptr; kept_pool_doubles = 0;
             own_asm.clear(); asm_.nseg = 0;
             own_pd.clear(); pd_ready = false;
+            own_lr.clear(); lr_set = lr_ok = false;
             own_handle.clear(); h_vals = nullptr; h_stats = nullptr; ev0 = ev1 = nullptr; V.tvals = nullptr; d_user_scale = nullptr; prof_ev.clear(); prof_used = 0; prof_kind.clear();
             if (stream3) { (void)hipStreamDestroy(stream3); stream3 = nullptr; }
             if (stream2) { (void)hipStreamDestroy(stream2); stream2 = nullptr; }
@@ -478,6 +482,7 @@ public:
         const bool hv = have_values;
         if (!setup(Sy, o, true)) return false;
         have_values = hv;
+        ++factor_count;      // (whatever was derived from the factorisation before the edit is stale)
         return true;
     }
     bool setup(const Symbolic& Sy, const NumericOptions& o, bool keep = false) {
@@ -914,6 +919,7 @@ public:
         if (!ready) { if (err_.empty()) err_ = "factor: solver not set up (no device?)"; return false; }
         if (!from_assembly) { asm_dirty = true; scale_valid = false; }      // other values than the assembled ones are equilibrated now: the next factor_assembled starts afresh
         if (multi) return factor_dist(dvals, reuse, st);          // needs a communicator (set_comm_*), fails loudly otherwise
+        ++factor_count;                                           // (bumped before the work: a failed factorisation leaves nothing current either)
         static const bool opt_off = knob_disabled("optimistic");
         if (!optimistic_ok && opt_wait > 0 && --opt_wait == 0) optimistic_ok = true;   // (one rejection early in an Ipopt run must not cost the optimistic schedule for the life of the structure)
         optimistic = V.fastpiv && !opt_off && !prof_on && optimistic_ok;
@@ -1335,11 +1341,13 @@ public:
     bool pd_solve_once(int rhs, int res, double alpha, double beta) {
         DeviceGuard guard(dev);
         if (!pd_ready || rhs < 0 || rhs >= PD_NVEC || res < 0 || res >= PD_NVEC) { err_ = "pd_solve_once: pd_define first / no such vector"; return false; }
+        if (lr_set && (!lr_fits_x("pd_solve_once") || !lr_require_current("pd_solve_once"))) return false;
         const int g4 = grid1d(pd_dim4), gb = grid1d(std::max(std::max(pd_.nxl, pd_.nxu), std::max(pd_.nsl, pd_.nsu)));
         hipLaunchKernelGGL(k_pd_reduce, dim3(g4), dim3(256), 0, stream, pd_, (const double*)pd_vec[rhs], pd_aug, 0);
         hipLaunchKernelGGL(k_pd_reduce, dim3(gb), dim3(256), 0, stream, pd_, (const double*)pd_vec[rhs], pd_aug, 1);
         hipLaunchKernelGGL(k_pd_reduce, dim3(gb), dim3(256), 0, stream, pd_, (const double*)pd_vec[rhs], pd_aug, 2);
         if (!solve_device(1, pd_aug, pd_dim4, pd_aug, pd_dim4, false)) return false;
+        if (lr_set && !lr_correct(pd_aug, pd_dim4, 1)) return false;      // W carries B0 only: the Sherman-Morrison correction of the 4-block solution
         hipLaunchKernelGGL(k_pd_expand, dim3(g4), dim3(256), 0, stream, pd_, (const double*)pd_vec[rhs], (const double*)pd_aug, pd_vec[res], alpha, beta);
         HIPCHK(hipGetLastError());
         return true;
@@ -1348,9 +1356,11 @@ public:
     bool pd_residual(int rhs, int res, int resid, const double* deltas, double* norms) {
         DeviceGuard guard(dev);
         if (!pd_ready || rhs < 0 || rhs >= PD_NVEC || res < 0 || res >= PD_NVEC || resid < 0 || resid >= PD_NVEC) { err_ = "pd_residual: pd_define first / no such vector"; return false; }
+        if (lr_set && !lr_fits_x("pd_residual")) return false;
         const int g4 = grid1d(pd_dim4), gb = grid1d(std::max(std::max(pd_.nxl, pd_.nxu), std::max(pd_.nsl, pd_.nsu)));
         hipLaunchKernelGGL(k_zero_u64, dim3(1), dim3(64), 0, stream, pd_norms_d, 4);
         hipLaunchKernelGGL(k_pd_resid_rows, dim3(g4), dim3(256), 0, stream, pd_, (const double*)pd_vec[rhs], (const double*)pd_vec[res], pd_vec[resid], deltas[0], deltas[1], deltas[2], deltas[3]);
+        if (lr_set && !lr_residual(pd_vec[res], pd_vec[resid])) return false;      // x rows += V (V^T res_x) - U (U^T res_x)
         hipLaunchKernelGGL(k_pd_resid_bounds, dim3(gb), dim3(256), 0, stream, pd_, (const double*)pd_vec[rhs], (const double*)pd_vec[res], pd_vec[resid], 1);
         hipLaunchKernelGGL(k_pd_resid_bounds, dim3(gb), dim3(256), 0, stream, pd_, (const double*)pd_vec[rhs], (const double*)pd_vec[res], pd_vec[resid], 2);
         hipLaunchKernelGGL(k_pd_norms, dim3(grid1d(pd_len8)), dim3(256), 0, stream, pd_, (const double*)pd_vec[rhs], (const double*)pd_vec[res], (const double*)pd_vec[resid], pd_len8);
@@ -1358,6 +1368,177 @@ public:
         HIPCHK(hipStreamSynchronize(stream));
         for (int q = 0; q < 3; ++q) { double v; std::memcpy(&v, &pd_norms_h[q], sizeof v); norms[q] = v; }
         return true;
+    }
+
+    // ---------------- low-rank update of the factored system: K~ = K + V V^T - U U^T (IpLowRankAugSystemSolver.cpp) ----------------
+    // V (rows x nv) and U (rows x nu) act on the first `rows` indices of the CALLER's numbering and stay on the device until lowrank_set /
+    // lowrank_clear; lowrank_update forms, through the CURRENT factorisation,
+    //   Z1 = K^-1 V,  M1 = I + sym(V^T Z1),  W1 = K^-1 U,  C = M1^-1 (Z1^T U),  Z2 = W1 - Z1 C,  M2 = I - sym(U^T Z2)          (:299-396)
+    // and a solve corrects x0 = K^-1 b in place:  x1 = x0 - Z1 M1^-1 (V^T x0),  x = x1 + Z2 M2^-1 (U^T x1)                       (:195-228, from the
+    // running solution instead of the right-hand side).  M1, M2 positive definite <=> K~ has K's inertia.  The update is CURRENT while
+    // factor_count -- bumped by every factorisation and every structure edit -- is the one lowrank_update saw.
+    long long factor_count = 0;
+    bool lr_set = false, lr_ok = false; long long lr_at = -1;
+    int lr_rows = 0, lr_nv = 0, lr_nu = 0; double lr_update_ms = 0;
+    double *lr_V = nullptr, *lr_U = nullptr, *lr_Z1 = nullptr, *lr_Z2 = nullptr, *lr_part = nullptr, *lr_T = nullptr, *lr_L1 = nullptr, *lr_L2 = nullptr, *lr_h = nullptr;
+    int lr_nslab() const { return std::max(1, (lr_rows + LR_SLAB - 1) / LR_SLAB); }
+    bool lr_current() const { return lr_set && lr_ok && lr_at == factor_count; }
+    bool lr_require_current(const char* who) {
+        if (lr_current()) return true;
+        err_ = std::string(who) + (!lr_set ? ": no low-rank update set (lowrank_set, then lowrank_update)"
+                                   : ": the low-rank update is not current for the factorisation in the handle (call lowrank_update; it must succeed)");
+        return false;
+    }
+    bool lr_fits_x(const char* who) {
+        if (lr_rows <= pd_.nx) return true;
+        err_ = std::string(who) + ": the low-rank update acts on more rows than the x block has (rows <= n_x)"; return false;
+    }
+    void lowrank_clear() { own_lr.clear(); lr_set = lr_ok = false; lr_at = -1; lr_rows = lr_nv = lr_nu = 0; lr_update_ms = 0; lr_V = lr_U = lr_Z1 = lr_Z2 = lr_part = lr_T = lr_L1 = lr_L2 = lr_h = nullptr; }
+    bool lowrank_set(int rows, int nv, const double* Vh, int ldv, int nu, const double* Uh, int ldu) {
+        DeviceGuard guard(dev);
+        if (!ready) { if (err_.empty()) err_ = "lowrank_set: solver not set up"; return false; }
+        if (multi) { err_ = "lowrank_set: not supported on a multi-GPU handle"; return false; }
+        HIPCHK(hipStreamSynchronize(stream));      // (a correction still in flight reads the buffers about to be freed)
+        lowrank_clear();
+        const size_t n = S->n;
+        lr_rows = rows; lr_nv = nv; lr_nu = nu;
+        DeviceOwner& O = own_lr;
+        if (!O.raw(&lr_V, (size_t)rows * nv) || !O.raw(&lr_U, (size_t)rows * nu) || !O.raw(&lr_Z1, n * nv) || !O.raw(&lr_Z2, n * nu) ||
+            !O.raw(&lr_part, (size_t)lr_nslab() * LR_MAX * LR_MAX) || !O.raw(&lr_T, LR_MAX * LR_MAX) || !O.raw(&lr_L1, LR_MAX * LR_MAX) || !O.raw(&lr_L2, LR_MAX * LR_MAX) ||
+            !O.pinned(&lr_h, LR_MAX * LR_MAX)) { lowrank_clear(); return false; }
+        if (rows > 0 && nv > 0) HIPCHK(hipMemcpy2D(lr_V, (size_t)rows * sizeof(double), Vh, (size_t)ldv * sizeof(double), (size_t)rows * sizeof(double), nv, hipMemcpyHostToDevice));
+        if (rows > 0 && nu > 0) HIPCHK(hipMemcpy2D(lr_U, (size_t)rows * sizeof(double), Uh, (size_t)ldu * sizeof(double), (size_t)rows * sizeof(double), nu, hipMemcpyHostToDevice));
+        lr_set = true;
+        return true;
+    }
+    // G = A^T B over the first lr_rows rows: gy = 1: one p x q block; gy > 1 (q = 1): gy separate columns of B.  Partials into lr_part.
+    void lr_gram(const double* A, long long lda, const double* B, long long ldb, int p, int q, int gy) {
+        hipLaunchKernelGGL(k_lr_gram, dim3(lr_nslab(), gy), dim3(256), 0, stream, A, lda, B, ldb, lr_rows, p, q, lr_part);
+    }
+    // the p x q Gram A^T B, summed on the device, into the pinned lr_h (synchronises)
+    bool lr_gram_host(const double* A, long long lda, const double* B, long long ldb, int p, int q) {
+        lr_gram(A, lda, B, ldb, p, q, 1);
+        hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lr_part, lr_nslab(), (long long)p, (long long)p * q, p, q, (const double*)nullptr, lr_T);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(lr_h, lr_T, (size_t)p * q * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        return true;
+    }
+    // Z (n x p) <- the columns of A (lr_rows x p) padded with zero rows, on the solver's stream
+    bool lr_pad(double* Z, const double* A, int p) {
+        const size_t n = S->n;
+        HIPCHK(hipMemsetAsync(Z, 0, n * (size_t)p * sizeof(double), stream));
+        if (lr_rows > 0) HIPCHK(hipMemcpy2DAsync(Z, n * sizeof(double), A, (size_t)lr_rows * sizeof(double), (size_t)lr_rows * sizeof(double), p, hipMemcpyDeviceToDevice, stream));
+        return true;
+    }
+    // which: 0 = the update is in force, 1 / 2 = M1 / M2 is not positive definite (K~ has not K's inertia); false: an error
+    bool lowrank_update(int* which) {
+        DeviceGuard guard(dev);
+        *which = 0;
+        if (!ready) { if (err_.empty()) err_ = "lowrank_update: solver not set up"; return false; }
+        if (!lr_set) { err_ = "lowrank_update: lowrank_set first"; return false; }
+        lr_ok = false;
+        const auto t0 = std::chrono::steady_clock::now();
+        const int n = S->n, nv = lr_nv, nu = lr_nu;
+        double M[LR_MAX * LR_MAX], Cm[LR_MAX * LR_MAX];
+        // The inner solves are the existing nrhs > 1 path.  With several solve contexts their columns run on the contexts' streams; solve_device makes
+        // the solver's stream wait for every context's `done` event before it returns, and -- timed -- synchronises: what follows here on `stream`
+        // (Gram, apply) is ordered behind all columns.
+        if (n > 0 && nv > 0) {
+            if (!lr_pad(lr_Z1, lr_V, nv) || !solve_device(nv, lr_Z1, n, lr_Z1, n, true)) return false;
+            if (!lr_gram_host(lr_V, lr_rows, lr_Z1, n, nv, nv)) return false;
+            lr_shifted_sym(lr_h, nv, 1.0, M);
+            if (!lr_cholesky(M, nv)) { *which = 1; return true; }
+            HIPCHK(hipMemcpyAsync(lr_L1, M, (size_t)nv * nv * sizeof(double), hipMemcpyHostToDevice, stream));
+            HIPCHK(hipStreamSynchronize(stream));      // (M is pageable and is written again below)
+        }
+        if (n > 0 && nu > 0) {
+            if (!lr_pad(lr_Z2, lr_U, nu) || !solve_device(nu, lr_Z2, n, lr_Z2, n, true)) return false;      // W1
+            if (nv > 0) {
+                if (!lr_gram_host(lr_Z1, n, lr_U, lr_rows, nv, nu)) return false;                          // Z1^T U
+                for (int e = 0; e < nv * nu; ++e) Cm[e] = lr_h[e];
+                lr_cholesky_solve(M, nv, Cm, nu);                                                           // C = M1^-1 (Z1^T U)
+                HIPCHK(hipMemcpyAsync(lr_T, Cm, (size_t)nv * nu * sizeof(double), hipMemcpyHostToDevice, stream));
+                hipLaunchKernelGGL(k_lr_apply, dim3((n + 255) / 256), dim3(256), 0, stream, lr_Z2, (long long)n, (const double*)lr_Z1, (long long)n, (const double*)lr_T, (long long)n, nv, nu, -1.0);      // Z2 = W1 - Z1 C
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipStreamSynchronize(stream));  // (Cm is pageable; lr_T is written again by the next Gram)
+            }
+            if (!lr_gram_host(lr_U, lr_rows, lr_Z2, n, nu, nu)) return false;
+            lr_shifted_sym(lr_h, nu, -1.0, M);
+            if (!lr_cholesky(M, nu)) { *which = 2; return true; }
+            HIPCHK(hipMemcpyAsync(lr_L2, M, (size_t)nu * nu * sizeof(double), hipMemcpyHostToDevice, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+        }
+        lr_ok = true; lr_at = factor_count;
+        lr_update_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return true;
+    }
+    // the two corrections of nrhs solution columns X (leading dimension ldx), enqueued on the solver's stream: three launches per half, no host round trip
+    bool lr_correct(double* X, long long ldx, int nrhs) {
+        const long long n = S->n;
+        const int nslab = lr_nslab(), ga = (int)((n + 255) / 256);
+        if (n == 0) return true;
+        for (int c0 = 0; c0 < nrhs; c0 += LR_MAX) {
+            const int nc = std::min(LR_MAX, nrhs - c0);
+            double* Xc = X + (long long)c0 * ldx;
+            if (lr_nv > 0) {
+                lr_gram(lr_V, lr_rows, Xc, ldx, lr_nv, 1, nc);
+                hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lr_part, nslab, (long long)nslab * lr_nv, (long long)lr_nv, lr_nv, nc, (const double*)lr_L1, lr_T);
+                hipLaunchKernelGGL(k_lr_apply, dim3(ga), dim3(256), 0, stream, Xc, ldx, (const double*)lr_Z1, n, (const double*)lr_T, n, lr_nv, nc, -1.0);
+            }
+            if (lr_nu > 0) {
+                lr_gram(lr_U, lr_rows, Xc, ldx, lr_nu, 1, nc);
+                hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lr_part, nslab, (long long)nslab * lr_nu, (long long)lr_nu, lr_nu, nc, (const double*)lr_L2, lr_T);
+                hipLaunchKernelGGL(k_lr_apply, dim3(ga), dim3(256), 0, stream, Xc, ldx, (const double*)lr_Z2, n, (const double*)lr_T, n, lr_nu, nc, 1.0);
+            }
+        }
+        HIPCHK(hipGetLastError());
+        return true;
+    }
+    // resid[0:rows] += V (V^T res[0:rows]) - U (U^T res[0:rows])   (the x rows of the unreduced residual; W holds B0 only)
+    bool lr_residual(const double* res, double* resid) {
+        if (lr_rows == 0) return true;
+        const int ga = (lr_rows + 255) / 256;
+        for (int half = 0; half < 2; ++half) {
+            const int p = half == 0 ? lr_nv : lr_nu; const double* A = half == 0 ? lr_V : lr_U;
+            if (p == 0) continue;
+            lr_gram(A, lr_rows, res, lr_rows, p, 1, 1);
+            hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lr_part, lr_nslab(), (long long)lr_nslab() * p, (long long)p, p, 1, (const double*)nullptr, lr_T);
+            hipLaunchKernelGGL(k_lr_apply, dim3(ga), dim3(256), 0, stream, resid, (long long)lr_rows, A, (long long)lr_rows, (const double*)lr_T, (long long)lr_rows, p, 1, half == 0 ? 1.0 : -1.0);
+        }
+        HIPCHK(hipGetLastError());
+        return true;
+    }
+    bool lowrank_solve_device2(int nrhs, const double* db, int ldb, double* dx, int ldx) {
+        {
+            DeviceGuard guard(dev);
+            if (!ready) { if (err_.empty()) err_ = "lowrank_solve: solver not set up"; return false; }
+            if (!lr_require_current("lowrank_solve")) return false;
+        }
+        if (!solve_device(nrhs, db, ldb, dx, ldx, true)) return false;
+        DeviceGuard guard(dev);
+        if (!lr_correct(dx, ldx, nrhs)) return false;
+        HIPCHK(hipStreamSynchronize(stream));
+        return true;
+    }
+    bool lowrank_solve_host(int nrhs, double* rhs, int ld) {      // solve_host with the corrections between the plain solve and the download
+        DeviceGuard guard(dev);
+        if (!ready) { if (err_.empty()) err_ = "lowrank_solve: solver not set up"; return false; }
+        if (!lr_require_current("lowrank_solve")) return false;
+        const size_t n = S->n;
+        if (!ensure_rhs(n * (size_t)std::max(nrhs, 1))) return false;
+        if ((size_t)ld == n || nrhs == 1) HIPCHK(hipMemcpyAsync(d_rhs, rhs, n * (size_t)nrhs * sizeof(double), hipMemcpyHostToDevice, stream));
+        else for (int r = 0; r < nrhs; ++r) HIPCHK(hipMemcpyAsync(d_rhs + (size_t)r * n, rhs + (size_t)r * ld, n * sizeof(double), hipMemcpyHostToDevice, stream));
+        if (!solve_device(nrhs, d_rhs, (int)n, d_rhs, (int)n, true)) return false;
+        if (!lr_correct(d_rhs, (long long)n, nrhs)) return false;
+        if ((size_t)ld == n || nrhs == 1) HIPCHK(hipMemcpyAsync(rhs, d_rhs, n * (size_t)nrhs * sizeof(double), hipMemcpyDeviceToHost, stream));
+        else for (int r = 0; r < nrhs; ++r) HIPCHK(hipMemcpyAsync(rhs + (size_t)r * ld, d_rhs + (size_t)r * n, n * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        return true;
+    }
+    void lowrank_info(int* rows, int* nv, int* nu, int* current, double* update_ms) const {
+        if (rows) *rows = lr_set ? lr_rows : 0; if (nv) *nv = lr_set ? lr_nv : 0; if (nu) *nu = lr_set ? lr_nu : 0;
+        if (current) *current = lr_current() ? 1 : 0; if (update_ms) *update_ms = lr_set ? lr_update_ms : 0.0;
     }
 
     // ---------------- multi-GPU orchestration (eager launches) ----------------
@@ -1656,6 +1837,13 @@ bool Numeric::pd_put(int vec, const double* const* blocks) { return p_->pd_put(v
 bool Numeric::pd_get(int vec, double* const* blocks) { return p_->pd_get(vec, blocks); }
 bool Numeric::pd_solve_once(int rhs, int res, double alpha, double beta) { return p_->pd_solve_once(rhs, res, alpha, beta); }
 bool Numeric::pd_residual(int rhs, int res, int resid, const double* deltas, double* norms) { return p_->pd_residual(rhs, res, resid, deltas, norms); }
+bool Numeric::lowrank_set(int rows, int nv, const double* V, int ldv, int nu, const double* U, int ldu) { return p_->lowrank_set(rows, nv, V, ldv, nu, U, ldu); }
+bool Numeric::lowrank_update(int* which) { return p_->lowrank_update(which); }
+bool Numeric::lowrank_solve_host(int nrhs, double* rhs, int ld) { return p_->lowrank_solve_host(nrhs, rhs, ld); }
+bool Numeric::lowrank_solve_device2(int nrhs, const double* db, int ldb, double* dx, int ldx) { return p_->lowrank_solve_device2(nrhs, db, ldb, dx, ldx); }
+bool Numeric::lowrank_clear() { DeviceGuard guard(p_->dev); if (p_->stream) (void)hipStreamSynchronize(p_->stream); p_->lowrank_clear(); return true; }
+void Numeric::lowrank_info(int* rows, int* nv, int* nu, int* current, double* update_ms) const { p_->lowrank_info(rows, nv, nu, current, update_ms); }
+long long Numeric::factor_count() const { return p_->factor_count; }
 bool Numeric::ruiz_triplet(int device, int n, int nnz, const int* irn, const int* jcn, const double* a, int base, int sweeps, double* out, std::string& err)
 {
     int ndev = 0;

@@ -73,7 +73,9 @@ ABI_SYMBOLS = [
     "mi355x_kkt_comm_unique_id", "mi355x_kkt_set_comm_rccl", "mi355x_kkt_comm_shm_id", "mi355x_kkt_comm_shm_discard", "mi355x_kkt_set_comm_shm", "mi355x_kkt_set_comm_callbacks", "mi355x_kkt_set_comm_range_callback", "mi355x_kkt_exchange_bytes", "mi355x_kkt_comm_plan", "mi355x_kkt_comm_info",
     "mi355x_kkt_set_scaling", "mi355x_kkt_get_scaling", "mi355x_kkt_ruiz_scaling", "mi355x_kkt_matching_scaling", "mi355x_kkt_zero_pivots", "mi355x_kkt_failed_pivots", "mi355x_kkt_delay_columns", "mi355x_kkt_set_delay_rounds", "mi355x_kkt_assembly_define", "mi355x_kkt_assembly_buffer", "mi355x_kkt_assembly_upload", "mi355x_kkt_factor_assembled",
     "mi355x_kkt_pd_define", "mi355x_kkt_pd_put_data", "mi355x_kkt_pd_put", "mi355x_kkt_pd_get", "mi355x_kkt_pd_solve_once", "mi355x_kkt_pd_residual",
+    "mi355x_kkt_lowrank_set", "mi355x_kkt_lowrank_update", "mi355x_kkt_lowrank_solve", "mi355x_kkt_lowrank_solve_device2", "mi355x_kkt_lowrank_clear", "mi355x_kkt_lowrank_info",
 ]
+LOWRANK_MAX = 32
 KERNEL_KINDS = ["gather_scale", "front_wave", "front_lds64", "front_lds128", "big_assemble", "big_diag", "big_trsm", "big_schur",
                 "stats", "solve_perm", "fwd_wave", "fwd_lds", "fwd_big", "bwd_wave", "bwd_lds", "bwd_big", "fwd_big_upd", "bwd_big_dot"]
 
@@ -138,6 +140,12 @@ def load_library():
     lib.mi355x_kkt_pd_get.argtypes = [vp, C.c_int, vp]
     lib.mi355x_kkt_pd_solve_once.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double]
     lib.mi355x_kkt_pd_residual.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.mi355x_kkt_lowrank_set.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int]
+    lib.mi355x_kkt_lowrank_update.argtypes = [vp, ip]
+    lib.mi355x_kkt_lowrank_solve.argtypes = [vp, C.c_int, vp, C.c_int]
+    lib.mi355x_kkt_lowrank_solve_device2.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int]
+    lib.mi355x_kkt_lowrank_clear.argtypes = [vp]
+    lib.mi355x_kkt_lowrank_info.argtypes = [vp, ip, ip, ip, ip, dp]
     lib.mi355x_kkt_set_comm_rccl.argtypes = [vp, vp]
     lib.mi355x_kkt_comm_shm_id.argtypes = [vp, C.c_int]
     lib.mi355x_kkt_set_comm_shm.argtypes = [vp, vp]
@@ -316,6 +324,57 @@ class KKTSolver:
         if self.lib.mi355x_kkt_pd_residual(self._h, int(rhs), int(res), int(resid), d.ctypes.data, nr.ctypes.data) != 0:
             raise KKTError("pd_residual: " + self.last_error())
         return nr
+
+    # --- low-rank update of the factored system, K + V V^T - U U^T (include/mi355x_kkt.h; reference IpLowRankAugSystemSolver.cpp) ---
+    def lowrank_set(self, V, U, rows=None):
+        """V (rows x nv) and U (rows x nu), numpy, acting on the first `rows` indices; None or zero columns = that half is absent"""
+        def prep(A):
+            if A is None:
+                return None
+            A = np.asarray(A, dtype=np.float64)
+            return np.asfortranarray(A.reshape(-1, 1) if A.ndim == 1 else A)
+        Vf, Uf = prep(V), prep(U)
+        if rows is None:
+            rows = Vf.shape[0] if Vf is not None else (Uf.shape[0] if Uf is not None else 0)
+        for A in (Vf, Uf):
+            if A is not None and A.shape[0] != rows:
+                raise KKTError("lowrank_set: V and U must have `rows` rows")
+        nv = 0 if Vf is None else Vf.shape[1]; nu = 0 if Uf is None else Uf.shape[1]
+        st = self.lib.mi355x_kkt_lowrank_set(self._h, int(rows), nv, Vf.ctypes.data if nv and rows else None, max(int(rows), 1),
+                                             nu, Uf.ctypes.data if nu and rows else None, max(int(rows), 1))
+        if st != 0:
+            raise KKTError("lowrank_set: " + self.last_error())
+
+    def lowrank_update(self):
+        """after a factorisation: (status, which) -- (SUCCESS, 0), or (WRONG_INERTIA, 1 | 2) when M1 | M2 is not positive definite"""
+        which = C.c_int(0)
+        st = self.lib.mi355x_kkt_lowrank_update(self._h, C.byref(which))
+        if st == FATAL:
+            raise KKTError("lowrank_update: " + self.last_error())
+        return st, which.value
+
+    def lowrank_solve(self, rhs: np.ndarray):
+        """in place, like multi_solve's right-hand side: one vector of n, or (nrhs, n) C-contiguous"""
+        assert rhs.dtype == np.float64 and rhs.flags.c_contiguous
+        nrhs = 1 if rhs.ndim == 1 else rhs.shape[0]
+        if self.lib.mi355x_kkt_lowrank_solve(self._h, nrhs, rhs.ctypes.data, self._n) != 0:
+            raise KKTError("lowrank_solve: " + self.last_error())
+
+    def lowrank_solve_device2(self, db_ptr: int, dx_ptr: int, nrhs=1, ldb=None, ldx=None):
+        st = self.lib.mi355x_kkt_lowrank_solve_device2(self._h, nrhs, C.c_void_p(db_ptr), self._n if ldb is None else int(ldb),
+                                                       C.c_void_p(dx_ptr), self._n if ldx is None else int(ldx))
+        if st != 0:
+            raise KKTError("lowrank_solve_device2: " + self.last_error())
+
+    def lowrank_clear(self):
+        if self.lib.mi355x_kkt_lowrank_clear(self._h) != 0:
+            raise KKTError("lowrank_clear: " + self.last_error())
+
+    def lowrank_info(self) -> dict:
+        r, v, u, c, ms = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_double(0.0)
+        if self.lib.mi355x_kkt_lowrank_info(self._h, C.byref(r), C.byref(v), C.byref(u), C.byref(c), C.byref(ms)) != 0:
+            raise KKTError("lowrank_info: " + self.last_error())
+        return {"rows": r.value, "nv": v.value, "nu": u.value, "current": bool(c.value), "update_ms": ms.value}
 
     # --- multi-GPU communicator (include/mi355x_kkt.h): after one of these, multi_solve / factor_device / solve_device* of a
     #     handle created with nranks > 1 run the distributed sequence inside the library ---
