@@ -235,6 +235,46 @@ int  mi355x_kkt_lowrank_solve_device2(mi355x_kkt_handle h, int nrhs, const doubl
 int  mi355x_kkt_lowrank_clear(mi355x_kkt_handle h);
 int  mi355x_kkt_lowrank_info(mi355x_kkt_handle h, int* rows, int* nv, int* nu, int* current, double* update_ms);
 
+/* ---- limited-memory BFGS: the (s, y) history on the device, V and U formed there -------------------------------------------------------------
+ * What the reference's LimMemQuasiNewtonUpdater does for `hessian_approximation limited-memory` with the BFGS update "with skipping" (its default),
+ * IpLimMemQuasiNewtonUpdater.cpp -- with the tall products on the device instead of host MultiVectorMatrix products over the whole history: an
+ * accepted step moves TWO vectors (s, y) to the device, V and U never exist in host memory.  History S = [s_1 .. s_k], Y = [y_1 .. y_k], oldest
+ * first, k <= max_history, `rows` entries each (the first `rows` indices of the caller's numbering, as for _lowrank_set).
+ *   skip    (CheckSkippingBFGS :985-1019)  s^T y <= sqrt(eps) |s|_2 |y|_2: nothing changes.  A non-finite s^T s, s^T y or y^T y is a skip too (a
+ *           stated deviation: the reference never sees one).
+ *   store   (UpdateInternalData :769-818)  append the pair, or drop the oldest when the history is full; D = diag(s_i^T y_i), L (strictly lower,
+ *           L_ij = s_i^T y_j, i > j) and S^T S follow by "augment" / "shift": only the new row and column are computed.
+ *   sigma   (:405-432)  from the new pair: init 0 scalar1 s^T y / s^T s, 1 scalar2 y^T y / s^T y, 2 scalar3 their arithmetic, 3 scalar4 their
+ *           geometric mean, 4 constant init_val; then clipped to [sigma_min, sigma_max].  Reference defaults: 0, 1, 1e-8, 1e8.  Before the first
+ *           stored pair sigma = init_val.
+ *   columns (:440-520)  V = Y D^(-1/2),  Lt = L D^(-1/2),  M = Lt Lt^T + sigma S^T S,  J = chol(M),  C = J^(-T),  Lbar = Lt^T C,
+ *           U = sigma S C + V Lbar:  sigma I + V V^T - U U^T  is the BFGS matrix of the stored pairs started from sigma I.
+ *   M not positive definite (:484-495)  the pair and sigma stay stored, the installed V, U stay what they were.
+ * _lbfgs_push (host vectors of `rows`) / _lbfgs_push_device (device vectors, complete before the call; free again when it returns), *outcome (may be NULL):
+ *   0  pair stored, V and U formed and INSTALLED as the handle's low-rank update, exactly as _lowrank_set(rows, memory, V, rows, memory, U, rows)
+ *      would: the update is not current; the caller factors with sigma on the x diagonal and calls _lowrank_update
+ *   1  skipped, nothing changed (an update that was current stays current)
+ *   2  pair stored and sigma updated; M was not positive definite, the installed columns are unchanged
+ * A push allocates no device memory while the installed shape (rows, nv, nu) stays the same (a full history).  The history survives
+ * refactorisations and delayed-pivot structure edits; _lowrank_set / _lowrank_clear replace / remove the installed columns and leave it alone.
+ *   _lbfgs_reset  forgets the pairs, sigma = init_val, removes the installed update;   _lbfgs_clear  undefines: frees the history
+ *   _lbfgs_info   outputs may be NULL; skipped_in_a_row: pushes skipped since the last stored pair (the caller's reset policy reads it); push_ms:
+ *                 host ms of the last push
+ *   _lbfgs_get    what: 0 S, 1 Y (rows x memory, oldest first, column-major, ld = rows), 2 V, 3 U (the installed columns, ld = rows),
+ *                 4 D (memory), 5 L, 6 S^T S (memory x memory, column-major); FATAL when `capacity` (doubles) is too small
+ *   _lbfgs_coefficients  stand-alone, HOST, no handle, no GPU: C and Lbar (m x m, column-major) from S^T S, L, D (m x m, m x m, m) and sigma;
+ *                 SUCCESS, SINGULAR (a D_j or a Cholesky pivot <= 0 or not finite), FATAL (m outside [0, 32] or a null array)
+ * Arguments are checked before the device is touched; single-GPU handles only (nranks > 1: FATAL). */
+#define MI355X_KKT_LBFGS_MAX 32                         /* = MI355X_KKT_LOWRANK_MAX: V and U have one column per stored pair */
+int  mi355x_kkt_lbfgs_define(mi355x_kkt_handle h, int rows, int max_history, int init, double init_val, double sigma_min, double sigma_max);
+int  mi355x_kkt_lbfgs_push(mi355x_kkt_handle h, const double* s, const double* y, int* outcome);
+int  mi355x_kkt_lbfgs_push_device(mi355x_kkt_handle h, const double* d_s, const double* d_y, int* outcome);
+int  mi355x_kkt_lbfgs_reset(mi355x_kkt_handle h);
+int  mi355x_kkt_lbfgs_clear(mi355x_kkt_handle h);
+int  mi355x_kkt_lbfgs_info(mi355x_kkt_handle h, int* rows, int* max_history, int* memory, double* sigma, int* skipped_in_a_row, double* push_ms);
+int  mi355x_kkt_lbfgs_get(mi355x_kkt_handle h, int what, double* out, int64_t capacity);
+int  mi355x_kkt_lbfgs_coefficients(int m, const double* sts, const double* L, const double* D, double sigma, double* C_out, double* Lbar_out);
+
 int  mi355x_kkt_set_pivtol(mi355x_kkt_handle h, double u);
 int  mi355x_kkt_set_pivtolmax(mi355x_kkt_handle h, double umax);
 /* IncreaseQuality (IpSparseSymLinearSolverInterface.hpp:220): raises u <- min(pivtolmax, u^0.75) (the rule of

@@ -7,6 +7,7 @@
 #include "matching_scaling.h"
 #include "comm_shm.h"
 #include "env_knobs.h"
+#include "lbfgs_host.h"      // the small algebra of an L-BFGS push: mi355x_kkt_lbfgs_coefficients is this header alone
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -472,6 +473,82 @@ int mi355x_kkt_lowrank_info(mi355x_kkt_handle h, int* rows, int* nv, int* nu, in
     if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
     h->num->lowrank_info(rows, nv, nu, current, update_ms);
     return MI355X_KKT_SUCCESS;
+}
+// ---- limited-memory BFGS on the device (IpLimMemQuasiNewtonUpdater.cpp): the (s, y) history, V and U formed there and installed as the low-rank update ----
+// The same order as above: every argument, then the multi-GPU refusal, then the device.
+int mi355x_kkt_lbfgs_define(mi355x_kkt_handle h, int rows, int max_history, int init, double init_val, double sigma_min, double sigma_max)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "lbfgs_define";
+    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
+    if (rows < 1 || rows > h->sym.n) LR_FAIL("rows must be in [1, n]");
+    if (max_history < 1 || max_history > MI355X_KKT_LBFGS_MAX) LR_FAIL("max_history must be in [1, 32]");
+    if (init < 0 || init > 4) LR_FAIL("init must be in [0, 4] (scalar1..4, constant)");
+    if (!(init_val > 0.0) || !std::isfinite(init_val)) LR_FAIL("init_val must be positive and finite");
+    if (!(sigma_min > 0.0) || !std::isfinite(sigma_min)) LR_FAIL("sigma_min must be positive and finite");
+    if (!(sigma_max >= sigma_min) || !std::isfinite(sigma_max)) LR_FAIL("sigma_max must be finite and >= sigma_min");
+    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
+    try { if (!h->num->lbfgs_define(rows, max_history, init, init_val, sigma_min, sigma_max)) { h->err = h->num->error(); return MI355X_KKT_FATAL; } return MI355X_KKT_SUCCESS; }
+    catch (...) { h->err = "lbfgs_define: unexpected exception"; return MI355X_KKT_FATAL; }
+}
+static int lbfgs_push_any(mi355x_kkt_handle h, const char* name, const double* s, const double* y, bool device, int* outcome)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    if (outcome) *outcome = 1;
+    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
+    if (!s) LR_FAIL(device ? "d_s is null" : "s is null");
+    if (!y) LR_FAIL(device ? "d_y is null" : "y is null");
+    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
+    try {
+        int oc = 1;
+        if (!h->num->lbfgs_push(s, y, device, &oc)) { h->err = h->num->error(); return MI355X_KKT_FATAL; }
+        if (outcome) *outcome = oc;
+        return MI355X_KKT_SUCCESS;
+    } catch (...) { h->err = std::string(name) + ": unexpected exception"; return MI355X_KKT_FATAL; }
+}
+int mi355x_kkt_lbfgs_push(mi355x_kkt_handle h, const double* s, const double* y, int* outcome) { return lbfgs_push_any(h, "lbfgs_push", s, y, false, outcome); }
+int mi355x_kkt_lbfgs_push_device(mi355x_kkt_handle h, const double* d_s, const double* d_y, int* outcome) { return lbfgs_push_any(h, "lbfgs_push_device", d_s, d_y, true, outcome); }
+int mi355x_kkt_lbfgs_reset(mi355x_kkt_handle h)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "lbfgs_reset";
+    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
+    try { if (!h->num->lbfgs_reset()) { h->err = h->num->error(); return MI355X_KKT_FATAL; } return MI355X_KKT_SUCCESS; }
+    catch (...) { h->err = "lbfgs_reset: unexpected exception"; return MI355X_KKT_FATAL; }
+}
+int mi355x_kkt_lbfgs_clear(mi355x_kkt_handle h)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "lbfgs_clear";
+    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
+    try { h->num->lbfgs_clear(); return MI355X_KKT_SUCCESS; } catch (...) { h->err = "lbfgs_clear: unexpected exception"; return MI355X_KKT_FATAL; }
+}
+int mi355x_kkt_lbfgs_info(mi355x_kkt_handle h, int* rows, int* max_history, int* memory, double* sigma, int* skipped_in_a_row, double* push_ms)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "lbfgs_info";
+    if (rows) *rows = 0; if (max_history) *max_history = 0; if (memory) *memory = 0; if (sigma) *sigma = 0.0; if (skipped_in_a_row) *skipped_in_a_row = 0; if (push_ms) *push_ms = 0.0;
+    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
+    h->num->lbfgs_info(rows, max_history, memory, sigma, skipped_in_a_row, push_ms);
+    return MI355X_KKT_SUCCESS;
+}
+int mi355x_kkt_lbfgs_get(mi355x_kkt_handle h, int what, double* out, int64_t capacity)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "lbfgs_get";
+    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
+    if (what < 0 || what > 6) LR_FAIL("what must be in [0, 6]");
+    if (capacity < 0) LR_FAIL("capacity must be >= 0");
+    if (capacity > 0 && !out) LR_FAIL("out is null with capacity > 0");
+    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
+    try { if (!h->num->lbfgs_get(what, out, (long long)capacity)) { h->err = h->num->error(); return MI355X_KKT_FATAL; } return MI355X_KKT_SUCCESS; }
+    catch (...) { h->err = "lbfgs_get: unexpected exception"; return MI355X_KKT_FATAL; }
+}
+// host only, no handle, no device: the small algebra of a push (lbfgs_host.h), m x m column-major with leading dimension m
+int mi355x_kkt_lbfgs_coefficients(int m, const double* sts, const double* L, const double* D, double sigma, double* C_out, double* Lbar_out)
+{
+    if (m < 0 || m > MI355X_KKT_LBFGS_MAX || (m > 0 && (!sts || !L || !D || !C_out || !Lbar_out))) return MI355X_KKT_FATAL;
+    return mi355x::lb_coefficients(m, sts, L, m, D, sigma, nullptr, C_out, Lbar_out, m) ? MI355X_KKT_SUCCESS : MI355X_KKT_SINGULAR;
 }
 #undef LR_FAIL
 

@@ -1,0 +1,102 @@
+// kernels_lbfgs.hip.inc -- part of numeric.hip (one translation unit; included there, inside namespace mi355x, behind kernels_lowrank.hip.inc): the
+// tall-skinny algebra of the limited-memory BFGS updater (reference IpLimMemQuasiNewtonUpdater.cpp: the dots of UpdateInternalData :769-818 and
+// CheckSkippingBFGS :985-1019, the columns V and U :440-520; restated in DESIGN.md).  The history S, Y (rows x max_history each, leading dimension
+// `ld`) is a RING of column slots: the kernels get the logical -> physical slot map by value, so dropping the oldest pair copies nothing.
+// ================================================================================================
+// Two kernels, both streaming (1/4 flop per byte in the dots, m / 16 -- 2 at m = 32 -- in the form: HBM is the ruler, fp64 MFMA buys nothing):
+//   k_lb_dots   per slab of LR_SLAB rows the partials of  s^T S_j, s^T Y_j (j over the m live pairs, oldest first),  s^T s, s^T y, y^T y:
+//               2 m + 3 numbers per slab, summed over the slabs by k_lr_reduce (kernels_lowrank.hip.inc) in its fixed order
+//   k_lb_form   writes the new pair into its slot and forms  V = Y diag(d),  U = sigma S C + V Lbar  in one pass, one thread per row, the small
+//               matrices (d, C, Lbar: lbfgs_host.h) in LDS
+// No atomics; every sum has an order fixed by (rows, m) -- dots: a thread's four rows of the slab in ascending order, the 64 lanes of a wavefront by
+// the xor butterfly 32, 16, 8, 4, 2, 1, the four wavefronts in ascending order, then k_lr_reduce's order over the slabs; form: k ascending in each sum.
+// KP = the compile-time bound on m the loops are unrolled to (8 / 16 / 32: arrays indexed at compile time stay in registers).
+// ================================================================================================
+#define LB_MAX 32         // pairs (MI355X_KKT_LBFGS_MAX = LR_MAX: V and U have one column per stored pair)
+#define LB_NOUT (2 * LB_MAX + 3)
+
+struct LbRing { int m; unsigned char slot[LB_MAX]; };      // logical column j (oldest first), j < m, lives in physical slot slot[j]
+
+// part[slab * (2 m + 3) + o]:  o < m: s^T S_o;  m <= o < 2 m: s^T Y_(o - m);  then s^T s, s^T y, y^T y  -- over the slab's rows
+template <int KP>
+__global__ __launch_bounds__(256) void k_lb_dots(const double* __restrict__ S, const double* __restrict__ Y, long long ld, const double* __restrict__ s,
+                                                 const double* __restrict__ y, int rows, LbRing ring, double* __restrict__ part)
+{
+    __shared__ double wsum[4][LB_NOUT];
+    const int t = threadIdx.x, m = ring.m, nout = 2 * m + 3;
+    const long long r0 = (long long)blockIdx.x * LR_SLAB;
+    double aS[KP], aY[KP], ss = 0.0, sy = 0.0, yy = 0.0;
+#pragma unroll
+    for (int j = 0; j < KP; ++j) { aS[j] = 0.0; aY[j] = 0.0; }
+    for (int q = 0; q < LR_SLAB / 256; ++q) {
+        const long long r = r0 + q * 256 + t;
+        if (r < rows) {
+            const double sv = s[r], yv = y[r];
+            ss = fma(sv, sv, ss); sy = fma(sv, yv, sy); yy = fma(yv, yv, yy);
+#pragma unroll
+            for (int j = 0; j < KP; ++j)
+                if (j < m) {                                           // (uniform)
+                    const long long c = (long long)ring.slot[j] * ld + r;
+                    aS[j] = fma(sv, S[c], aS[j]); aY[j] = fma(sv, Y[c], aY[j]);
+                }
+        }
+    }
+    const int w = t >> 6, lane = t & 63;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        ss += __shfl_xor(ss, d); sy += __shfl_xor(sy, d); yy += __shfl_xor(yy, d);
+#pragma unroll
+        for (int j = 0; j < KP; ++j)
+            if (j < m) { aS[j] += __shfl_xor(aS[j], d); aY[j] += __shfl_xor(aY[j], d); }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < KP; ++j)
+            if (j < m) { wsum[w][j] = aS[j]; wsum[w][m + j] = aY[j]; }
+        wsum[w][2 * m] = ss; wsum[w][2 * m + 1] = sy; wsum[w][2 * m + 2] = yy;
+    }
+    __syncthreads();
+    if (t < nout) part[(long long)blockIdx.x * nout + t] = ((wsum[0][t] + wsum[1][t]) + wsum[2][t]) + wsum[3][t];
+}
+
+// coef (device): d[LB_MAX], then C and Lbar, LB_MAX x LB_MAX column-major each (C upper, Lbar strictly upper triangular; zero elsewhere).
+// ring.m counts the NEW pair, which is logical column m - 1: it is read from s, y and written to its slot of S, Y.  Per row i
+//   V[i, j] = Y[i, j] d_j,   U[i, j] = fma(sigma, sum_{k <= j} S[i, k] C[k, j], sum_{k < j} V[i, k] Lbar[k, j])      (k ascending, fma chains from 0)
+template <int KP>
+__global__ __launch_bounds__(256) void k_lb_form(double* S, double* Y, long long ld, const double* __restrict__ s, const double* __restrict__ y, int rows,
+                                                 LbRing ring, const double* __restrict__ coef, double sigma, double* __restrict__ V, double* __restrict__ U, long long ldv)
+{
+    __shared__ double sd[KP], sC[KP * KP], sL[KP * KP];
+    const int m = ring.m;
+    for (int e = threadIdx.x; e < KP * KP; e += 256) {
+        const int k = e % KP, j = e / KP;
+        sC[e] = coef[LB_MAX + k + j * LB_MAX]; sL[e] = coef[LB_MAX + LB_MAX * LB_MAX + k + j * LB_MAX];
+    }
+    if (threadIdx.x < KP) sd[threadIdx.x] = coef[threadIdx.x];
+    __syncthreads();
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows) return;
+    double sv[KP], vv[KP];
+#pragma unroll
+    for (int j = 0; j < KP; ++j) {
+        sv[j] = 0.0; vv[j] = 0.0;
+        if (j < m) {                                                   // (uniform)
+            const long long c = (long long)ring.slot[j] * ld + i;
+            double yv;
+            if (j == m - 1) { sv[j] = s[i]; yv = y[i]; S[c] = sv[j]; Y[c] = yv; }
+            else { sv[j] = S[c]; yv = Y[c]; }
+            vv[j] = yv * sd[j];
+            V[i + j * ldv] = vv[j];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < KP; ++j)
+        if (j < m) {
+            double a = 0.0, b = 0.0;
+#pragma unroll
+            for (int k = 0; k <= j; ++k) a = fma(sv[k], sC[k + j * KP], a);
+#pragma unroll
+            for (int k = 0; k < j; ++k) b = fma(vv[k], sL[k + j * KP], b);
+            U[i + j * ldv] = fma(sigma, a, b);
+        }
+}

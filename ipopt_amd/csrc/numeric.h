@@ -94,6 +94,15 @@ public:
     bool   lowrank_solve_device2(int nrhs, const double* db, int ldb, double* dx, int ldx);
     bool   lowrank_clear();
     void   lowrank_info(int* rows, int* nv, int* nu, int* current, double* update_ms) const;
+    // limited-memory BFGS (IpLimMemQuasiNewtonUpdater.cpp, BFGS "with skipping"): the (s, y) history of `rows` entries per vector stays on the device;
+    // a push (host or device vectors) answers *outcome = 0 stored, V and U formed on the device and installed as the low-rank update above (not current),
+    // 1 skipped, 2 stored but M not positive definite: the installed columns stay.  lbfgs_get what: 0 S, 1 Y, 2 V, 3 U, 4 D, 5 L, 6 S^T S.
+    bool   lbfgs_define(int rows, int max_history, int init, double init_val, double sigma_min, double sigma_max);
+    bool   lbfgs_push(const double* s, const double* y, bool device, int* outcome);
+    bool   lbfgs_reset();
+    bool   lbfgs_clear();
+    void   lbfgs_info(int* rows, int* max_history, int* memory, double* sigma, int* skipped_in_a_row, double* push_ms) const;
+    bool   lbfgs_get(int what, double* out, long long capacity);
     long long factor_count() const;                  // bumped by every factorisation (the refactorisations of a delayed-pivot loop included) and every structure edit
     // communicator of a multi-GPU handle: with one set, factor()/solve_*() run the whole distributed sequence themselves
     bool   set_comm_rccl(const void* unique_id128);                                   // RCCL (dlopen'ed), ncclCommInitRank(nranks, id, rank)

@@ -40,6 +40,7 @@
 #include "matching_scaling.h"
 #include "device_owner.h"      // DeviceOwner, HIPCHK
 #include "lowrank_host.h"      // the host Cholesky of the low-rank update
+#include "lbfgs_host.h"        // the small algebra of the limited-memory BFGS updater
 
 namespace mi355x {
 
@@ -69,6 +70,7 @@ static constexpr double ZERO_REL = 1e-14;                // zero-pivot test rela
 #include "kernels_pd_multigpu.hip.inc"
 #include "kernels_match.hip.inc"
 #include "kernels_lowrank.hip.inc"
+#include "kernels_lbfgs.hip.inc"
 // ------------------------------------------------------------------------------------------------
 // host-side orchestration
 // ------------------------------------------------------------------------------------------------
@@ -100,6 +102,7 @@ public:
     DeviceOwner own_asm{err_};         // until assembly_define or release(false): the assembly sources and their staging
     DeviceOwner own_pd{err_};          // until pd_define or release(false): the primal-dual workspace
     DeviceOwner own_lr{err_};          // until lowrank_set / lowrank_clear or release(false): the low-rank update (caller's numbering: survives a restructure, like own_pd)
+    DeviceOwner own_lb{err_};          // until lbfgs_define / lbfgs_clear or release(false): the L-BFGS history (caller's numbering, like own_lr)
     DevView V{};
     int* d_stats = nullptr;
     double* d_rhs = nullptr; size_t d_rhs_cap = 0;
@@ -463,6 +466,7 @@ public:
             own_asm.clear(); asm_.nseg = 0;
             own_pd.clear(); pd_ready = false;
             own_lr.clear(); lr_set = lr_ok = false;
+            own_lb.clear(); lb_defined = false;
             own_handle.clear(); h_vals = nullptr; h_stats = nullptr; ev0 = ev1 = nullptr; V.tvals = nullptr; d_user_scale = nullptr; prof_ev.clear(); prof_used = 0; prof_kind.clear();
             if (stream3) { (void)hipStreamDestroy(stream3); stream3 = nullptr; }
             if (stream2) { (void)hipStreamDestroy(stream2); stream2 = nullptr; }
@@ -1394,11 +1398,10 @@ public:
         err_ = std::string(who) + ": the low-rank update acts on more rows than the x block has (rows <= n_x)"; return false;
     }
     void lowrank_clear() { own_lr.clear(); lr_set = lr_ok = false; lr_at = -1; lr_rows = lr_nv = lr_nu = 0; lr_update_ms = 0; lr_V = lr_U = lr_Z1 = lr_Z2 = lr_part = lr_T = lr_L1 = lr_L2 = lr_h = nullptr; }
-    bool lowrank_set(int rows, int nv, const double* Vh, int ldv, int nu, const double* Uh, int ldu) {
-        DeviceGuard guard(dev);
-        if (!ready) { if (err_.empty()) err_ = "lowrank_set: solver not set up"; return false; }
-        if (multi) { err_ = "lowrank_set: not supported on a multi-GPU handle"; return false; }
-        HIPCHK(hipStreamSynchronize(stream));      // (a correction still in flight reads the buffers about to be freed)
+    // the buffers of an update of the shape (rows, nv, nu), set and not current: those in place when that is the installed shape (nothing is
+    // allocated: an L-BFGS push with a full history installs its columns into them), fresh ones otherwise.  Nothing may be in flight on them.
+    bool lr_shape(int rows, int nv, int nu) {
+        if (lr_set && rows == lr_rows && nv == lr_nv && nu == lr_nu) { lr_ok = false; lr_at = -1; lr_update_ms = 0; return true; }
         lowrank_clear();
         const size_t n = S->n;
         lr_rows = rows; lr_nv = nv; lr_nu = nu;
@@ -1406,6 +1409,16 @@ public:
         if (!O.raw(&lr_V, (size_t)rows * nv) || !O.raw(&lr_U, (size_t)rows * nu) || !O.raw(&lr_Z1, n * nv) || !O.raw(&lr_Z2, n * nu) ||
             !O.raw(&lr_part, (size_t)lr_nslab() * LR_MAX * LR_MAX) || !O.raw(&lr_T, LR_MAX * LR_MAX) || !O.raw(&lr_L1, LR_MAX * LR_MAX) || !O.raw(&lr_L2, LR_MAX * LR_MAX) ||
             !O.pinned(&lr_h, LR_MAX * LR_MAX)) { lowrank_clear(); return false; }
+        lr_set = true;
+        return true;
+    }
+    bool lowrank_set(int rows, int nv, const double* Vh, int ldv, int nu, const double* Uh, int ldu) {
+        DeviceGuard guard(dev);
+        if (!ready) { if (err_.empty()) err_ = "lowrank_set: solver not set up"; return false; }
+        if (multi) { err_ = "lowrank_set: not supported on a multi-GPU handle"; return false; }
+        HIPCHK(hipStreamSynchronize(stream));      // (a correction still in flight reads the buffers about to be freed or overwritten)
+        if (!lr_shape(rows, nv, nu)) return false;
+        lr_set = false;                            // (until both copies have arrived)
         if (rows > 0 && nv > 0) HIPCHK(hipMemcpy2D(lr_V, (size_t)rows * sizeof(double), Vh, (size_t)ldv * sizeof(double), (size_t)rows * sizeof(double), nv, hipMemcpyHostToDevice));
         if (rows > 0 && nu > 0) HIPCHK(hipMemcpy2D(lr_U, (size_t)rows * sizeof(double), Uh, (size_t)ldu * sizeof(double), (size_t)rows * sizeof(double), nu, hipMemcpyHostToDevice));
         lr_set = true;
@@ -1539,6 +1552,125 @@ public:
     void lowrank_info(int* rows, int* nv, int* nu, int* current, double* update_ms) const {
         if (rows) *rows = lr_set ? lr_rows : 0; if (nv) *nv = lr_set ? lr_nv : 0; if (nu) *nu = lr_set ? lr_nu : 0;
         if (current) *current = lr_current() ? 1 : 0; if (update_ms) *update_ms = lr_set ? lr_update_ms : 0.0;
+    }
+
+    // ---------------- limited-memory BFGS: the (s, y) history on the device, V and U formed there (IpLimMemQuasiNewtonUpdater.cpp) ----------------
+    // S, Y (rows x max_history, a ring of column slots; logical column j = slot (lb_head + j) % lb_max) stay on the device until lbfgs_define /
+    // lbfgs_clear; a push moves two vectors: k_lb_dots + k_lr_reduce give the 2 m + 3 dots (ONE download, ONE synchronisation), lbfgs_host.h does the
+    // skip test, sigma, the augment / shift of D, L, S^T S and the coefficients d, C, Lbar, and k_lb_form writes the pair into its slot and V, U into the
+    // low-rank update's own buffers: outcome 0 is lowrank_set(rows, m, V, m, U) with these columns.  Caller's numbering, like own_lr: survives a restructure.
+    bool lb_defined = false;
+    int lb_rows = 0, lb_max = 0, lb_init = 0, lb_m = 0, lb_head = 0, lb_skipped = 0;
+    double lb_init_val = 1.0, lb_smin = 1e-8, lb_smax = 1e8, lb_sig = 1.0, lb_push_ms = 0;
+    double *lb_S = nullptr, *lb_Y = nullptr, *lb_sy = nullptr, *lb_part = nullptr, *lb_T = nullptr, *lb_coef = nullptr, *lb_h = nullptr, *lb_hc = nullptr;
+    double lb_D[LB_MAX], lb_L[LB_MAX * LB_MAX], lb_STS[LB_MAX * LB_MAX];
+    static constexpr int LB_NCOEF = LB_MAX + 2 * LB_MAX * LB_MAX;
+    int lb_nslab() const { return std::max(1, (lb_rows + LR_SLAB - 1) / LR_SLAB); }
+    LbRing lb_ring(int m) const { LbRing R; R.m = m; for (int j = 0; j < LB_MAX; ++j) R.slot[j] = (unsigned char)((lb_head + j) % std::max(lb_max, 1)); return R; }
+    void lb_forget() { lb_m = lb_head = lb_skipped = 0; lb_sig = lb_init_val; }
+    void lbfgs_clear() { own_lb.clear(); lb_defined = false; lb_rows = lb_max = 0; lb_push_ms = 0; lb_forget(); lb_S = lb_Y = lb_sy = lb_part = lb_T = lb_coef = lb_h = lb_hc = nullptr; }
+    bool lbfgs_define(int rows, int max_history, int init, double init_val, double smin, double smax) {
+        DeviceGuard guard(dev);
+        if (!ready) { if (err_.empty()) err_ = "lbfgs_define: solver not set up"; return false; }
+        if (multi) { err_ = "lbfgs_define: not supported on a multi-GPU handle"; return false; }
+        HIPCHK(hipStreamSynchronize(stream));
+        lbfgs_clear();
+        lb_rows = rows; lb_max = max_history; lb_init = init; lb_init_val = init_val; lb_smin = smin; lb_smax = smax;
+        DeviceOwner& O = own_lb;
+        if (!O.zeroed(&lb_S, (size_t)rows * max_history) || !O.zeroed(&lb_Y, (size_t)rows * max_history) || !O.raw(&lb_sy, 2 * (size_t)rows) ||
+            !O.raw(&lb_part, (size_t)lb_nslab() * LB_NOUT) || !O.raw(&lb_T, LB_NOUT) || !O.raw(&lb_coef, LB_NCOEF) ||
+            !O.pinned(&lb_h, LB_NOUT) || !O.pinned(&lb_hc, LB_NCOEF)) { lbfgs_clear(); return false; }
+        HIPCHK(hipDeviceSynchronize());            // (the zero fills ran on the default stream: device_owner.h)
+        lb_forget();
+        lb_defined = true;
+        return true;
+    }
+    bool lbfgs_reset() {
+        DeviceGuard guard(dev);
+        if (!lb_defined) { err_ = "lbfgs_reset: lbfgs_define first"; return false; }
+        HIPCHK(hipStreamSynchronize(stream));
+        lb_forget();
+        lowrank_clear();
+        return true;
+    }
+    template <int KP> void lb_launch_dots(const double* ds, const double* dy) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_dots<KP>), dim3(lb_nslab()), dim3(256), 0, stream, (const double*)lb_S, (const double*)lb_Y, (long long)lb_rows, ds, dy, lb_rows, lb_ring(lb_m), lb_part);
+    }
+    template <int KP> void lb_launch_form(const double* ds, const double* dy) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_form<KP>), dim3((lb_rows + 255) / 256), dim3(256), 0, stream, lb_S, lb_Y, (long long)lb_rows, ds, dy, lb_rows, lb_ring(lb_m),
+                           (const double*)lb_coef, lb_sig, lr_V, lr_U, (long long)lb_rows);
+    }
+    // s, y: host vectors (device = false: uploaded to the staging pair) or device vectors of lb_rows.  *outcome: 0 stored and installed, 1 skipped, 2 stored, M not positive definite
+    bool lbfgs_push(const double* s, const double* y, bool device, int* outcome) {
+        DeviceGuard guard(dev);
+        *outcome = 1;
+        if (!ready) { if (err_.empty()) err_ = "lbfgs_push: solver not set up"; return false; }
+        if (!lb_defined) { err_ = "lbfgs_push: lbfgs_define first"; return false; }
+        const auto t0 = std::chrono::steady_clock::now();
+        const size_t vb = (size_t)lb_rows * sizeof(double);
+        const double *ds = s, *dy = y;
+        if (!device) {
+            HIPCHK(hipMemcpyAsync(lb_sy, s, vb, hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemcpyAsync(lb_sy + lb_rows, y, vb, hipMemcpyHostToDevice, stream));
+            ds = lb_sy; dy = lb_sy + lb_rows;
+        }
+        const int m0 = lb_m, nout = 2 * m0 + 3;
+        if (m0 <= 8) lb_launch_dots<8>(ds, dy); else if (m0 <= 16) lb_launch_dots<16>(ds, dy); else lb_launch_dots<32>(ds, dy);
+        hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lb_part, lb_nslab(), 0LL, (long long)nout, nout, 1, (const double*)nullptr, lb_T);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(lb_h, lb_T, (size_t)nout * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));      // the one synchronisation of a push (it also ends the form kernel of the push before: lb_hc is free)
+        const double ss = lb_h[2 * m0], sy = lb_h[2 * m0 + 1], yy = lb_h[2 * m0 + 2];
+        auto done = [&] { lb_push_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); return true; };
+        if (lb_skip(ss, sy, yy)) { ++lb_skipped; return done(); }
+        lb_skipped = 0;
+        lb_sig = lb_sigma(lb_init, lb_init_val, lb_smin, lb_smax, ss, sy, yy);
+        if (lb_m == lb_max) lb_head = (lb_head + 1) % lb_max;
+        lb_m = lb_store(lb_m, lb_max, lb_D, lb_L, lb_STS, lb_h, lb_h + m0, ss, sy);
+        const LbRing R = lb_ring(lb_m);
+        std::fill(lb_hc, lb_hc + LB_NCOEF, 0.0);
+        if (!lb_coefficients(lb_m, lb_STS, lb_L, LB_MAX, lb_D, lb_sig, lb_hc, lb_hc + LB_MAX, lb_hc + LB_MAX + LB_MAX * LB_MAX, LB_MAX)) {
+            // the reference has stored the pair by now (:484-495): so have we; the installed columns stay what they were
+            double* slot = lb_S + (size_t)R.slot[lb_m - 1] * lb_rows; double* sloty = lb_Y + (size_t)R.slot[lb_m - 1] * lb_rows;
+            HIPCHK(hipMemcpyAsync(slot, ds, vb, hipMemcpyDeviceToDevice, stream));
+            HIPCHK(hipMemcpyAsync(sloty, dy, vb, hipMemcpyDeviceToDevice, stream));
+            if (device) HIPCHK(hipStreamSynchronize(stream));
+            *outcome = 2;
+            return done();
+        }
+        if (!lr_shape(lb_rows, lb_m, lb_m)) return false;      // (nothing is in flight behind the synchronisation above)
+        HIPCHK(hipMemcpyAsync(lb_coef, lb_hc, LB_NCOEF * sizeof(double), hipMemcpyHostToDevice, stream));
+        if (lb_m <= 8) lb_launch_form<8>(ds, dy); else if (lb_m <= 16) lb_launch_form<16>(ds, dy); else lb_launch_form<32>(ds, dy);
+        HIPCHK(hipGetLastError());
+        if (device) HIPCHK(hipStreamSynchronize(stream));      // (the caller's vectors are free again when the call returns)
+        *outcome = 0;
+        return done();
+    }
+    void lbfgs_info(int* rows, int* max_history, int* memory, double* sigma, int* skipped, double* push_ms) const {
+        if (rows) *rows = lb_defined ? lb_rows : 0; if (max_history) *max_history = lb_defined ? lb_max : 0; if (memory) *memory = lb_defined ? lb_m : 0;
+        if (sigma) *sigma = lb_defined ? lb_sig : 0.0; if (skipped) *skipped = lb_defined ? lb_skipped : 0; if (push_ms) *push_ms = lb_defined ? lb_push_ms : 0.0;
+    }
+    // what: 0 S, 1 Y (rows x memory, oldest first), 2 V, 3 U (the installed columns of the low-rank update), 4 D, 5 L, 6 S^T S (memory x memory); column-major, no padding
+    bool lbfgs_get(int what, double* out, long long capacity) {
+        DeviceGuard guard(dev);
+        if (!lb_defined) { err_ = "lbfgs_get: lbfgs_define first"; return false; }
+        const long long need = what <= 1 ? (long long)lb_rows * lb_m : what == 2 ? (lr_set ? (long long)lr_rows * lr_nv : 0) : what == 3 ? (lr_set ? (long long)lr_rows * lr_nu : 0)
+                             : what == 4 ? lb_m : (long long)lb_m * lb_m;
+        if (capacity < need) { err_ = "lbfgs_get: capacity is below the " + std::to_string(need) + " doubles of this array"; return false; }
+        HIPCHK(hipStreamSynchronize(stream));
+        if (what <= 1) {
+            const LbRing R = lb_ring(lb_m);
+            for (int j = 0; j < lb_m; ++j)
+                HIPCHK(hipMemcpy(out + (size_t)j * lb_rows, (what == 0 ? lb_S : lb_Y) + (size_t)R.slot[j] * lb_rows, (size_t)lb_rows * sizeof(double), hipMemcpyDeviceToHost));
+        } else if (what <= 3) {
+            if (need > 0) HIPCHK(hipMemcpy(out, what == 2 ? lr_V : lr_U, (size_t)need * sizeof(double), hipMemcpyDeviceToHost));
+        } else if (what == 4) {
+            for (int j = 0; j < lb_m; ++j) out[j] = lb_D[j];
+        } else {
+            const double* A = what == 5 ? lb_L : lb_STS;
+            for (int j = 0; j < lb_m; ++j) for (int i = 0; i < lb_m; ++i) out[i + (size_t)j * lb_m] = A[i + j * LB_MAX];
+        }
+        return true;
     }
 
     // ---------------- multi-GPU orchestration (eager launches) ----------------
@@ -1844,6 +1976,12 @@ bool Numeric::lowrank_solve_device2(int nrhs, const double* db, int ldb, double*
 bool Numeric::lowrank_clear() { DeviceGuard guard(p_->dev); if (p_->stream) (void)hipStreamSynchronize(p_->stream); p_->lowrank_clear(); return true; }
 void Numeric::lowrank_info(int* rows, int* nv, int* nu, int* current, double* update_ms) const { p_->lowrank_info(rows, nv, nu, current, update_ms); }
 long long Numeric::factor_count() const { return p_->factor_count; }
+bool Numeric::lbfgs_define(int rows, int max_history, int init, double init_val, double sigma_min, double sigma_max) { return p_->lbfgs_define(rows, max_history, init, init_val, sigma_min, sigma_max); }
+bool Numeric::lbfgs_push(const double* s, const double* y, bool device, int* outcome) { return p_->lbfgs_push(s, y, device, outcome); }
+bool Numeric::lbfgs_reset() { return p_->lbfgs_reset(); }
+bool Numeric::lbfgs_clear() { DeviceGuard guard(p_->dev); if (p_->stream) (void)hipStreamSynchronize(p_->stream); p_->lbfgs_clear(); return true; }
+void Numeric::lbfgs_info(int* rows, int* max_history, int* memory, double* sigma, int* skipped_in_a_row, double* push_ms) const { p_->lbfgs_info(rows, max_history, memory, sigma, skipped_in_a_row, push_ms); }
+bool Numeric::lbfgs_get(int what, double* out, long long capacity) { return p_->lbfgs_get(what, out, capacity); }
 bool Numeric::ruiz_triplet(int device, int n, int nnz, const int* irn, const int* jcn, const double* a, int base, int sweeps, double* out, std::string& err)
 {
     int ndev = 0;

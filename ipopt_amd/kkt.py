@@ -74,8 +74,12 @@ ABI_SYMBOLS = [
     "mi355x_kkt_set_scaling", "mi355x_kkt_get_scaling", "mi355x_kkt_ruiz_scaling", "mi355x_kkt_matching_scaling", "mi355x_kkt_zero_pivots", "mi355x_kkt_failed_pivots", "mi355x_kkt_delay_columns", "mi355x_kkt_set_delay_rounds", "mi355x_kkt_assembly_define", "mi355x_kkt_assembly_buffer", "mi355x_kkt_assembly_upload", "mi355x_kkt_factor_assembled",
     "mi355x_kkt_pd_define", "mi355x_kkt_pd_put_data", "mi355x_kkt_pd_put", "mi355x_kkt_pd_get", "mi355x_kkt_pd_solve_once", "mi355x_kkt_pd_residual",
     "mi355x_kkt_lowrank_set", "mi355x_kkt_lowrank_update", "mi355x_kkt_lowrank_solve", "mi355x_kkt_lowrank_solve_device2", "mi355x_kkt_lowrank_clear", "mi355x_kkt_lowrank_info",
+    "mi355x_kkt_lbfgs_define", "mi355x_kkt_lbfgs_push", "mi355x_kkt_lbfgs_push_device", "mi355x_kkt_lbfgs_reset", "mi355x_kkt_lbfgs_clear", "mi355x_kkt_lbfgs_info", "mi355x_kkt_lbfgs_get", "mi355x_kkt_lbfgs_coefficients",
 ]
 LOWRANK_MAX = 32
+LBFGS_MAX = 32
+LBFGS_INIT = {"scalar1": 0, "scalar2": 1, "scalar3": 2, "scalar4": 3, "constant": 4}      # limited_memory_initialization
+LBFGS_STORED, LBFGS_SKIPPED, LBFGS_NOT_POSDEF = 0, 1, 2                                     # outcome of a push
 KERNEL_KINDS = ["gather_scale", "front_wave", "front_lds64", "front_lds128", "big_assemble", "big_diag", "big_trsm", "big_schur",
                 "stats", "solve_perm", "fwd_wave", "fwd_lds", "fwd_big", "bwd_wave", "bwd_lds", "bwd_big", "fwd_big_upd", "bwd_big_dot"]
 
@@ -146,6 +150,14 @@ def load_library():
     lib.mi355x_kkt_lowrank_solve_device2.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int]
     lib.mi355x_kkt_lowrank_clear.argtypes = [vp]
     lib.mi355x_kkt_lowrank_info.argtypes = [vp, ip, ip, ip, ip, dp]
+    lib.mi355x_kkt_lbfgs_define.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]
+    lib.mi355x_kkt_lbfgs_push.argtypes = [vp, vp, vp, ip]
+    lib.mi355x_kkt_lbfgs_push_device.argtypes = [vp, vp, vp, ip]
+    lib.mi355x_kkt_lbfgs_reset.argtypes = [vp]
+    lib.mi355x_kkt_lbfgs_clear.argtypes = [vp]
+    lib.mi355x_kkt_lbfgs_info.argtypes = [vp, ip, ip, ip, dp, ip, dp]
+    lib.mi355x_kkt_lbfgs_get.argtypes = [vp, C.c_int, vp, C.c_int64]
+    lib.mi355x_kkt_lbfgs_coefficients.argtypes = [C.c_int, vp, vp, vp, C.c_double, vp, vp]
     lib.mi355x_kkt_set_comm_rccl.argtypes = [vp, vp]
     lib.mi355x_kkt_comm_shm_id.argtypes = [vp, C.c_int]
     lib.mi355x_kkt_set_comm_shm.argtypes = [vp, vp]
@@ -156,6 +168,19 @@ def load_library():
     lib.mi355x_kkt_comm_info.argtypes = [vp, ip, ip, ip, ip]
     _LIB = lib
     return lib
+
+
+def lbfgs_coefficients(sts, L, D, sigma):
+    """host only, no handle, no GPU: (status, C, Lbar) of include/mi355x_kkt.h's mi355x_kkt_lbfgs_coefficients; status SUCCESS or SINGULAR"""
+    D = np.ascontiguousarray(D, dtype=np.float64); m = D.shape[0]
+    sts = np.asfortranarray(sts, dtype=np.float64); L = np.asfortranarray(L, dtype=np.float64)
+    if sts.shape != (m, m) or L.shape != (m, m):
+        raise KKTError("lbfgs_coefficients: S^T S and L must be m x m, D of m")
+    Cm = np.zeros((m, m), order="F"); Lbar = np.zeros((m, m), order="F")
+    st = load_library().mi355x_kkt_lbfgs_coefficients(m, sts.ctypes.data, L.ctypes.data, D.ctypes.data, float(sigma), Cm.ctypes.data, Lbar.ctypes.data)
+    if st == FATAL:
+        raise KKTError("lbfgs_coefficients: m must be in [0, 32]")
+    return st, Cm, Lbar
 
 
 class KKTSolver:
@@ -375,6 +400,59 @@ class KKTSolver:
         if self.lib.mi355x_kkt_lowrank_info(self._h, C.byref(r), C.byref(v), C.byref(u), C.byref(c), C.byref(ms)) != 0:
             raise KKTError("lowrank_info: " + self.last_error())
         return {"rows": r.value, "nv": v.value, "nu": u.value, "current": bool(c.value), "update_ms": ms.value}
+
+    # --- limited-memory BFGS: the (s, y) history on the device, V and U formed there (include/mi355x_kkt.h; reference IpLimMemQuasiNewtonUpdater.cpp) ---
+    def lbfgs_define(self, rows, max_history=6, init="scalar1", init_val=1.0, sigma_min=1e-8, sigma_max=1e8):
+        """init: a name of LBFGS_INIT or its number"""
+        st = self.lib.mi355x_kkt_lbfgs_define(self._h, int(rows), int(max_history), LBFGS_INIT.get(init, init), init_val, sigma_min, sigma_max)
+        if st != 0:
+            raise KKTError("lbfgs_define: " + self.last_error())
+
+    def lbfgs_push(self, s: np.ndarray, y: np.ndarray) -> int:
+        """host vectors of `rows`; -> outcome: LBFGS_STORED (V, U installed as the low-rank update), LBFGS_SKIPPED, LBFGS_NOT_POSDEF"""
+        rows = self.lbfgs_info()["rows"]
+        s = np.ascontiguousarray(s, dtype=np.float64); y = np.ascontiguousarray(y, dtype=np.float64)
+        if rows and (s.shape != (rows,) or y.shape != (rows,)):      # (rows = 0: nothing is defined, which the library says itself)
+            raise KKTError("lbfgs_push: s and y must be vectors of `rows`")
+        oc = C.c_int(0)
+        if self.lib.mi355x_kkt_lbfgs_push(self._h, s.ctypes.data, y.ctypes.data, C.byref(oc)) != 0:
+            raise KKTError("lbfgs_push: " + self.last_error())
+        return oc.value
+
+    def lbfgs_push_device(self, ds_ptr: int, dy_ptr: int) -> int:
+        """device vectors of `rows`, complete before the call"""
+        oc = C.c_int(0)
+        if self.lib.mi355x_kkt_lbfgs_push_device(self._h, C.c_void_p(ds_ptr), C.c_void_p(dy_ptr), C.byref(oc)) != 0:
+            raise KKTError("lbfgs_push_device: " + self.last_error())
+        return oc.value
+
+    def lbfgs_reset(self):
+        if self.lib.mi355x_kkt_lbfgs_reset(self._h) != 0:
+            raise KKTError("lbfgs_reset: " + self.last_error())
+
+    def lbfgs_clear(self):
+        if self.lib.mi355x_kkt_lbfgs_clear(self._h) != 0:
+            raise KKTError("lbfgs_clear: " + self.last_error())
+
+    def lbfgs_info(self) -> dict:
+        r, mh, m, sk, sg, ms = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_double(0.0), C.c_double(0.0)
+        if self.lib.mi355x_kkt_lbfgs_info(self._h, C.byref(r), C.byref(mh), C.byref(m), C.byref(sg), C.byref(sk), C.byref(ms)) != 0:
+            raise KKTError("lbfgs_info: " + self.last_error())
+        return {"rows": r.value, "max_history": mh.value, "memory": m.value, "sigma": sg.value, "skipped_in_a_row": sk.value, "push_ms": ms.value}
+
+    def lbfgs_get(self, what) -> np.ndarray:
+        """what: "S" | "Y" (rows x memory, oldest first), "V" | "U" (the installed columns), "D" (memory), "L" | "STS" (memory x memory), or 0..6"""
+        w = {"S": 0, "Y": 1, "V": 2, "U": 3, "D": 4, "L": 5, "STS": 6}.get(what, what)
+        I = self.lbfgs_info(); m = I["memory"]
+        if w in (2, 3):
+            lr = self.lowrank_info()
+            shape = (lr["rows"], lr["nv"] if w == 2 else lr["nu"])
+        else:
+            shape = (I["rows"], m) if w in (0, 1) else (m,) if w == 4 else (m, m)
+        out = np.zeros(shape, dtype=np.float64, order="F")
+        if self.lib.mi355x_kkt_lbfgs_get(self._h, int(w), out.ctypes.data if out.size else None, out.size) != 0:
+            raise KKTError("lbfgs_get: " + self.last_error())
+        return out
 
     # --- multi-GPU communicator (include/mi355x_kkt.h): after one of these, multi_solve / factor_device / solve_device* of a
     #     handle created with nranks > 1 run the distributed sequence inside the library ---
