@@ -352,7 +352,16 @@ int  mi355x_kkt_get_symbolic(mi355x_kkt_handle h, int what, int* out, int64_t ca
  *   "lc_ptr" / "lc_fronts" (leaf chains: their fronts, leaf first), "df_runs" ({lv0, lv1, tab0, nlev, nq} per k_front_df run),
  *   "chain_segs" (9 ints per data-flow sweep segment), "chain_links" ({s, k, koff, fi} per link), "chain_descs" ({link0, nlinks, tail, ktot, s0, init}
  *   per chain), "join" ({base, count, maxm, who} per kind), "exchange" ({step, glo, gsz, arena doubles, top-rhs doubles} per range),
- *   "col_owner", "stat_owner", "scalars" {levels, exchange steps, leaf-chain levels, leaf chains, look-ahead, grouped, tfuse fronts, big fronts, stages}. */
+ *   "col_owner", "stat_owner", "scalars" {levels, exchange steps, leaf-chain levels, leaf chains, look-ahead, grouped, tfuse fronts, big fronts, stages}.
+ *   What a system REACHES -- the fields the kernels and the launch code branch on (the tests show with them that a fixture runs the path it names):
+ *   "path_bits" one int per launch-list entry: 1 contribution block formed by its update (tfuse), 2 assembles itself (selfasm), 4 solo (fused forward
+ *   solve), 8 split (look-ahead), 16 has an XCD tile table, 32 has a second one (part 2 of a split update), 64 asmcut != 0, 128 k_big_assemble2's
+ *   fast path is open to it, 256 in place on a child;  "asm_fast_ok" (per entry: children that kernel pulls, 0 = not for it), "asmcut" (per entry);
+ *   "levels" 10 ints per level {la_tiles1, la_tiles2, la_full, lv_asm_skip, lv_narrow_tiles, part_tiles[0], part_tiles[1], wave_mmin (2^30: no such
+ *   front), wave_mmax, wave_kmax};  "groups" 11 ints per level of the single-GPU / own-subtree grouped schedule {g0, g1, split, nrb, tiles64, tiles,
+ *   la1, la2, p1t, la3, nsplit};  "path_scalars" {pair_solve, la_any, ints of the tile tables, grp_cut_level, solve_group, cb_window};
+ *   "inputs" the settings the plan is built with {chain_solve, fuse_dt, fastpiv, asm_pull, leafchain, front_df, tfuse, fuse_upd, selfasm, grouped,
+ *   xcd_tiles, lookahead, pair_solve, p1_small, la_wgs, la_min_nt, grp_rbw_max, chain_solve_maxc, fuse_dt_maxwg, la_min_tiles}. */
 int  mi355x_kkt_get_launch_plan(mi355x_kkt_handle h, int nranks, int rank, const char* what, int* out, int64_t capacity, int64_t* count);
 
 /* ---- measurement: device time per kernel kind (hip events around every launch of an eager, graph-less factor + one

@@ -719,6 +719,18 @@ int mi355x_kkt_get_launch_plan(mi355x_kkt_handle h, int nranks, int rank, const 
         else if (w == "exchange") for (const RangeSeg& G : P.ex.rsegs) put({G.d, G.glo, G.gsz, G.aend - G.abeg, G.tend - G.tbeg});
         else if (w == "col_owner") v = P.col_owner;
         else if (w == "stat_owner") v = P.stat_owner;
+        // what a fixture REACHES (tests/support/reach.py): the fields the kernels branch on, which the arrays above do not show
+        else if (w == "path_bits") for (size_t q = 0; q < P.fmeta.size(); ++q) { const FrontMeta& M = P.fmeta[q];
+            put({(M.tfuse ? 1 : 0) | (M.selfasm ? 2 : 0) | (M.solo ? 4 : 0) | (M.split ? 8 : 0) | (M.ttab >= 0 ? 16 : 0) | (M.ttab2 >= 0 ? 32 : 0) | (M.asmcut ? 64 : 0) | (P.asm_fast_ok[q] ? 128 : 0) | (M.alias ? 256 : 0)}); }
+        else if (w == "asm_fast_ok") v.assign(P.asm_fast_ok.begin(), P.asm_fast_ok.end());
+        else if (w == "asmcut") v = P.asmcut;
+        else if (w == "levels") for (int lv = 0; lv < P.nlevels; ++lv)
+            put({P.la_tiles1[lv], P.la_tiles2[lv], P.la_full[lv], P.lv_asm_skip[lv], P.lv_narrow_tiles[lv], P.part_tiles[0][lv], P.part_tiles[1][lv], P.wave_mmin[lv], P.wave_mmax[lv], P.wave_kmax[lv]});
+        else if (w == "groups") { const GrpSched& G = P.grp[0]; for (int lv = 0; lv < P.nlevels; ++lv) put({G.g0[lv], G.g1[lv], G.split[lv], G.nrb[lv], G.tiles64[lv], G.tiles[lv], G.la1[lv], G.la2[lv], G.p1t[lv], G.la3[lv], G.nsplit[lv]}); }
+        else if (w == "path_scalars") put({P.pair_solve, P.la_any, (long long)P.tile_tab.size(), h->sym.grp_cut_level, h->sym.solve_group, h->sym.cb_window});
+        else if (w == "inputs") { const PlanInputs in = plan_inputs_from_env(nranks, rank, nranks > 1, 0);
+            put({in.chain_solve, in.fuse_dt, in.fastpiv, in.asm_pull, in.leafchain, in.front_df, in.tfuse, in.fuse_upd, in.selfasm, in.grouped, in.xcd_tiles, in.lookahead, in.pair_solve, in.p1_small,
+                 in.la_wgs, in.la_min_nt, in.grp_rbw_max, in.chain_solve_maxc, in.fuse_dt_maxwg, std::min<long long>(in.la_min_tiles, 0x7fffffffll)}); }
         else { h->err = "get_launch_plan: unknown array"; return MI355X_KKT_FATAL; }
         *count = (int64_t)v.size();
         if (out) { if ((int64_t)v.size() > cap) { h->err = "get_launch_plan: buffer too small"; return MI355X_KKT_FATAL; } std::copy(v.begin(), v.end(), out); }

@@ -126,6 +126,47 @@ def grid_kkt(nx_grid, ny_grid, dof=1, ncon=1, seed=0, delta_c=0.0, sigma_exp=3.0
     return kkt_from_blocks((r, c, v), Sigma, (jr.ravel(), jc.ravel(), jv.ravel()), np.full(m, delta_c), nxv, m) + (m,)
 
 
+def clique_kkt(sizes, sep, m_con, seed=0, delta_c=0.0):
+    """Dense cliques along a path: clique i couples sizes[i] primal variables, of which the first `sep` are the last `sep` of clique i - 1.  The
+    elimination tree is ONE chain of supernodes whose fronts shrink from the largest clique down -- the smallest system whose fronts are large
+    (order > 1024: the 128 x 128 trailing update; >= 12 tile rows: the XCD tile tables).  H is diagonally dominant (SPD), Sigma = 10^U(-3, 3); the
+    m_con constraint rows couple three consecutive variables each, with a dominant anchor in the middle, on DISJOINT supports (full row rank whatever
+    the values) => inertia (n_x, m_con, 0) exactly."""
+    rng = np.random.default_rng(seed)
+    sizes = [int(s) for s in sizes]
+    assert all(s > sep for s in sizes) and sep >= 0
+    nx = sum(sizes) - sep * (len(sizes) - 1)
+    assert 3 * m_con <= nx
+    hi, hj, hv, first = [], [], [], 0
+    for i, s in enumerate(sizes):
+        a, b = np.tril_indices(s, -1)
+        if i > 0 and sep > 0:                       # (the pairs inside the shared variables belong to clique i - 1)
+            keep = a >= sep
+            a, b = a[keep], b[keep]
+        hi.append(first + b); hj.append(first + a); hv.append(rng.uniform(-1, 1, a.shape[0]))      # upper: row < col
+        first += s - sep
+    hi, hj, hv = np.concatenate(hi), np.concatenate(hj), np.concatenate(hv)
+    diag = np.zeros(nx)
+    np.add.at(diag, hi, np.abs(hv)); np.add.at(diag, hj, np.abs(hv))
+    diag += rng.uniform(0.1, 1.0, nx)
+    hi = np.concatenate([np.arange(nx), hi]); hj = np.concatenate([np.arange(nx), hj]); hv = np.concatenate([diag, hv])
+    Sigma = 10.0 ** rng.uniform(-3, 3, nx)
+    start = (np.arange(m_con) * nx) // max(m_con, 1)
+    start = np.minimum(start, nx - 3)
+    ji = np.repeat(np.arange(m_con), 3); jj = (start[:, None] + np.arange(3)[None, :]).ravel()
+    jv = rng.uniform(-1, 1, (m_con, 3)); jv[:, 1] = 1.5 + rng.uniform(0, 1, m_con)
+    return kkt_from_blocks((hi, hj, hv), Sigma, (ji, jj, jv.ravel()), np.full(m_con, delta_c), nx, m_con) + (m_con,)
+
+
+def block_diag(*systems):
+    """the direct sum of systems (n, row, col, val, neg): independent components in one matrix -- one elimination forest, so the fronts of all of
+    them share the tree levels and the launches."""
+    off, rows, cols, vals, negs = 0, [], [], [], 0
+    for n, r, c, v, neg in systems:
+        rows.append(r - 1 + off); cols.append(c - 1 + off); vals.append(v); negs += neg; off += n
+    return _finish(off, rows, cols, vals) + (negs,)
+
+
 def to_scipy(n, row, col, val):
     """full symmetric scipy CSR matrix of a one-triangle triplet list (duplicates summed)."""
     import scipy.sparse as sp

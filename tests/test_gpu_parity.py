@@ -271,7 +271,7 @@ def test_internal_refinement_improves_an_ill_conditioned_solve():
 def test_optional_code_paths_stay_exact(opts):
     """every non-default analysis / kernel option must give the same inertia and a converged solve"""
     if opts.get("wide_panels"):
-        n, r, c, v, neg = kktgen.grid_kkt(110, 90, dof=3, ncon=2, seed=31)   # separator fronts of ~1 200 rows: 128-column panels kick in
+        n, r, c, v, neg = kktgen.grid_kkt(110, 90, dof=3, ncon=2, seed=31)   # separator fronts of up to 730 rows, supernodes of up to 128 columns (tests/test_reach.py pins both): 128-column panels kick in
     else:
         n, r, c, v, neg = kktgen.grid_kkt(48, 44, dof=3, ncon=2, seed=23)
     K = kktgen.to_scipy(n, r, c, v)
@@ -287,9 +287,13 @@ def test_optional_code_paths_stay_exact(opts):
 def test_lookahead_split_updates_are_exact_and_reproducible(monkeypatch, part1):
     """the two-stream look-ahead of the group-end trailing updates (normally only on very large fronts) forced onto a
     mid-size system: same inertia, converged solve, bitwise identical to the single-stream factorisation -- with part 1 (the first 256
-    columns, on the main stream) in 64 x 64 tiles (k_big_schur_p1, the default where few tiles are in the launch) and in the 128 x 128 ones"""
+    columns, on the main stream) in 64 x 64 tiles (k_big_schur_p1, the default where few tiles are in the launch) and in the 128 x 128 ones.
+    What this fixture runs today (tests/test_reach.py, test_the_110x90_grid_forks_no_look_ahead): the plan marks one update as split, so the
+    factorisation takes the eager multi-stream schedule with its side stream -- but the largest front has 730 rows, and part 1 / part 2 are
+    launched only for fronts above 1024 rows: the split-update kernels themselves are compared in tests/test_gpu_fast_paths.py
+    (lookahead / p1_small on the clique_grid fixture, where two levels fork)."""
     if part1 == "tiles128": monkeypatch.setenv("MI355X_KKT_DISABLE", "p1_small")
-    n, r, c, v, neg = kktgen.grid_kkt(110, 90, dof=3, ncon=2, seed=31)        # fronts up to ~1 200 rows: several split updates
+    n, r, c, v, neg = kktgen.grid_kkt(110, 90, dof=3, ncon=2, seed=31)        # fronts up to 730 rows: one update marked split, none above 1024 rows
     K = kktgen.to_scipy(n, r, c, v)
     b = K @ np.ones(n)
     monkeypatch.setenv("MI355X_KKT_DISABLE", "lookahead")

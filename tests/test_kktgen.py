@@ -24,3 +24,28 @@ def test_synthetic_generator_on_the_xoshiro_stream_has_the_inertia_it_was_built_
     b = K @ np.ones(n)
     x, oneg, ozero, _ = ko.factor_solve(n, r, c, v, b, u=0.01)
     assert oneg == neg and ozero == 0 and np.abs(x - 1).max() <= 1e-6
+
+
+def test_clique_generator_has_the_structure_and_the_inertia_it_was_built_for():
+    """cliques along a path that share `sep` variables, three-variable constraint rows on disjoint supports: inertia (n_x, m, 0) by LAPACK's eigenvalues,
+    with and without shared variables, without constraints, and as a direct sum"""
+    for sizes, sep, m in (([40], 0, 6), ([30, 25, 20], 5, 9), ([35, 35], 0, 0)):
+        n, r, c, v, neg = kktgen.clique_kkt(sizes, sep, m, seed=5)
+        nx = sum(sizes) - sep * (len(sizes) - 1)
+        assert n == nx + m and neg == m
+        K = kktgen.to_scipy(n, r, c, v).toarray()
+        w = np.linalg.eigvalsh(K)
+        assert int((w < 0).sum()) == m and np.abs(w).min() > 1e-8
+        H = K[:nx, :nx] != 0
+        first = 0
+        for s in sizes:                                    # every clique is dense, and nothing couples variables of no common clique
+            assert H[first:first + s, first:first + s].all()
+            first += s - sep
+        assert int(np.tril(H, -1).sum()) == sum(s * (s - 1) // 2 for s in sizes) - (len(sizes) - 1) * sep * (sep - 1) // 2
+        J = K[nx:, :nx] != 0
+        assert np.all(J.sum(axis=1) == 3) and np.all(J.sum(axis=0) <= 1)      # disjoint supports: full row rank whatever the values
+    a, b = kktgen.clique_kkt([20], 0, 3, seed=1), kktgen.grid_kkt(4, 3, dof=2, ncon=1, seed=2)
+    n, r, c, v, neg = kktgen.block_diag(a, b)
+    K = kktgen.to_scipy(n, r, c, v).toarray()
+    assert n == a[0] + b[0] and neg == a[4] + b[4] == int((np.linalg.eigvalsh(K) < 0).sum())
+    assert not K[:a[0], a[0]:].any() and np.array_equal(K[:a[0], :a[0]], kktgen.to_scipy(*a[:4]).toarray())
