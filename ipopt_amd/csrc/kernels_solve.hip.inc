@@ -133,6 +133,201 @@ __global__ __launch_bounds__(NT) void k_bwd(DevView V, int list_off)
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Fronts of order 33..128 on the level launches of the single-GPU schedule (MI355X_KKT_DISABLE=mid_solve: k_fwd / k_bwd above): the arithmetic of
+// k_fwd / k_bwd, entry by entry in the same order (same bits), with the loads batched.  Everything whose address the front record gives -- pivot order,
+// D, the first MID_KB columns of the row of L11^{-1} and of the panel rows a thread owns, the child records -- is requested before anything is waited
+// for, then the children's vectors (forward) / the ancestors' entries (backward), then arithmetic: three dependent memory phases for a front of
+// k <= MID_KB pivots (98 % of them on the tree levels below the chains), one more per further MID_KB columns, instead of one per two to four entries.
+// A guarded entry of a batch is loaded from a clamped address inside the same array and dropped by a select on the RESULT of its fma: no branch and no
+// wait per element, and the accumulator keeps its bits (the sign of a zero included).  ONE WAVEFRONT PER FRONT -- a workgroup of 256 threads per front
+// of order 65..128, as k_fwd<256> has it, was measured slower (1.99 against 1.85 ms per solve of synth_1e6; k_fwd / k_bwd: 2.05) --, MR = rows of the
+// front per lane (1: order <= 64, 2: order <= 128); k <= MID_KMAX (solve_level asks for it: the 128-column panels of the wide_panels option stay with
+// k_fwd / k_bwd).
+// ------------------------------------------------------------------------------------------------
+constexpr int MID_KB = 16, MID_KMAX = 64;      // columns per batch; the pivot count these kernels take (max_sn_cols: a thread owns ONE pivot row / column)
+// batch pb of row j of the inverse (forward: columns p <= j) / of column j (backward: rows j + q), batch jb of panel row i
+__device__ __forceinline__ void mid_ld_mrow(double (&mv)[MID_KB], const double* Mg, const int k, const int j, const int pb)
+{
+#pragma unroll
+    for (int p = 0; p < MID_KB; ++p) { const bool ok = j < k && pb + p <= j; mv[p] = Mg[ok ? j + (size_t)(pb + p) * k : 0]; }
+}
+__device__ __forceinline__ void mid_ld_mcol(double (&mv)[MID_KB], const double* Mg, const int k, const int p, const int qb)
+{
+#pragma unroll
+    for (int q = 0; q < MID_KB; ++q) { const bool ok = p + qb + q < k; mv[q] = Mg[ok ? p + qb + q + (size_t)p * k : 0]; }
+}
+__device__ __forceinline__ void mid_ld_lrow(double (&lv)[MID_KB], const double* Lg, const int k, const int m, const int ldp, const int i, const int jb)
+{
+#pragma unroll
+    for (int p = 0; p < MID_KB; ++p) { const bool ok = i < m && jb + p < k; lv[p] = Lg[ok ? i + (size_t)(jb + p) * ldp : 0]; }
+}
+// a0 += over the even, a1 += over the odd entries q < n of a batch (ascending); x: the LDS vector from the batch's first entry on (readable MID_KB entries past its end)
+__device__ __forceinline__ void mid_acc(const double (&v)[MID_KB], const double* x, const int n, double& a0, double& a1)
+{
+#pragma unroll
+    for (int q = 0; q < MID_KB; q += 2) {
+        const double f0 = fma(v[q], x[q], a0), f1 = fma(v[q + 1], x[q + 1], a1);
+        a0 = q < n ? f0 : a0; a1 = q + 1 < n ? f1 : a1;
+    }
+}
+
+template <int MR>
+__global__ __launch_bounds__(64) void k_fwd_mid(DevView V, int list_off)
+{
+    __shared__ double xp[MID_KMAX], ys[MID_KMAX + MID_KB], bp[MID_KMAX + MID_KB], xu[128];
+    const int tid = threadIdx.x;
+    const FrontMeta M = V.fmeta[list_off + blockIdx.x];
+    const int c0 = M.c0, k = M.k, m = M.m, ldp = M.ldp, ch0 = M.ch0, ch1 = M.ch1;
+    const double* Mg = V.minv + M.minv_off;
+    const double* Lg = V.L + M.panel_off;
+    // ---- phase 1: the front record gives every address.  The child records first (what phase 2 waits for): lane c of every wavefront loads child c's ----
+    const int nch = ch1 - ch0 < 4 ? ch1 - ch0 : 4;
+    int mcl = 0, rbl = 0; long long cbl = 0;
+    if (nch > 0) { const ChildMeta* Cl = V.cmeta + ch0 + ((tid & 3) < nch ? (tid & 3) : nch - 1); mcl = Cl->mc; rbl = Cl->relbase; cbl = Cl->cvbase; }
+    const bool piv = tid < k;
+    const int jc = piv ? tid : 0;
+    const double xwv = V.xw[c0 + jc];
+    const int lpv = V.lperm[c0 + jc];
+    double mrow[MID_KB], lrow[MR][MID_KB];
+    mid_ld_mrow(mrow, Mg, k, tid, 0);
+#pragma unroll
+    for (int r = 0; r < MR; ++r) mid_ld_lrow(lrow[r], Lg, k, m, ldp, k + tid + 64 * r, 0);
+    const int pt = V.ptype[c0 + jc];
+    const double dq = V.dinv[c0 + jc], oq = V.doff[c0 + jc], oq1 = V.doff[c0 + (jc > 0 ? jc - 1 : 0)];
+    // ---- phase 2: the children's contribution vectors (the first four children's in one batch) ----
+    int tg[4][MR]; double cv[4][MR];
+    if (nch > 0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {      // (lanes c >= nch hold the last child's record again: valid addresses, no entry taken)
+            const int mc = c < nch ? __builtin_amdgcn_readlane(mcl, c) : 0, rb = __builtin_amdgcn_readlane(rbl, c);
+            const long long cb = ((long long)__builtin_amdgcn_readlane((int)(cbl >> 32), c) << 32) | (unsigned)__builtin_amdgcn_readlane((int)cbl, c);
+#pragma unroll
+            for (int r = 0; r < MR; ++r) {
+                const int t = tid + 64 * r; const bool on = t < mc;
+                const int g = V.rel[rb + (on ? t : 0)]; cv[c][r] = V.cvec[cb + (on ? t : 0)];
+                tg[c][r] = on ? g : -1;
+            }
+        }
+    }
+    // ---- phase 3: arithmetic ----
+    if (piv) xp[tid] = xwv;
+    for (int i = k + tid; i < m; i += 64) xu[i - k] = 0.0;
+    __syncthreads();
+    if (nch > 0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+#pragma unroll
+            for (int r = 0; r < MR; ++r) { const int g = tg[c][r]; if (g >= 0) { if (g < k) xp[g] += cv[c][r]; else xu[g - k] += cv[c][r]; } }
+            __syncthreads();
+        }
+        for (int cp = ch0 + 4; cp < ch1; ++cp) {                 // (more than four children: rare)
+            const ChildMeta Cm = V.cmeta[cp];
+            for (int t = tid; t < Cm.mc; t += 64) {
+                const int g = V.rel[Cm.relbase + t]; const double v = V.cvec[Cm.cvbase + t];
+                if (g < k) xp[g] += v; else xu[g - k] += v;
+            }
+            __syncthreads();
+        }
+    }
+    if (piv) bp[tid] = xp[lpv];
+    __syncthreads();
+    {   // y = Minv * (P b): thread j walks row j of the column-major inverse, even and odd columns p <= j apart
+        double a0 = 0.0, a1 = 0.0;
+        mid_acc(mrow, bp, tid + 1, a0, a1);
+        for (int pb = MID_KB; pb < k; pb += MID_KB) { double mv[MID_KB]; mid_ld_mrow(mv, Mg, k, tid, pb); mid_acc(mv, bp + pb, tid + 1 - pb, a0, a1); }
+        if (piv) ys[tid] = a0 + a1;
+    }
+    __syncthreads();
+    {   // c = (children) - L21 y: a thread's rows, even and odd columns apart
+        double t0[MR], t1[MR];
+#pragma unroll
+        for (int r = 0; r < MR; ++r) { t0[r] = 0.0; t1[r] = 0.0; mid_acc(lrow[r], ys, k, t0[r], t1[r]); }
+        for (int jb = MID_KB; jb < k; jb += MID_KB) {
+            double lv[MR][MID_KB];
+#pragma unroll
+            for (int r = 0; r < MR; ++r) mid_ld_lrow(lv[r], Lg, k, m, ldp, k + tid + 64 * r, jb);
+#pragma unroll
+            for (int r = 0; r < MR; ++r) mid_acc(lv[r], ys + jb, k - jb, t0[r], t1[r]);
+        }
+#pragma unroll
+        for (int r = 0; r < MR; ++r) { const int i = k + tid + 64 * r; if (i < m) V.cvec[M.cv + i] = xu[i - k] - (t0[r] + t1[r]); }
+    }
+    if (piv) {
+        const int j = tid;
+        double z;
+        if (pt == 1) z = ys[j] * dq;
+        else if (pt == 2) z = dq * ys[j] + oq * ys[j + 1];
+        else z = oq1 * ys[j - 1] + dq * ys[j];
+        V.zb[c0 + j] = z;
+    }
+}
+
+// backward: MID_KB columns per batch, rows lane and lane + 64 (MR = 2) of each per lane
+template <int MR>
+__global__ __launch_bounds__(64) void k_bwd_mid(DevView V, int list_off)
+{
+    __shared__ double ws[MID_KMAX + MID_KB], xu[128];
+    const int tid = threadIdx.x, lane = tid;
+    const FrontMeta M = V.fmeta[list_off + blockIdx.x];
+    const int c0 = M.c0, k = M.k, r0 = M.r0, m = M.m, ldp = M.ldp, nu = m - k;
+    const double* Mg = V.minv + M.minv_off;
+    const double* Lg = V.L + M.panel_off;
+    // ---- phase 1 ----
+    int ridx[MR];
+#pragma unroll
+    for (int r = 0; r < MR; ++r) { const int i = lane + 64 * r; ridx[r] = V.sn_rows[r0 + (i < nu ? k + i : 0)]; }
+    const bool piv = tid < k;
+    const int jc = piv ? tid : 0;
+    const double zbv = V.zb[c0 + jc];
+    double lcol[MID_KB][MR];
+#pragma unroll
+    for (int q = 0; q < MID_KB; ++q)
+#pragma unroll
+        for (int r = 0; r < MR; ++r) { const int j = q, i = lane + 64 * r; const bool ok = j < k && i < nu; lcol[q][r] = Lg[ok ? k + i + (size_t)j * ldp : 0]; }
+    double mcol[MID_KB];
+    mid_ld_mcol(mcol, Mg, k, tid, 0);
+    const int lpv = V.lperm[c0 + jc];
+    // ---- phase 2: the ancestors' solution entries (the fence keeps the scheduler from drawing the gather, and its wait, in front of the batch) ----
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int r = 0; r < MR; ++r) xu[lane + 64 * r] = V.xw[ridx[r]];      // (unconditional: rows >= nu hold the front's first row again and are never read)
+    // ---- phase 3 ----
+    ws[piv ? tid : MID_KMAX + MID_KB - 1] = zbv;      // (unconditional: a store under `piv` draws the load into the branch, behind the gather)
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < MID_KB; ++q) {
+        const int j = q;
+        double t = 0.0;
+#pragma unroll
+        for (int r = 0; r < MR; ++r) { const int i = lane + 64 * r; const double f = fma(lcol[q][r], xu[i], t); t = i < nu ? f : t; }
+        t = wave_sum(t);
+        if (lane == 0 && j < k) ws[j] -= t;
+    }
+    for (int jb = MID_KB; jb < k; jb += MID_KB) {
+        double lv[MID_KB][MR];
+#pragma unroll
+        for (int q = 0; q < MID_KB; ++q)
+#pragma unroll
+            for (int r = 0; r < MR; ++r) { const int j = jb + q, i = lane + 64 * r; const bool ok = j < k && i < nu; lv[q][r] = Lg[ok ? k + i + (size_t)j * ldp : 0]; }
+#pragma unroll
+        for (int q = 0; q < MID_KB; ++q) {
+            const int j = jb + q;
+            double t = 0.0;
+#pragma unroll
+            for (int r = 0; r < MR; ++r) { const int i = lane + 64 * r; const double f = fma(lv[q][r], xu[i], t); t = i < nu ? f : t; }
+            t = wave_sum(t);
+            if (lane == 0 && j < k) ws[j] -= t;
+        }
+    }
+    __syncthreads();
+    {   // x_p = sum_{j >= p} Minv(j,p) w_j: thread p walks its own column of the inverse, rows p, p + 2, ... and p + 1, p + 3, ... apart
+        double a0 = 0.0, a1 = 0.0;
+        mid_acc(mcol, ws + jc, k - tid, a0, a1);
+        for (int qb = MID_KB; qb < k; qb += MID_KB) { double mv[MID_KB]; mid_ld_mcol(mv, Mg, k, tid, qb); mid_acc(mv, ws + (piv ? tid + qb < k ? tid + qb : 0 : 0), k - tid - qb, a0, a1); }
+        if (piv) V.xw[c0 + lpv] = a0 + a1;
+    }
+}
 
 
 // ------------------------------------------------------------------------------------------------

@@ -1002,9 +1002,10 @@ public:
 
     // ---- the solve walkers: solve_level holds the only copy of the per-class launch choice, solve_sweep the chain segments, the gate of the solve
     //      contexts and the leaf chains.  What the single-GPU schedule alone takes is a condition on `single` here ----
+    const bool mid_on = !knob_disabled("mid_solve");      // fronts of order 33..128 on the level launches: k_fwd_mid / k_bwd_mid (off: k_fwd / k_bwd)
     static size_t lds_solve(int mmax, int kmax) { return (size_t)(mmax + 3 * kmax) * sizeof(double) + 16; }
     void solve_level(const Sched& sc, int lv, bool forward, int top_mode) {
-        const bool single = is_single(sc), pair = single && P.pair_solve;
+        const bool single = is_single(sc), pair = single && P.pair_solve, mid = single && !top_mode && mid_on && S->maxsupernode <= MID_KMAX;      // mid: load-batched kernels for the fronts of order 33..128
         for (int fc = 0; fc < FC_COUNT; ++fc) {
             const int b0 = bucket0(sc, lv, fc), nb = bucket0(sc, lv, fc + 1) - b0;
             if (nb == 0) continue;
@@ -1014,6 +1015,8 @@ public:
                 else if (fc == FC_WAVE && pair && P.wave_kmax[lv] <= 16) LAUNCH(KK_FWD_WAVE, (k_fwd_pair<16>), dim3((nb + 1) / 2), dim3(64), 0, stream, V, b0, nb);
                 else if (fc == FC_WAVE && pair) LAUNCH(KK_FWD_WAVE, (k_fwd_pair<32>), dim3((nb + 1) / 2), dim3(64), 0, stream, V, b0, nb);
                 else if (fc == FC_WAVE)   LAUNCH(KK_FWD_WAVE, (k_fwd<64>),  dim3(nb), dim3(64),  lds_solve(32, 32),   stream, V, b0, top_mode);
+                else if (fc == FC_LDS64 && mid)  LAUNCH(KK_FWD_LDS,  (k_fwd_mid<1>), dim3(nb), dim3(64), 0, stream, V, b0);
+                else if (fc == FC_LDS128 && mid) LAUNCH(KK_FWD_LDS,  (k_fwd_mid<2>), dim3(nb), dim3(64), 0, stream, V, b0);
                 else if (fc == FC_LDS64)  LAUNCH(KK_FWD_LDS,  (k_fwd<64>),  dim3(nb), dim3(64),  lds_solve(64, 64),   stream, V, b0, top_mode);
                 else if (fc == FC_LDS128) LAUNCH(KK_FWD_LDS,  (k_fwd<256>), dim3(nb), dim3(256), lds_solve(128, 128), stream, V, b0, top_mode);
                 else if (ng <= 0) continue;
@@ -1026,6 +1029,8 @@ public:
                 else if (fc == FC_WAVE && pair && P.wave_kmax[lv] <= 16) LAUNCH(KK_BWD_WAVE, (k_bwd_pair<16>), dim3((nb + 1) / 2), dim3(64), 0, stream, V, b0, nb);
                 else if (fc == FC_WAVE && pair) LAUNCH(KK_BWD_WAVE, (k_bwd_pair<32>), dim3((nb + 1) / 2), dim3(64), 0, stream, V, b0, nb);
                 else if (fc == FC_WAVE)   LAUNCH(KK_BWD_WAVE, (k_bwd<64>),  dim3(nb), dim3(64),  lds_solve(32, 32),   stream, V, b0);
+                else if (fc == FC_LDS64 && mid)  LAUNCH(KK_BWD_LDS,  (k_bwd_mid<1>), dim3(nb), dim3(64), 0, stream, V, b0);
+                else if (fc == FC_LDS128 && mid) LAUNCH(KK_BWD_LDS,  (k_bwd_mid<2>), dim3(nb), dim3(64), 0, stream, V, b0);
                 else if (fc == FC_LDS64)  LAUNCH(KK_BWD_LDS,  (k_bwd<64>),  dim3(nb), dim3(64),  lds_solve(64, 64),   stream, V, b0);
                 else if (fc == FC_LDS128) LAUNCH(KK_BWD_LDS,  (k_bwd<256>), dim3(nb), dim3(256), lds_solve(128, 128), stream, V, b0);
                 else if (ng <= 0) continue;
