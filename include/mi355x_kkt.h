@@ -275,6 +275,37 @@ int  mi355x_kkt_lbfgs_info(mi355x_kkt_handle h, int* rows, int* max_history, int
 int  mi355x_kkt_lbfgs_get(mi355x_kkt_handle h, int what, double* out, int64_t capacity);
 int  mi355x_kkt_lbfgs_coefficients(int m, const double* sts, const double* L, const double* D, double sigma, double* C_out, double* Lbar_out);
 
+/* ---- limited-memory SR1: the same history, V and U from an eigen-split; one stored push can be taken back ---------------------------------------
+ * `limited_memory_update_type sr1` of the same updater (IpLimMemQuasiNewtonUpdater.cpp :523-671, SplitEigenvalues :873-983).  A history defined by
+ * _lbfgs_define_sr1 (the arguments of _lbfgs_define without the two clips) is served by the SAME _lbfgs_push / _push_device / _reset / _clear /
+ * _info / _get; a push then works like this, D, L, S^T S being those of the BFGS history (same augment / shift):
+ *   skip    no curvature test: only a non-finite s^T s, s^T y or y^T y, or the eigenvalue rule below
+ *   sigma   (:551-578)  the new pair is the only stored one: init_val; otherwise with t = max(1e-8, |s^T y|): scalar1 t / s^T s, scalar2 y^T y / t,
+ *           scalar3 / scalar4 their arithmetic / geometric mean, constant init_val.  NOT clipped.
+ *   split   Z = D + L + L^T - sigma S^T S = Q diag(E) Q^T, E ascending, nneg of them < 0; emax = max(|E_0|, |E_(m-1)|), emin the |E_j| next to the
+ *           sign change (E_0, -E_(m-1) or min(-E_(nneg-1), E_nneg)); the push is SKIPPED when emax = 0 or emin / emax < 1e-12 (:890-928)
+ *   columns W = Y - sigma S, Qs[:, j] = Q[:, j] / sqrt(|E_j|):  U = W Qs[:, :nneg] (nu = nneg columns), V = W Qs[:, nneg:] (nv = memory - nneg):
+ *           sigma I + V V^T - U U^T = sigma I + W Z^-1 W^T is the SR1 matrix of the stored pairs started from sigma I
+ * Outcomes are 0 (stored, V and U installed as _lowrank_set(rows, nv, V, rows, nu, U, rows) would) and 1 (skipped) only.  A skipped push changes
+ * NOTHING but skipped_in_a_row: the pair is committed only after the split rule has passed (the reference restores its backup, :624-628).
+ * The split nv + nu = memory moves from push to push: the update's buffers get room for max_history columns on each side, so a push allocates nothing.
+ *   _lbfgs_undo   SR1 only (a BFGS history: FATAL).  Takes the last stored push back (the reference's "Undoing most recent SR1 update", :523-532):
+ *                 pairs -- the evicted one included --, D, L, S^T S, sigma and the split are those before that push, V and U are formed again from
+ *                 them (bitwise what that earlier push installed; memory 0: the update is removed) and are not current; skipped_in_a_row is its
+ *                 value before the undone push plus one; *undone (may be NULL) = 1.  One level: after a skipped push, an undo, _reset, _define*,
+ *                 _clear there is nothing to undo and the call succeeds with *undone = 0, nothing changed.
+ *   _lbfgs_sr1_info  outputs may be NULL; type 0 BFGS / 1 SR1; nneg, E (the `memory` eigenvalues of the installed split, ascending; FATAL when
+ *                 `capacity` is below memory) and can_undo are 0 / untouched for a BFGS history
+ *   _lbfgs_sr1_coefficients  stand-alone, HOST, no handle, no GPU: E (m), Qs (m x m, column-major) and nneg from S^T S, L, D and sigma; SUCCESS,
+ *                 SINGULAR (the split rule says skip: E and nneg are set, Qs is not scaled), FATAL (m outside [0, 32], a null array, or the cyclic
+ *                 Jacobi eigen-solver did not converge within its 30 sweeps) */
+#define MI355X_KKT_LBFGS_BFGS 0
+#define MI355X_KKT_LBFGS_SR1  1
+int  mi355x_kkt_lbfgs_define_sr1(mi355x_kkt_handle h, int rows, int max_history, int init, double init_val);
+int  mi355x_kkt_lbfgs_undo(mi355x_kkt_handle h, int* undone);
+int  mi355x_kkt_lbfgs_sr1_info(mi355x_kkt_handle h, int* type, int* nneg, int* can_undo, double* E, int capacity);
+int  mi355x_kkt_lbfgs_sr1_coefficients(int m, const double* sts, const double* L, const double* D, double sigma, double* E_out, double* Qs_out, int* nneg_out);
+
 int  mi355x_kkt_set_pivtol(mi355x_kkt_handle h, double u);
 int  mi355x_kkt_set_pivtolmax(mi355x_kkt_handle h, double umax);
 /* IncreaseQuality (IpSparseSymLinearSolverInterface.hpp:220): raises u <- min(pivtolmax, u^0.75) (the rule of

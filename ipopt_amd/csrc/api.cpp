@@ -550,6 +550,57 @@ int mi355x_kkt_lbfgs_coefficients(int m, const double* sts, const double* L, con
     if (m < 0 || m > MI355X_KKT_LBFGS_MAX || (m > 0 && (!sts || !L || !D || !C_out || !Lbar_out))) return MI355X_KKT_FATAL;
     return mi355x::lb_coefficients(m, sts, L, m, D, sigma, nullptr, C_out, Lbar_out, m) ? MI355X_KKT_SUCCESS : MI355X_KKT_SINGULAR;
 }
+// ---- limited-memory SR1: the same history, V and U from the eigen-split of Z; one stored push can be taken back ----
+int mi355x_kkt_lbfgs_define_sr1(mi355x_kkt_handle h, int rows, int max_history, int init, double init_val)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "lbfgs_define_sr1";
+    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
+    if (rows < 1 || rows > h->sym.n) LR_FAIL("rows must be in [1, n]");
+    if (max_history < 1 || max_history > MI355X_KKT_LBFGS_MAX) LR_FAIL("max_history must be in [1, 32]");
+    if (init < 0 || init > 4) LR_FAIL("init must be in [0, 4] (scalar1..4, constant)");
+    if (!(init_val > 0.0) || !std::isfinite(init_val)) LR_FAIL("init_val must be positive and finite");
+    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
+    try { if (!h->num->lbfgs_define_sr1(rows, max_history, init, init_val)) { h->err = h->num->error(); return MI355X_KKT_FATAL; } return MI355X_KKT_SUCCESS; }
+    catch (...) { h->err = "lbfgs_define_sr1: unexpected exception"; return MI355X_KKT_FATAL; }
+}
+int mi355x_kkt_lbfgs_undo(mi355x_kkt_handle h, int* undone)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "lbfgs_undo";
+    if (undone) *undone = 0;
+    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
+    try {
+        int u = 0;
+        if (!h->num->lbfgs_undo(&u)) { h->err = h->num->error(); return MI355X_KKT_FATAL; }
+        if (undone) *undone = u;
+        return MI355X_KKT_SUCCESS;
+    } catch (...) { h->err = "lbfgs_undo: unexpected exception"; return MI355X_KKT_FATAL; }
+}
+int mi355x_kkt_lbfgs_sr1_info(mi355x_kkt_handle h, int* type, int* nneg, int* can_undo, double* E, int capacity)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "lbfgs_sr1_info";
+    if (type) *type = 0; if (nneg) *nneg = 0; if (can_undo) *can_undo = 0;
+    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
+    if (capacity < 0) LR_FAIL("capacity must be >= 0");
+    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
+    int t = 0, memory = 0;
+    h->num->lbfgs_sr1_info(&t, nullptr, nullptr, nullptr);
+    h->num->lbfgs_info(nullptr, nullptr, &memory, nullptr, nullptr, nullptr);
+    if (E && t == 1 && capacity < memory) LR_FAIL("capacity is below the " + std::to_string(memory) + " eigenvalues of the installed split");
+    h->num->lbfgs_sr1_info(type, nneg, can_undo, E);
+    return MI355X_KKT_SUCCESS;
+}
+// host only, no handle, no device: the eigen-split of an SR1 push (lbfgs_host.h), m x m column-major with leading dimension m
+int mi355x_kkt_lbfgs_sr1_coefficients(int m, const double* sts, const double* L, const double* D, double sigma, double* E_out, double* Qs_out, int* nneg_out)
+{
+    if (m < 0 || m > MI355X_KKT_LBFGS_MAX || (m > 0 && (!sts || !L || !D || !E_out || !Qs_out))) return MI355X_KKT_FATAL;
+    int nneg = 0;
+    const int r = mi355x::lb_sr1_coefficients(m, sts, L, m, D, sigma, E_out, Qs_out, m, &nneg);
+    if (nneg_out) *nneg_out = nneg;
+    return r == mi355x::LB_SR1_OK ? MI355X_KKT_SUCCESS : r == mi355x::LB_SR1_SKIP ? MI355X_KKT_SINGULAR : MI355X_KKT_FATAL;
+}
 #undef LR_FAIL
 
 int mi355x_kkt_solve(mi355x_kkt_handle h, int nrhs, double* rhs, int ld)

@@ -3,11 +3,13 @@
 // CheckSkippingBFGS :985-1019, the columns V and U :440-520; restated in DESIGN.md).  The history S, Y (rows x max_history each, leading dimension
 // `ld`) is a RING of column slots: the kernels get the logical -> physical slot map by value, so dropping the oldest pair copies nothing.
 // ================================================================================================
-// Two kernels, both streaming (1/4 flop per byte in the dots, m / 16 -- 2 at m = 32 -- in the form: HBM is the ruler, fp64 MFMA buys nothing):
+// Three kernels, all streaming (1/4 flop per byte in the dots, m / 16 -- 2 at m = 32 -- in the form: HBM is the ruler, fp64 MFMA buys nothing):
 //   k_lb_dots   per slab of LR_SLAB rows the partials of  s^T S_j, s^T Y_j (j over the m live pairs, oldest first),  s^T s, s^T y, y^T y:
 //               2 m + 3 numbers per slab, summed over the slabs by k_lr_reduce (kernels_lowrank.hip.inc) in its fixed order
 //   k_lb_form   writes the new pair into its slot and forms  V = Y diag(d),  U = sigma S C + V Lbar  in one pass, one thread per row, the small
 //               matrices (d, C, Lbar: lbfgs_host.h) in LDS
+//   k_lb_form_sr1  its SR1 sibling (reference :630-669):  W = Y - sigma S,  U = W Qs[:, :nneg],  V = W Qs[:, nneg:]  with the scaled eigenvectors Qs of
+//               Z = D + L + L^T - sigma S^T S (lb_sr1_coefficients, lbfgs_host.h) in LDS; 2 m^2 flop per row over 8 (3 m + 2) bytes: streaming as well
 // No atomics; every sum has an order fixed by (rows, m) -- dots: a thread's four rows of the slab in ascending order, the 64 lanes of a wavefront by
 // the xor butterfly 32, 16, 8, 4, 2, 1, the four wavefronts in ascending order, then k_lr_reduce's order over the slabs; form: k ascending in each sum.
 // KP = the compile-time bound on m the loops are unrolled to (8 / 16 / 32: arrays indexed at compile time stay in registers).
@@ -98,5 +100,43 @@ __global__ __launch_bounds__(256) void k_lb_form(double* S, double* Y, long long
 #pragma unroll
             for (int k = 0; k < j; ++k) b = fma(vv[k], sL[k + j * KP], b);
             U[i + j * ldv] = fma(sigma, a, b);
+        }
+}
+
+// coef (device): Qs, LB_MAX x LB_MAX column-major (rows and columns >= m are zero).  ring.m = m live columns.  s != nullptr: the NEW pair is logical
+// column m - 1, read from s, y and written to its slot of S, Y;  s == nullptr: every column is read from its slot and S, Y are only read (the
+// re-form of an undo).  Per row i, w_k = fma(-sigma, S[i, k], Y[i, k]) and for every column c < m
+//   out = sum_{k < m} w_k Qs[k, c]   (k ascending, an fma chain from 0)   ->   U[i, c] when c < nneg,  V[i, c - nneg] otherwise
+// so V has m - nneg and U has nneg columns of leading dimension ldv: the caller sizes them so BEFORE the launch.
+template <int KP>
+__global__ __launch_bounds__(256) void k_lb_form_sr1(double* S, double* Y, long long ld, const double* __restrict__ s, const double* __restrict__ y, int rows,
+                                                     LbRing ring, const double* __restrict__ coef, double sigma, int nneg, double* __restrict__ V, double* __restrict__ U, long long ldv)
+{
+    __shared__ double sQ[KP * KP];
+    const int m = ring.m;
+    for (int e = threadIdx.x; e < KP * KP; e += 256) sQ[e] = coef[e % KP + (e / KP) * LB_MAX];
+    __syncthreads();
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows) return;
+    double w[KP];
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+        w[k] = 0.0;
+        if (k < m) {                                                   // (uniform)
+            const long long c = (long long)ring.slot[k] * ld + i;
+            double sv, yv;
+            if (s != nullptr && k == m - 1) { sv = s[i]; yv = y[i]; S[c] = sv; Y[c] = yv; }
+            else { sv = S[c]; yv = Y[c]; }
+            w[k] = fma(-sigma, sv, yv);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < KP; ++c)
+        if (c < m) {
+            double a = 0.0;
+#pragma unroll
+            for (int k = 0; k < KP; ++k)
+                if (k < m) a = fma(w[k], sQ[k + c * KP], a);
+            if (c < nneg) U[i + c * ldv] = a; else V[i + (c - nneg) * ldv] = a;
         }
 }

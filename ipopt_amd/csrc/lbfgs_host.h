@@ -1,7 +1,8 @@
 // lbfgs_host.h -- the small dense algebra of the limited-memory BFGS updater (numeric.hip lbfgs_push and the stand-alone
 // mi355x_kkt_lbfgs_coefficients share it; reference IpLimMemQuasiNewtonUpdater.cpp: CheckSkippingBFGS :985-1019, sigma :405-432,
 // UpdateInternalData :769-818, the columns :440-520): plain host loops with a fixed order, column-major with an explicit leading
-// dimension, at most 32 pairs.  No HIP in here: a stand-alone host program can include it.
+// dimension, at most 32 pairs.  No HIP in here: a stand-alone host program can include it.  Behind the BFGS part, the SR1 update of the same
+// updater (:523-671, SplitEigenvalues :873-983): sigma, a cyclic Jacobi eigen-solver and the split of Z = D + L + L^T - sigma S^T S.
 #pragma once
 #include <cmath>
 #include <limits>
@@ -92,6 +93,103 @@ inline bool lb_coefficients(int m, const double* sts, const double* L, int ldi, 
             Lbar[i + j * ldo] = s;
         }
     return true;
+}
+
+// ---- limited-memory SR1 (reference :523-671, SplitEigenvalues :873-983) ----
+// sigma of B0 = sigma I for an SR1 push, m_after = the pairs stored once the new one is in: the only pair -> init_val; otherwise the BFGS formulas with
+// t = max(1e-8, |s^T y|) in the place of s^T y.  Not clipped (the reference does not clip here).
+inline double lb_sr1_sigma(int init, double init_val, int m_after, double ss, double sy, double yy)
+{
+    if (m_after <= 1) return init_val;
+    const double t = std::fmax(1e-8, std::fabs(sy));
+    switch (init) {
+    case 0: return t / ss;
+    case 1: return yy / t;
+    case 2: return (t / ss + yy / t) / 2.0;
+    case 3: return std::sqrt((t / ss) * (yy / t));
+    default: return init_val;
+    }
+}
+
+static constexpr int LBH_JACOBI_SWEEPS = 30;
+
+// Cyclic Jacobi for the symmetric m x m A (column-major, leading dimension m, both triangles kept; destroyed): A = Q diag(E) Q^T, E ascending (ties by
+// the index the value had on the diagonal), Q's columns (leading dimension ldq) in E's order.  A sweep visits (p, q), p < q, by rows.
+//   skip    the rotation of (p, q) is skipped when  |a_pq| <= u min(|a_pp|, |a_qq|)  or  |a_pq| <= u^2 |A|_F,  u = 2^-53, |A|_F of the matrix given
+//   rotate  theta = (a_qq - a_pp) / (2 a_pq),  t = sign(theta) / (|theta| + sqrt(theta^2 + 1)),  c = 1 / sqrt(t^2 + 1),  s = t c
+//   stop    after the first sweep that rotated nothing; false when LBH_JACOBI_SWEEPS sweeps all rotated something (a NaN ends here as well)
+inline bool lb_jacobi(int m, double* A, double* E, double* Q, int ldq)
+{
+    const double u = std::ldexp(1.0, -53);
+    double fro = 0.0;
+    for (int j = 0; j < m; ++j)
+        for (int i = 0; i < m; ++i) { fro += A[i + j * m] * A[i + j * m]; Q[i + j * ldq] = i == j ? 1.0 : 0.0; }
+    const double floor_ = u * u * std::sqrt(fro);
+    bool converged = false;
+    for (int sweep = 0; sweep < LBH_JACOBI_SWEEPS && !converged; ++sweep) {
+        int rotated = 0;
+        for (int p = 0; p + 1 < m; ++p)
+            for (int q = p + 1; q < m; ++q) {
+                const double apq = A[p + q * m], app = A[p + p * m], aqq = A[q + q * m], g = std::fabs(apq);
+                if (g <= u * std::fmin(std::fabs(app), std::fabs(aqq)) || g <= floor_) continue;
+                ++rotated;
+                const double theta = (aqq - app) / (2.0 * apq);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+                A[p + p * m] = app - t * apq; A[q + q * m] = aqq + t * apq; A[p + q * m] = A[q + p * m] = 0.0;
+                for (int k = 0; k < m; ++k) {
+                    if (k != p && k != q) {
+                        const double akp = A[k + p * m], akq = A[k + q * m];
+                        A[k + p * m] = A[p + k * m] = c * akp - s * akq;
+                        A[k + q * m] = A[q + k * m] = s * akp + c * akq;
+                    }
+                    const double qkp = Q[k + p * ldq], qkq = Q[k + q * ldq];
+                    Q[k + p * ldq] = c * qkp - s * qkq;
+                    Q[k + q * ldq] = s * qkp + c * qkq;
+                }
+            }
+        converged = rotated == 0;
+    }
+    if (!converged) return false;
+    int idx[LBH_MAX]; double col[LBH_MAX * LBH_MAX];
+    for (int j = 0; j < m; ++j) {                                      // insertion sort of the indices: stable, so ties keep their index order
+        int k = j;
+        while (k > 0 && A[idx[k - 1] + idx[k - 1] * m] > A[j + j * m]) { idx[k] = idx[k - 1]; --k; }
+        idx[k] = j;
+    }
+    for (int j = 0; j < m; ++j) { E[j] = A[idx[j] + idx[j] * m]; for (int i = 0; i < m; ++i) col[i + j * m] = Q[i + idx[j] * ldq]; }
+    for (int j = 0; j < m; ++j) for (int i = 0; i < m; ++i) Q[i + j * ldq] = col[i + j * m];
+    return true;
+}
+
+enum { LB_SR1_OK = 0, LB_SR1_SKIP = 1, LB_SR1_FAILED = 2 };
+
+// Z = D + L + L^T - sigma sym(S^T S) = Q diag(E) Q^T (E ascending, *nneg of them < 0);  Qs[:, j] = Q[:, j] / sqrt(|E_j|):  with W = Y - sigma S,
+// U = W Qs[:, :nneg], V = W Qs[:, nneg:],  sigma I + V V^T - U U^T = sigma I + W Z^-1 W^T  is the SR1 matrix of the pairs started from sigma I.
+// sts, L leading dimension ld; Qs leading dimension ldo.  LB_SR1_SKIP: emax = max(|E_0|, |E_(m-1)|) is 0, or emin / emax < 1e-12 with emin the
+// |E_j| next to the sign change (E_0, -E_(m-1), or min(-E_(nneg-1), E_nneg)): E is set, Qs is not.  LB_SR1_FAILED: the eigen-solver ran out of sweeps.
+inline int lb_sr1_coefficients(int m, const double* sts, const double* L, int ld, const double* D, double sigma, double* E, double* Qs, int ldo, int* nneg)
+{
+    double Z[LBH_MAX * LBH_MAX];
+    *nneg = 0;
+    if (m == 0) return LB_SR1_OK;
+    for (int j = 0; j < m; ++j) {
+        Z[j + j * m] = D[j] - sigma * sts[j + j * ld];
+        for (int i = j + 1; i < m; ++i) Z[i + j * m] = Z[j + i * m] = L[i + j * ld] - sigma * (0.5 * (sts[i + j * ld] + sts[j + i * ld]));
+    }
+    if (!lb_jacobi(m, Z, E, Qs, ldo)) return LB_SR1_FAILED;
+    int nn = 0;
+    for (int j = 0; j < m; ++j) if (E[j] < 0.0) ++nn;
+    *nneg = nn;
+    const double emax = std::fmax(std::fabs(E[0]), std::fabs(E[m - 1]));
+    if (emax == 0.0) return LB_SR1_SKIP;
+    const double emin = nn == 0 ? E[0] : nn == m ? -E[m - 1] : std::fmin(-E[nn - 1], E[nn]);
+    if (emin / emax < 1e-12) return LB_SR1_SKIP;
+    for (int j = 0; j < m; ++j) {
+        const double r = std::sqrt(std::fabs(E[j]));
+        for (int i = 0; i < m; ++i) Qs[i + j * ldo] = Qs[i + j * ldo] / r;
+    }
+    return LB_SR1_OK;
 }
 
 } // namespace mi355x

@@ -103,6 +103,12 @@ public:
     bool   lbfgs_clear();
     void   lbfgs_info(int* rows, int* max_history, int* memory, double* sigma, int* skipped_in_a_row, double* push_ms) const;
     bool   lbfgs_get(int what, double* out, long long capacity);
+    // limited-memory SR1 (the same file, case SR1): a history defined here answers a push with 0 or 1 only (V: memory - nneg columns, U: nneg, from
+    // the eigen-split of Z = D + L + L^T - sigma S^T S) and can take its last stored push back once (lbfgs_undo; a BFGS history refuses).
+    // lbfgs_sr1_info: E receives the `memory` eigenvalues of the installed split, ascending (the caller checks the capacity).
+    bool   lbfgs_define_sr1(int rows, int max_history, int init, double init_val);
+    bool   lbfgs_undo(int* undone);
+    void   lbfgs_sr1_info(int* type, int* nneg, int* can_undo, double* E) const;
     long long factor_count() const;                  // bumped by every factorisation (the refactorisations of a delayed-pivot loop included) and every structure edit
     // communicator of a multi-GPU handle: with one set, factor()/solve_*() run the whole distributed sequence themselves
     bool   set_comm_rccl(const void* unique_id128);                                   // RCCL (dlopen'ed), ncclCommInitRank(nranks, id, rank)

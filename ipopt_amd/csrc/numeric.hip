@@ -1388,7 +1388,7 @@ public:
     // factor_count -- bumped by every factorisation and every structure edit -- is the one lowrank_update saw.
     long long factor_count = 0;
     bool lr_set = false, lr_ok = false; long long lr_at = -1;
-    int lr_rows = 0, lr_nv = 0, lr_nu = 0; double lr_update_ms = 0;
+    int lr_rows = 0, lr_nv = 0, lr_nu = 0, lr_capv = 0, lr_capu = 0; double lr_update_ms = 0;      // lr_cap*: the columns the buffers were allocated for (>= lr_nv, lr_nu)
     double *lr_V = nullptr, *lr_U = nullptr, *lr_Z1 = nullptr, *lr_Z2 = nullptr, *lr_part = nullptr, *lr_T = nullptr, *lr_L1 = nullptr, *lr_L2 = nullptr, *lr_h = nullptr;
     int lr_nslab() const { return std::max(1, (lr_rows + LR_SLAB - 1) / LR_SLAB); }
     bool lr_current() const { return lr_set && lr_ok && lr_at == factor_count; }
@@ -1402,16 +1402,19 @@ public:
         if (lr_rows <= pd_.nx) return true;
         err_ = std::string(who) + ": the low-rank update acts on more rows than the x block has (rows <= n_x)"; return false;
     }
-    void lowrank_clear() { own_lr.clear(); lr_set = lr_ok = false; lr_at = -1; lr_rows = lr_nv = lr_nu = 0; lr_update_ms = 0; lr_V = lr_U = lr_Z1 = lr_Z2 = lr_part = lr_T = lr_L1 = lr_L2 = lr_h = nullptr; }
+    void lowrank_clear() { own_lr.clear(); lr_set = lr_ok = false; lr_at = -1; lr_rows = lr_nv = lr_nu = lr_capv = lr_capu = 0; lr_update_ms = 0; lr_V = lr_U = lr_Z1 = lr_Z2 = lr_part = lr_T = lr_L1 = lr_L2 = lr_h = nullptr; }
     // the buffers of an update of the shape (rows, nv, nu), set and not current: those in place when that is the installed shape (nothing is
     // allocated: an L-BFGS push with a full history installs its columns into them), fresh ones otherwise.  Nothing may be in flight on them.
-    bool lr_shape(int rows, int nv, int nu) {
-        if (lr_set && rows == lr_rows && nv == lr_nv && nu == lr_nu) { lr_ok = false; lr_at = -1; lr_update_ms = 0; return true; }
+    // cap > 0 (an SR1 push, whose split nv + nu = m moves from push to push): fresh buffers get room for max(nv, cap) and max(nu, cap) columns, and
+    // buffers in place are kept whenever they have room for nv and nu columns -- then a push allocates nothing although the shape changes.
+    bool lr_shape(int rows, int nv, int nu, int cap = 0) {
+        const bool fits = cap > 0 ? nv <= lr_capv && nu <= lr_capu : nv == lr_nv && nu == lr_nu;
+        if (lr_set && rows == lr_rows && fits) { lr_nv = nv; lr_nu = nu; lr_ok = false; lr_at = -1; lr_update_ms = 0; return true; }
         lowrank_clear();
         const size_t n = S->n;
-        lr_rows = rows; lr_nv = nv; lr_nu = nu;
+        lr_rows = rows; lr_nv = nv; lr_nu = nu; lr_capv = std::max(nv, cap); lr_capu = std::max(nu, cap);
         DeviceOwner& O = own_lr;
-        if (!O.raw(&lr_V, (size_t)rows * nv) || !O.raw(&lr_U, (size_t)rows * nu) || !O.raw(&lr_Z1, n * nv) || !O.raw(&lr_Z2, n * nu) ||
+        if (!O.raw(&lr_V, (size_t)rows * lr_capv) || !O.raw(&lr_U, (size_t)rows * lr_capu) || !O.raw(&lr_Z1, n * lr_capv) || !O.raw(&lr_Z2, n * lr_capu) ||
             !O.raw(&lr_part, (size_t)lr_nslab() * LR_MAX * LR_MAX) || !O.raw(&lr_T, LR_MAX * LR_MAX) || !O.raw(&lr_L1, LR_MAX * LR_MAX) || !O.raw(&lr_L2, LR_MAX * LR_MAX) ||
             !O.pinned(&lr_h, LR_MAX * LR_MAX)) { lowrank_clear(); return false; }
         lr_set = true;
@@ -1564,25 +1567,33 @@ public:
     // lbfgs_clear; a push moves two vectors: k_lb_dots + k_lr_reduce give the 2 m + 3 dots (ONE download, ONE synchronisation), lbfgs_host.h does the
     // skip test, sigma, the augment / shift of D, L, S^T S and the coefficients d, C, Lbar, and k_lb_form writes the pair into its slot and V, U into the
     // low-rank update's own buffers: outcome 0 is lowrank_set(rows, m, V, m, U) with these columns.  Caller's numbering, like own_lr: survives a restructure.
+    // lb_type 1, limited-memory SR1 (:523-671): the same dots, D, L, S^T S; the host works on COPIES (sigma, then the eigen-split of Z,
+    // lb_sr1_coefficients) and commits them only when the split rule passed, so a skipped push moves nothing but the counter; k_lb_form_sr1 forms
+    // V (m - nneg columns) and U (nneg).  One stored push can be taken back (lbfgs_undo: the reference's RestoreInternalDataBackup): the state before
+    // it is kept in lb_bk, and the ring has lb_max + 1 slots, so the pair that push evicted is still in its slot.
     bool lb_defined = false;
+    int lb_type = 0, lb_slots = 0, lb_nneg = 0;
+    double lb_E[LB_MAX] = {}, lb_Qs[LB_MAX * LB_MAX] = {};
+    struct LbBackup { bool valid = false; int m = 0, head = 0, nneg = 0, skipped = 0; double sig = 1.0, D[LB_MAX] = {}, L[LB_MAX * LB_MAX] = {}, STS[LB_MAX * LB_MAX] = {}, E[LB_MAX] = {}, Qs[LB_MAX * LB_MAX] = {}; } lb_bk;
     int lb_rows = 0, lb_max = 0, lb_init = 0, lb_m = 0, lb_head = 0, lb_skipped = 0;
     double lb_init_val = 1.0, lb_smin = 1e-8, lb_smax = 1e8, lb_sig = 1.0, lb_push_ms = 0;
     double *lb_S = nullptr, *lb_Y = nullptr, *lb_sy = nullptr, *lb_part = nullptr, *lb_T = nullptr, *lb_coef = nullptr, *lb_h = nullptr, *lb_hc = nullptr;
-    double lb_D[LB_MAX], lb_L[LB_MAX * LB_MAX], lb_STS[LB_MAX * LB_MAX];
+    double lb_D[LB_MAX] = {}, lb_L[LB_MAX * LB_MAX] = {}, lb_STS[LB_MAX * LB_MAX] = {};
     static constexpr int LB_NCOEF = LB_MAX + 2 * LB_MAX * LB_MAX;
     int lb_nslab() const { return std::max(1, (lb_rows + LR_SLAB - 1) / LR_SLAB); }
-    LbRing lb_ring(int m) const { LbRing R; R.m = m; for (int j = 0; j < LB_MAX; ++j) R.slot[j] = (unsigned char)((lb_head + j) % std::max(lb_max, 1)); return R; }
-    void lb_forget() { lb_m = lb_head = lb_skipped = 0; lb_sig = lb_init_val; }
-    void lbfgs_clear() { own_lb.clear(); lb_defined = false; lb_rows = lb_max = 0; lb_push_ms = 0; lb_forget(); lb_S = lb_Y = lb_sy = lb_part = lb_T = lb_coef = lb_h = lb_hc = nullptr; }
-    bool lbfgs_define(int rows, int max_history, int init, double init_val, double smin, double smax) {
+    LbRing lb_ring(int m) const { LbRing R; R.m = m; for (int j = 0; j < LB_MAX; ++j) R.slot[j] = (unsigned char)((lb_head + j) % std::max(lb_slots, 1)); return R; }
+    void lb_forget() { lb_m = lb_head = lb_skipped = lb_nneg = 0; lb_sig = lb_init_val; lb_bk.valid = false; }
+    void lbfgs_clear() { own_lb.clear(); lb_defined = false; lb_rows = lb_max = lb_slots = lb_type = 0; lb_push_ms = 0; lb_forget(); lb_S = lb_Y = lb_sy = lb_part = lb_T = lb_coef = lb_h = lb_hc = nullptr; }
+    bool lbfgs_define(int rows, int max_history, int init, double init_val, double smin, double smax, int type) {
         DeviceGuard guard(dev);
         if (!ready) { if (err_.empty()) err_ = "lbfgs_define: solver not set up"; return false; }
         if (multi) { err_ = "lbfgs_define: not supported on a multi-GPU handle"; return false; }
         HIPCHK(hipStreamSynchronize(stream));
         lbfgs_clear();
         lb_rows = rows; lb_max = max_history; lb_init = init; lb_init_val = init_val; lb_smin = smin; lb_smax = smax;
+        lb_type = type; lb_slots = max_history + (type == 1 ? 1 : 0);      // (SR1: the evicted pair survives the push that evicts it)
         DeviceOwner& O = own_lb;
-        if (!O.zeroed(&lb_S, (size_t)rows * max_history) || !O.zeroed(&lb_Y, (size_t)rows * max_history) || !O.raw(&lb_sy, 2 * (size_t)rows) ||
+        if (!O.zeroed(&lb_S, (size_t)rows * lb_slots) || !O.zeroed(&lb_Y, (size_t)rows * lb_slots) || !O.raw(&lb_sy, 2 * (size_t)rows) ||
             !O.raw(&lb_part, (size_t)lb_nslab() * LB_NOUT) || !O.raw(&lb_T, LB_NOUT) || !O.raw(&lb_coef, LB_NCOEF) ||
             !O.pinned(&lb_h, LB_NOUT) || !O.pinned(&lb_hc, LB_NCOEF)) { lbfgs_clear(); return false; }
         HIPCHK(hipDeviceSynchronize());            // (the zero fills ran on the default stream: device_owner.h)
@@ -1604,6 +1615,72 @@ public:
     template <int KP> void lb_launch_form(const double* ds, const double* dy) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_form<KP>), dim3((lb_rows + 255) / 256), dim3(256), 0, stream, lb_S, lb_Y, (long long)lb_rows, ds, dy, lb_rows, lb_ring(lb_m),
                            (const double*)lb_coef, lb_sig, lr_V, lr_U, (long long)lb_rows);
+    }
+    // s == nullptr: no new pair, every column comes from its slot (undo).  lr_V, lr_U must have the shape (lb_rows, lb_m - lb_nneg, lb_nneg).
+    template <int KP> void lb_launch_form_sr1(const double* ds, const double* dy) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_form_sr1<KP>), dim3((lb_rows + 255) / 256), dim3(256), 0, stream, lb_S, lb_Y, (long long)lb_rows, ds, dy, lb_rows, lb_ring(lb_m),
+                           (const double*)lb_coef, lb_sig, lb_nneg, lr_V, lr_U, (long long)lb_rows);
+    }
+    // installs the columns of the current SR1 state (lb_m >= 1, lb_Qs, lb_nneg, lb_sig) as the low-rank update; nothing may be in flight
+    bool lb_install_sr1(const double* ds, const double* dy) {
+        if (!lr_shape(lb_rows, lb_m - lb_nneg, lb_nneg, lb_max)) return false;
+        std::copy(lb_Qs, lb_Qs + LB_MAX * LB_MAX, lb_hc);
+        HIPCHK(hipMemcpyAsync(lb_coef, lb_hc, LB_MAX * LB_MAX * sizeof(double), hipMemcpyHostToDevice, stream));
+        if (lb_m <= 8) lb_launch_form_sr1<8>(ds, dy); else if (lb_m <= 16) lb_launch_form_sr1<16>(ds, dy); else lb_launch_form_sr1<32>(ds, dy);
+        HIPCHK(hipGetLastError());
+        return true;
+    }
+    // the host half of an SR1 push, behind the download of the dots: *outcome 0 stored and installed, 1 skipped (only the counter moved)
+    bool lb_push_sr1(const double* ds, const double* dy, bool device, int m0, double ss, double sy, double yy, int* outcome) {
+        if (!std::isfinite(ss) || !std::isfinite(sy) || !std::isfinite(yy)) { ++lb_skipped; lb_bk.valid = false; return true; }
+        double D[LB_MAX], L[LB_MAX * LB_MAX], STS[LB_MAX * LB_MAX], E[LB_MAX], Qs[LB_MAX * LB_MAX];
+        std::copy(lb_D, lb_D + LB_MAX, D); std::copy(lb_L, lb_L + LB_MAX * LB_MAX, L); std::copy(lb_STS, lb_STS + LB_MAX * LB_MAX, STS);
+        const int m1 = lb_store(m0, lb_max, D, L, STS, lb_h, lb_h + m0, ss, sy);
+        const double sig = lb_sr1_sigma(lb_init, lb_init_val, m1, ss, sy, yy);
+        std::fill(Qs, Qs + LB_MAX * LB_MAX, 0.0); std::fill(E, E + LB_MAX, 0.0);
+        int nneg = 0;
+        const int r = lb_sr1_coefficients(m1, STS, L, LB_MAX, D, sig, E, Qs, LB_MAX, &nneg);
+        if (r == LB_SR1_FAILED) { err_ = "lbfgs_push: the eigen-solver of the SR1 split did not converge in " + std::to_string(LBH_JACOBI_SWEEPS) + " sweeps"; return false; }
+        if (r == LB_SR1_SKIP) { ++lb_skipped; lb_bk.valid = false; return true; }
+        LbBackup& B = lb_bk;                                               // the state before the commit: what lbfgs_undo restores
+        B.valid = true; B.m = lb_m; B.head = lb_head; B.nneg = lb_nneg; B.skipped = lb_skipped; B.sig = lb_sig;
+        std::copy(lb_D, lb_D + LB_MAX, B.D); std::copy(lb_L, lb_L + LB_MAX * LB_MAX, B.L); std::copy(lb_STS, lb_STS + LB_MAX * LB_MAX, B.STS);
+        std::copy(lb_E, lb_E + LB_MAX, B.E); std::copy(lb_Qs, lb_Qs + LB_MAX * LB_MAX, B.Qs);
+        if (m0 == lb_max) lb_head = (lb_head + 1) % lb_slots;
+        lb_m = m1; lb_sig = sig; lb_nneg = nneg; lb_skipped = 0;
+        std::copy(D, D + LB_MAX, lb_D); std::copy(L, L + LB_MAX * LB_MAX, lb_L); std::copy(STS, STS + LB_MAX * LB_MAX, lb_STS);
+        std::copy(E, E + LB_MAX, lb_E); std::copy(Qs, Qs + LB_MAX * LB_MAX, lb_Qs);
+        if (!lb_install_sr1(ds, dy)) return false;
+        if (device) HIPCHK(hipStreamSynchronize(stream));      // (the caller's vectors are free again when the call returns)
+        *outcome = 0;
+        return true;
+    }
+    // takes the last stored SR1 push back: *undone 1, or 0 when there is nothing to undo (then nothing changes)
+    bool lbfgs_undo(int* undone) {
+        DeviceGuard guard(dev);
+        *undone = 0;
+        if (!ready) { if (err_.empty()) err_ = "lbfgs_undo: solver not set up"; return false; }
+        if (!lb_defined) { err_ = "lbfgs_undo: lbfgs_define first"; return false; }
+        if (lb_type != 1) { err_ = "lbfgs_undo: only an SR1 history (lbfgs_define_sr1) can take a push back"; return false; }
+        if (!lb_bk.valid) return true;
+        HIPCHK(hipStreamSynchronize(stream));      // (the form kernel of the push reads lb_coef, a correction may read the columns about to be replaced)
+        const LbBackup& B = lb_bk;
+        lb_m = B.m; lb_head = B.head; lb_nneg = B.nneg; lb_sig = B.sig; lb_skipped = B.skipped + 1;
+        std::copy(B.D, B.D + LB_MAX, lb_D); std::copy(B.L, B.L + LB_MAX * LB_MAX, lb_L); std::copy(B.STS, B.STS + LB_MAX * LB_MAX, lb_STS);
+        std::copy(B.E, B.E + LB_MAX, lb_E); std::copy(B.Qs, B.Qs + LB_MAX * LB_MAX, lb_Qs);
+        lb_bk.valid = false;
+        if (lb_m == 0) lowrank_clear();
+        else {
+            if (!lb_install_sr1(nullptr, nullptr)) return false;
+            HIPCHK(hipStreamSynchronize(stream));
+        }
+        *undone = 1;
+        return true;
+    }
+    void lbfgs_sr1_info(int* type, int* nneg, int* can_undo, double* E) const {
+        const bool sr1 = lb_defined && lb_type == 1;
+        if (type) *type = lb_defined ? lb_type : 0; if (nneg) *nneg = sr1 ? lb_nneg : 0; if (can_undo) *can_undo = sr1 && lb_bk.valid ? 1 : 0;
+        if (E && sr1) for (int j = 0; j < lb_m; ++j) E[j] = lb_E[j];
     }
     // s, y: host vectors (device = false: uploaded to the staging pair) or device vectors of lb_rows.  *outcome: 0 stored and installed, 1 skipped, 2 stored, M not positive definite
     bool lbfgs_push(const double* s, const double* y, bool device, int* outcome) {
@@ -1627,6 +1704,7 @@ public:
         HIPCHK(hipStreamSynchronize(stream));      // the one synchronisation of a push (it also ends the form kernel of the push before: lb_hc is free)
         const double ss = lb_h[2 * m0], sy = lb_h[2 * m0 + 1], yy = lb_h[2 * m0 + 2];
         auto done = [&] { lb_push_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); return true; };
+        if (lb_type == 1) return lb_push_sr1(ds, dy, device, m0, ss, sy, yy, outcome) && done();
         if (lb_skip(ss, sy, yy)) { ++lb_skipped; return done(); }
         lb_skipped = 0;
         lb_sig = lb_sigma(lb_init, lb_init_val, lb_smin, lb_smax, ss, sy, yy);
@@ -1981,7 +2059,10 @@ bool Numeric::lowrank_solve_device2(int nrhs, const double* db, int ldb, double*
 bool Numeric::lowrank_clear() { DeviceGuard guard(p_->dev); if (p_->stream) (void)hipStreamSynchronize(p_->stream); p_->lowrank_clear(); return true; }
 void Numeric::lowrank_info(int* rows, int* nv, int* nu, int* current, double* update_ms) const { p_->lowrank_info(rows, nv, nu, current, update_ms); }
 long long Numeric::factor_count() const { return p_->factor_count; }
-bool Numeric::lbfgs_define(int rows, int max_history, int init, double init_val, double sigma_min, double sigma_max) { return p_->lbfgs_define(rows, max_history, init, init_val, sigma_min, sigma_max); }
+bool Numeric::lbfgs_define(int rows, int max_history, int init, double init_val, double sigma_min, double sigma_max) { return p_->lbfgs_define(rows, max_history, init, init_val, sigma_min, sigma_max, 0); }
+bool Numeric::lbfgs_define_sr1(int rows, int max_history, int init, double init_val) { return p_->lbfgs_define(rows, max_history, init, init_val, 1e-8, 1e8, 1); }
+bool Numeric::lbfgs_undo(int* undone) { return p_->lbfgs_undo(undone); }
+void Numeric::lbfgs_sr1_info(int* type, int* nneg, int* can_undo, double* E) const { p_->lbfgs_sr1_info(type, nneg, can_undo, E); }
 bool Numeric::lbfgs_push(const double* s, const double* y, bool device, int* outcome) { return p_->lbfgs_push(s, y, device, outcome); }
 bool Numeric::lbfgs_reset() { return p_->lbfgs_reset(); }
 bool Numeric::lbfgs_clear() { DeviceGuard guard(p_->dev); if (p_->stream) (void)hipStreamSynchronize(p_->stream); p_->lbfgs_clear(); return true; }

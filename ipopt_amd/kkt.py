@@ -75,11 +75,13 @@ ABI_SYMBOLS = [
     "mi355x_kkt_pd_define", "mi355x_kkt_pd_put_data", "mi355x_kkt_pd_put", "mi355x_kkt_pd_get", "mi355x_kkt_pd_solve_once", "mi355x_kkt_pd_residual",
     "mi355x_kkt_lowrank_set", "mi355x_kkt_lowrank_update", "mi355x_kkt_lowrank_solve", "mi355x_kkt_lowrank_solve_device2", "mi355x_kkt_lowrank_clear", "mi355x_kkt_lowrank_info",
     "mi355x_kkt_lbfgs_define", "mi355x_kkt_lbfgs_push", "mi355x_kkt_lbfgs_push_device", "mi355x_kkt_lbfgs_reset", "mi355x_kkt_lbfgs_clear", "mi355x_kkt_lbfgs_info", "mi355x_kkt_lbfgs_get", "mi355x_kkt_lbfgs_coefficients",
+    "mi355x_kkt_lbfgs_define_sr1", "mi355x_kkt_lbfgs_undo", "mi355x_kkt_lbfgs_sr1_info", "mi355x_kkt_lbfgs_sr1_coefficients",
 ]
 LOWRANK_MAX = 32
 LBFGS_MAX = 32
 LBFGS_INIT = {"scalar1": 0, "scalar2": 1, "scalar3": 2, "scalar4": 3, "constant": 4}      # limited_memory_initialization
 LBFGS_STORED, LBFGS_SKIPPED, LBFGS_NOT_POSDEF = 0, 1, 2                                     # outcome of a push
+LBFGS_BFGS, LBFGS_SR1 = 0, 1                                                                # limited_memory_update_type of a history
 KERNEL_KINDS = ["gather_scale", "front_wave", "front_lds64", "front_lds128", "big_assemble", "big_diag", "big_trsm", "big_schur",
                 "stats", "solve_perm", "fwd_wave", "fwd_lds", "fwd_big", "bwd_wave", "bwd_lds", "bwd_big", "fwd_big_upd", "bwd_big_dot"]
 
@@ -158,6 +160,10 @@ def load_library():
     lib.mi355x_kkt_lbfgs_info.argtypes = [vp, ip, ip, ip, dp, ip, dp]
     lib.mi355x_kkt_lbfgs_get.argtypes = [vp, C.c_int, vp, C.c_int64]
     lib.mi355x_kkt_lbfgs_coefficients.argtypes = [C.c_int, vp, vp, vp, C.c_double, vp, vp]
+    lib.mi355x_kkt_lbfgs_define_sr1.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double]
+    lib.mi355x_kkt_lbfgs_undo.argtypes = [vp, ip]
+    lib.mi355x_kkt_lbfgs_sr1_info.argtypes = [vp, ip, ip, ip, vp, C.c_int]
+    lib.mi355x_kkt_lbfgs_sr1_coefficients.argtypes = [C.c_int, vp, vp, vp, C.c_double, vp, vp, ip]
     lib.mi355x_kkt_set_comm_rccl.argtypes = [vp, vp]
     lib.mi355x_kkt_comm_shm_id.argtypes = [vp, C.c_int]
     lib.mi355x_kkt_set_comm_shm.argtypes = [vp, vp]
@@ -181,6 +187,20 @@ def lbfgs_coefficients(sts, L, D, sigma):
     if st == FATAL:
         raise KKTError("lbfgs_coefficients: m must be in [0, 32]")
     return st, Cm, Lbar
+
+
+def lbfgs_sr1_coefficients(sts, L, D, sigma):
+    """host only, no handle, no GPU: (status, E, Qs, nneg) of include/mi355x_kkt.h's mi355x_kkt_lbfgs_sr1_coefficients; status SUCCESS, or SINGULAR
+    when the split rule says skip (then Qs is not scaled)"""
+    D = np.ascontiguousarray(D, dtype=np.float64); m = D.shape[0]
+    sts = np.asfortranarray(sts, dtype=np.float64); L = np.asfortranarray(L, dtype=np.float64)
+    if sts.shape != (m, m) or L.shape != (m, m):
+        raise KKTError("lbfgs_sr1_coefficients: S^T S and L must be m x m, D of m")
+    E = np.zeros(m); Qs = np.zeros((m, m), order="F"); nneg = C.c_int(0)
+    st = load_library().mi355x_kkt_lbfgs_sr1_coefficients(m, sts.ctypes.data, L.ctypes.data, D.ctypes.data, float(sigma), E.ctypes.data, Qs.ctypes.data, C.byref(nneg))
+    if st == FATAL:
+        raise KKTError("lbfgs_sr1_coefficients: m must be in [0, 32]" if not 0 <= m <= LBFGS_MAX else "lbfgs_sr1_coefficients: the eigen-solver did not converge")
+    return st, E, Qs, nneg.value
 
 
 class KKTSolver:
@@ -453,6 +473,29 @@ class KKTSolver:
         if self.lib.mi355x_kkt_lbfgs_get(self._h, int(w), out.ctypes.data if out.size else None, out.size) != 0:
             raise KKTError("lbfgs_get: " + self.last_error())
         return out
+
+    # --- limited-memory SR1: the same history and calls; V (memory - nneg columns), U (nneg) from the eigen-split of Z; one push can be taken back ---
+    def lbfgs_define_sr1(self, rows, max_history=6, init="scalar1", init_val=1.0):
+        """init: a name of LBFGS_INIT or its number; sigma is not clipped"""
+        st = self.lib.mi355x_kkt_lbfgs_define_sr1(self._h, int(rows), int(max_history), LBFGS_INIT.get(init, init), init_val)
+        if st != 0:
+            raise KKTError("lbfgs_define_sr1: " + self.last_error())
+
+    def lbfgs_undo(self) -> int:
+        """takes the last stored push of an SR1 history back; -> 1, or 0 when there is nothing to undo"""
+        u = C.c_int(0)
+        if self.lib.mi355x_kkt_lbfgs_undo(self._h, C.byref(u)) != 0:
+            raise KKTError("lbfgs_undo: " + self.last_error())
+        return u.value
+
+    def lbfgs_sr1_info(self) -> dict:
+        """type LBFGS_BFGS | LBFGS_SR1, nneg, can_undo, E: the `memory` eigenvalues of the installed split, ascending (empty for a BFGS history)"""
+        t, nn, cu = C.c_int(0), C.c_int(0), C.c_int(0)
+        E = np.zeros(LBFGS_MAX)
+        if self.lib.mi355x_kkt_lbfgs_sr1_info(self._h, C.byref(t), C.byref(nn), C.byref(cu), E.ctypes.data, LBFGS_MAX) != 0:
+            raise KKTError("lbfgs_sr1_info: " + self.last_error())
+        m = self.lbfgs_info()["memory"] if t.value == LBFGS_SR1 else 0
+        return {"type": t.value, "nneg": nn.value, "can_undo": bool(cu.value), "E": E[:m].copy()}
 
     # --- multi-GPU communicator (include/mi355x_kkt.h): after one of these, multi_solve / factor_device / solve_device* of a
     #     handle created with nranks > 1 run the distributed sequence inside the library ---
