@@ -384,16 +384,24 @@ int mi355x_kkt_pd_residual(mi355x_kkt_handle h, int rhs, int res, int resid, con
 // ---- low-rank update of the factored system (IpLowRankAugSystemSolver.cpp): K + V V^T - U U^T ----
 // Every argument is checked before the device is touched (the checks answer on a machine without one); then the multi-GPU refusal, then the device.
 #define LR_FAIL(msg) do { h->err = std::string(name) + ": " + (msg); return MI355X_KKT_FATAL; } while (0)
-static int lowrank_gate(mi355x_kkt_handle h, const char* name)
+// behind a call's own argument checks: the not-analysed and multi-GPU refusals, the device, then (needs_factor) the factorisation
+static int lowrank_ready(mi355x_kkt_handle h, const char* name, bool needs_factor)
 {
+    if (!h) return MI355X_KKT_FATAL;
     if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
     if (h->opts.nranks > 1) LR_FAIL("not supported on a multi-GPU handle");
+    if (!h->numeric_ready) LR_FAIL("no usable HIP device (no CPU fallback)" + (h->setup_err.empty() ? std::string() : ": " + h->setup_err));
+    if (needs_factor && !h->factored) LR_FAIL("no factorisation available");
     return MI355X_KKT_SUCCESS;
 }
-static int lowrank_device(mi355x_kkt_handle h, const char* name)
+// lowrank_ready, then call(): false is the engine's failure (its error text becomes the handle's)
+extern "C++" {      // (a template cannot have C linkage)
+template <class F> static int lowrank_call(mi355x_kkt_handle h, const char* name, bool needs_factor, F&& call)
 {
-    if (!h->numeric_ready) LR_FAIL("no usable HIP device (no CPU fallback)" + (h->setup_err.empty() ? std::string() : ": " + h->setup_err));
-    return MI355X_KKT_SUCCESS;
+    if (lowrank_ready(h, name, needs_factor) != 0) return MI355X_KKT_FATAL;
+    try { if (!call()) { h->err = h->num->error(); return MI355X_KKT_FATAL; } return MI355X_KKT_SUCCESS; }
+    catch (...) { h->err = std::string(name) + ": unexpected exception"; return MI355X_KKT_FATAL; }
+}
 }
 int mi355x_kkt_lowrank_set(mi355x_kkt_handle h, int rows, int nv, const double* V, int ldv, int nu, const double* U, int ldu)
 {
@@ -407,24 +415,18 @@ int mi355x_kkt_lowrank_set(mi355x_kkt_handle h, int rows, int nv, const double* 
     if (nu > 0 && ldu < rows) LR_FAIL("ldu must be >= rows");
     if (nv > 0 && rows > 0 && !V) LR_FAIL("V is null with nv > 0");
     if (nu > 0 && rows > 0 && !U) LR_FAIL("U is null with nu > 0");
-    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
-    try { if (!h->num->lowrank_set(rows, nv, V, ldv, nu, U, ldu)) { h->err = h->num->error(); return MI355X_KKT_FATAL; } return MI355X_KKT_SUCCESS; }
-    catch (...) { h->err = "lowrank_set: unexpected exception"; return MI355X_KKT_FATAL; }
+    return lowrank_call(h, name, false, [&] { return h->num->lowrank_set(rows, nv, V, ldv, nu, U, ldu); });
 }
 int mi355x_kkt_lowrank_update(mi355x_kkt_handle h, int* which_failed)
 {
     if (!h) return MI355X_KKT_FATAL;
-    const char* name = "lowrank_update";
     if (which_failed) *which_failed = 0;
-    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
-    if (!h->factored) LR_FAIL("no factorisation available");
-    try {
-        int which = 0;
-        if (!h->num->lowrank_update(&which)) { h->err = h->num->error(); return MI355X_KKT_FATAL; }
-        if (which_failed) *which_failed = which;
-        if (which != 0) { h->err = std::string("lowrank_update: ") + (which == 1 ? "M1 = I + V^T K^-1 V" : "M2 = I - U^T (K + V V^T)^-1 U") + " is not positive definite (wrong inertia)"; return MI355X_KKT_WRONG_INERTIA; }
-        return MI355X_KKT_SUCCESS;
-    } catch (...) { h->err = "lowrank_update: unexpected exception"; return MI355X_KKT_FATAL; }
+    int which = 0;
+    const int st = lowrank_call(h, "lowrank_update", true, [&] { return h->num->lowrank_update(&which); });
+    if (st != MI355X_KKT_SUCCESS) return st;
+    if (which_failed) *which_failed = which;
+    if (which != 0) { h->err = std::string("lowrank_update: ") + (which == 1 ? "M1 = I + V^T K^-1 V" : "M2 = I - U^T (K + V V^T)^-1 U") + " is not positive definite (wrong inertia)"; return MI355X_KKT_WRONG_INERTIA; }
+    return MI355X_KKT_SUCCESS;
 }
 int mi355x_kkt_lowrank_solve(mi355x_kkt_handle h, int nrhs, double* rhs, int ld)
 {
@@ -434,12 +436,7 @@ int mi355x_kkt_lowrank_solve(mi355x_kkt_handle h, int nrhs, double* rhs, int ld)
     if (nrhs < 0) LR_FAIL("nrhs must be >= 0");
     if (nrhs > 0 && h->sym.n > 0 && !rhs) LR_FAIL("rhs_inout is null with nrhs > 0");
     if (nrhs > 1 && ld < h->sym.n) LR_FAIL("ld must be >= n");
-    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
-    if (!h->factored) LR_FAIL("no factorisation available");
-    try {
-        if (h->sym.n == 0 || nrhs == 0) return MI355X_KKT_SUCCESS;
-        if (!h->num->lowrank_solve_host(nrhs, rhs, ld)) { h->err = h->num->error(); return MI355X_KKT_FATAL; } return MI355X_KKT_SUCCESS;
-    } catch (...) { h->err = "lowrank_solve: unexpected exception"; return MI355X_KKT_FATAL; }
+    return lowrank_call(h, name, true, [&] { return h->sym.n == 0 || nrhs == 0 || h->num->lowrank_solve_host(nrhs, rhs, ld); });
 }
 int mi355x_kkt_lowrank_solve_device2(mi355x_kkt_handle h, int nrhs, const double* db, int ldb, double* dx, int ldx)
 {
@@ -451,45 +448,34 @@ int mi355x_kkt_lowrank_solve_device2(mi355x_kkt_handle h, int nrhs, const double
     if (nrhs > 0 && h->sym.n > 0 && !dx) LR_FAIL("d_x is null with nrhs > 0");
     if (nrhs > 1 && ldb < h->sym.n) LR_FAIL("ldb must be >= n");
     if (nrhs > 1 && ldx < h->sym.n) LR_FAIL("ldx must be >= n");
-    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
-    if (!h->factored) LR_FAIL("no factorisation available");
-    try {
-        if (h->sym.n == 0 || nrhs == 0) return MI355X_KKT_SUCCESS;
-        if (!h->num->lowrank_solve_device2(nrhs, db, ldb, dx, ldx)) { h->err = h->num->error(); return MI355X_KKT_FATAL; } return MI355X_KKT_SUCCESS;
-    } catch (...) { h->err = "lowrank_solve_device2: unexpected exception"; return MI355X_KKT_FATAL; }
+    return lowrank_call(h, name, true, [&] { return h->sym.n == 0 || nrhs == 0 || h->num->lowrank_solve_device2(nrhs, db, ldb, dx, ldx); });
 }
-int mi355x_kkt_lowrank_clear(mi355x_kkt_handle h)
-{
-    if (!h) return MI355X_KKT_FATAL;
-    const char* name = "lowrank_clear";
-    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
-    try { h->num->lowrank_clear(); return MI355X_KKT_SUCCESS; } catch (...) { h->err = "lowrank_clear: unexpected exception"; return MI355X_KKT_FATAL; }
-}
+int mi355x_kkt_lowrank_clear(mi355x_kkt_handle h) { return lowrank_call(h, "lowrank_clear", false, [&] { return h->num->lowrank_clear(); }); }
 int mi355x_kkt_lowrank_info(mi355x_kkt_handle h, int* rows, int* nv, int* nu, int* current, double* update_ms)
 {
     if (!h) return MI355X_KKT_FATAL;
-    const char* name = "lowrank_info";
     if (rows) *rows = 0; if (nv) *nv = 0; if (nu) *nu = 0; if (current) *current = 0; if (update_ms) *update_ms = 0.0;
-    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
-    h->num->lowrank_info(rows, nv, nu, current, update_ms);
-    return MI355X_KKT_SUCCESS;
+    return lowrank_call(h, "lowrank_info", false, [&] { h->num->lowrank_info(rows, nv, nu, current, update_ms); return true; });
 }
 // ---- limited-memory BFGS on the device (IpLimMemQuasiNewtonUpdater.cpp): the (s, y) history, V and U formed there and installed as the low-rank update ----
 // The same order as above: every argument, then the multi-GPU refusal, then the device.
-int mi355x_kkt_lbfgs_define(mi355x_kkt_handle h, int rows, int max_history, int init, double init_val, double sigma_min, double sigma_max)
+static int lbfgs_define_args(mi355x_kkt_handle h, const char* name, int rows, int max_history, int init, double init_val)      // (lbfgs_define and lbfgs_define_sr1)
 {
-    if (!h) return MI355X_KKT_FATAL;
-    const char* name = "lbfgs_define";
     if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
     if (rows < 1 || rows > h->sym.n) LR_FAIL("rows must be in [1, n]");
     if (max_history < 1 || max_history > MI355X_KKT_LBFGS_MAX) LR_FAIL("max_history must be in [1, 32]");
     if (init < 0 || init > 4) LR_FAIL("init must be in [0, 4] (scalar1..4, constant)");
     if (!(init_val > 0.0) || !std::isfinite(init_val)) LR_FAIL("init_val must be positive and finite");
+    return MI355X_KKT_SUCCESS;
+}
+int mi355x_kkt_lbfgs_define(mi355x_kkt_handle h, int rows, int max_history, int init, double init_val, double sigma_min, double sigma_max)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "lbfgs_define";
+    if (lbfgs_define_args(h, name, rows, max_history, init, init_val) != 0) return MI355X_KKT_FATAL;
     if (!(sigma_min > 0.0) || !std::isfinite(sigma_min)) LR_FAIL("sigma_min must be positive and finite");
     if (!(sigma_max >= sigma_min) || !std::isfinite(sigma_max)) LR_FAIL("sigma_max must be finite and >= sigma_min");
-    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
-    try { if (!h->num->lbfgs_define(rows, max_history, init, init_val, sigma_min, sigma_max)) { h->err = h->num->error(); return MI355X_KKT_FATAL; } return MI355X_KKT_SUCCESS; }
-    catch (...) { h->err = "lbfgs_define: unexpected exception"; return MI355X_KKT_FATAL; }
+    return lowrank_call(h, name, false, [&] { return h->num->lbfgs_define(rows, max_history, init, init_val, sigma_min, sigma_max); });
 }
 static int lbfgs_push_any(mi355x_kkt_handle h, const char* name, const double* s, const double* y, bool device, int* outcome)
 {
@@ -498,39 +484,20 @@ static int lbfgs_push_any(mi355x_kkt_handle h, const char* name, const double* s
     if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
     if (!s) LR_FAIL(device ? "d_s is null" : "s is null");
     if (!y) LR_FAIL(device ? "d_y is null" : "y is null");
-    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
-    try {
-        int oc = 1;
-        if (!h->num->lbfgs_push(s, y, device, &oc)) { h->err = h->num->error(); return MI355X_KKT_FATAL; }
-        if (outcome) *outcome = oc;
-        return MI355X_KKT_SUCCESS;
-    } catch (...) { h->err = std::string(name) + ": unexpected exception"; return MI355X_KKT_FATAL; }
+    int oc = 1;
+    const int st = lowrank_call(h, name, false, [&] { return h->num->lbfgs_push(s, y, device, &oc); });
+    if (st == MI355X_KKT_SUCCESS && outcome) *outcome = oc;
+    return st;
 }
 int mi355x_kkt_lbfgs_push(mi355x_kkt_handle h, const double* s, const double* y, int* outcome) { return lbfgs_push_any(h, "lbfgs_push", s, y, false, outcome); }
 int mi355x_kkt_lbfgs_push_device(mi355x_kkt_handle h, const double* d_s, const double* d_y, int* outcome) { return lbfgs_push_any(h, "lbfgs_push_device", d_s, d_y, true, outcome); }
-int mi355x_kkt_lbfgs_reset(mi355x_kkt_handle h)
-{
-    if (!h) return MI355X_KKT_FATAL;
-    const char* name = "lbfgs_reset";
-    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
-    try { if (!h->num->lbfgs_reset()) { h->err = h->num->error(); return MI355X_KKT_FATAL; } return MI355X_KKT_SUCCESS; }
-    catch (...) { h->err = "lbfgs_reset: unexpected exception"; return MI355X_KKT_FATAL; }
-}
-int mi355x_kkt_lbfgs_clear(mi355x_kkt_handle h)
-{
-    if (!h) return MI355X_KKT_FATAL;
-    const char* name = "lbfgs_clear";
-    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
-    try { h->num->lbfgs_clear(); return MI355X_KKT_SUCCESS; } catch (...) { h->err = "lbfgs_clear: unexpected exception"; return MI355X_KKT_FATAL; }
-}
+int mi355x_kkt_lbfgs_reset(mi355x_kkt_handle h) { return lowrank_call(h, "lbfgs_reset", false, [&] { return h->num->lbfgs_reset(); }); }
+int mi355x_kkt_lbfgs_clear(mi355x_kkt_handle h) { return lowrank_call(h, "lbfgs_clear", false, [&] { return h->num->lbfgs_clear(); }); }
 int mi355x_kkt_lbfgs_info(mi355x_kkt_handle h, int* rows, int* max_history, int* memory, double* sigma, int* skipped_in_a_row, double* push_ms)
 {
     if (!h) return MI355X_KKT_FATAL;
-    const char* name = "lbfgs_info";
     if (rows) *rows = 0; if (max_history) *max_history = 0; if (memory) *memory = 0; if (sigma) *sigma = 0.0; if (skipped_in_a_row) *skipped_in_a_row = 0; if (push_ms) *push_ms = 0.0;
-    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
-    h->num->lbfgs_info(rows, max_history, memory, sigma, skipped_in_a_row, push_ms);
-    return MI355X_KKT_SUCCESS;
+    return lowrank_call(h, "lbfgs_info", false, [&] { h->num->lbfgs_info(rows, max_history, memory, sigma, skipped_in_a_row, push_ms); return true; });
 }
 int mi355x_kkt_lbfgs_get(mi355x_kkt_handle h, int what, double* out, int64_t capacity)
 {
@@ -540,9 +507,7 @@ int mi355x_kkt_lbfgs_get(mi355x_kkt_handle h, int what, double* out, int64_t cap
     if (what < 0 || what > 6) LR_FAIL("what must be in [0, 6]");
     if (capacity < 0) LR_FAIL("capacity must be >= 0");
     if (capacity > 0 && !out) LR_FAIL("out is null with capacity > 0");
-    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
-    try { if (!h->num->lbfgs_get(what, out, (long long)capacity)) { h->err = h->num->error(); return MI355X_KKT_FATAL; } return MI355X_KKT_SUCCESS; }
-    catch (...) { h->err = "lbfgs_get: unexpected exception"; return MI355X_KKT_FATAL; }
+    return lowrank_call(h, name, false, [&] { return h->num->lbfgs_get(what, out, (long long)capacity); });
 }
 // host only, no handle, no device: the small algebra of a push (lbfgs_host.h), m x m column-major with leading dimension m
 int mi355x_kkt_lbfgs_coefficients(int m, const double* sts, const double* L, const double* D, double sigma, double* C_out, double* Lbar_out)
@@ -555,27 +520,17 @@ int mi355x_kkt_lbfgs_define_sr1(mi355x_kkt_handle h, int rows, int max_history, 
 {
     if (!h) return MI355X_KKT_FATAL;
     const char* name = "lbfgs_define_sr1";
-    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
-    if (rows < 1 || rows > h->sym.n) LR_FAIL("rows must be in [1, n]");
-    if (max_history < 1 || max_history > MI355X_KKT_LBFGS_MAX) LR_FAIL("max_history must be in [1, 32]");
-    if (init < 0 || init > 4) LR_FAIL("init must be in [0, 4] (scalar1..4, constant)");
-    if (!(init_val > 0.0) || !std::isfinite(init_val)) LR_FAIL("init_val must be positive and finite");
-    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
-    try { if (!h->num->lbfgs_define_sr1(rows, max_history, init, init_val)) { h->err = h->num->error(); return MI355X_KKT_FATAL; } return MI355X_KKT_SUCCESS; }
-    catch (...) { h->err = "lbfgs_define_sr1: unexpected exception"; return MI355X_KKT_FATAL; }
+    if (lbfgs_define_args(h, name, rows, max_history, init, init_val) != 0) return MI355X_KKT_FATAL;
+    return lowrank_call(h, name, false, [&] { return h->num->lbfgs_define_sr1(rows, max_history, init, init_val); });
 }
 int mi355x_kkt_lbfgs_undo(mi355x_kkt_handle h, int* undone)
 {
     if (!h) return MI355X_KKT_FATAL;
-    const char* name = "lbfgs_undo";
     if (undone) *undone = 0;
-    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
-    try {
-        int u = 0;
-        if (!h->num->lbfgs_undo(&u)) { h->err = h->num->error(); return MI355X_KKT_FATAL; }
-        if (undone) *undone = u;
-        return MI355X_KKT_SUCCESS;
-    } catch (...) { h->err = "lbfgs_undo: unexpected exception"; return MI355X_KKT_FATAL; }
+    int u = 0;
+    const int st = lowrank_call(h, "lbfgs_undo", false, [&] { return h->num->lbfgs_undo(&u); });
+    if (st == MI355X_KKT_SUCCESS && undone) *undone = u;
+    return st;
 }
 int mi355x_kkt_lbfgs_sr1_info(mi355x_kkt_handle h, int* type, int* nneg, int* can_undo, double* E, int capacity)
 {
@@ -584,7 +539,7 @@ int mi355x_kkt_lbfgs_sr1_info(mi355x_kkt_handle h, int* type, int* nneg, int* ca
     if (type) *type = 0; if (nneg) *nneg = 0; if (can_undo) *can_undo = 0;
     if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
     if (capacity < 0) LR_FAIL("capacity must be >= 0");
-    if (lowrank_gate(h, name) != 0 || lowrank_device(h, name) != 0) return MI355X_KKT_FATAL;
+    if (lowrank_ready(h, name, false) != 0) return MI355X_KKT_FATAL;
     int t = 0, memory = 0;
     h->num->lbfgs_sr1_info(&t, nullptr, nullptr, nullptr);
     h->num->lbfgs_info(nullptr, nullptr, &memory, nullptr, nullptr, nullptr);

@@ -3,6 +3,21 @@
 // UpdateInternalData :769-818, the columns :440-520): plain host loops with a fixed order, column-major with an explicit leading
 // dimension, at most 32 pairs.  No HIP in here: a stand-alone host program can include it.  Behind the BFGS part, the SR1 update of the same
 // updater (:523-671, SplitEigenvalues :873-983): sigma, a cyclic Jacobi eigen-solver and the split of Z = D + L + L^T - sigma S^T S.
+//
+// At the end, the state machine of a history: LbParams (the constants), LbState (what a push can change) and the transitions.  They take the dots
+// of the new pair (sS[j] = s^T S_j, sY[j] = s^T Y_j over the stored pairs, oldest first; ss, sy, yy), call the helpers above in a fixed order and
+// touch no device; the caller (numeric.hip, or tests/support/lbfgs_state_check.cpp) owns the columns and moves them AFTER the transition:
+//   lb_slot(P, st, j)     the physical column slot of logical pair j (oldest first): (head + j) % slots, BFGS and SR1 alike.  P.slots >= 1.
+//   lb_push_bfgs          LB_PUSH_SKIPPED: lb_skip held, only `skipped` grew.  Otherwise skipped = 0, sigma, head advanced when the history was
+//                         full, D, L, S^T S augmented / shifted; the caller writes the pair into lb_slot(P, st, st.m - 1).  LB_PUSH_STORED: coef
+//                         holds d, C, Lbar (lb_coefficients).  LB_PUSH_NOT_PD: lb_coefficients failed; the pair IS stored, coef is not valid.
+//   lb_push_sr1           works on a copy.  LB_PUSH_SKIPPED (a dot is not finite, or the split rule): st is untouched but for skipped + 1, and the
+//                         backup is invalidated.  LB_PUSH_FAILED (the eigen-solver): nothing changes at all.  LB_PUSH_STORED: backup = st as it
+//                         was, st = the copy with skipped = 0; the caller writes the pair into lb_slot(P, st, st.m - 1), which with slots =
+//                         max_history + 1 is never the slot of a pair that is live in the backup.
+//   lb_undo               1: st = backup with skipped = backup.skipped + 1, the backup is invalidated (one level).  0: no valid backup, nothing
+//                         changes.  It does not look at the type: a BFGS history never has a valid backup, so it answers 0 there; refusing an
+//                         undo on a BFGS history as an error is the caller's business (lbfgs_undo in numeric.hip does).
 #pragma once
 #include <cmath>
 #include <limits>
@@ -190,6 +205,58 @@ inline int lb_sr1_coefficients(int m, const double* sts, const double* L, int ld
         for (int i = 0; i < m; ++i) Qs[i + j * ldo] = Qs[i + j * ldo] / r;
     }
     return LB_SR1_OK;
+}
+
+// ---- the state of a history and its transitions (see the head of this file) ----
+struct LbParams {                       // the constants of a history, set by define and never by a push.  type: 0 BFGS, 1 SR1
+    int type = 0, max_history = 0, slots = 0, init = 0;      // slots = max_history (BFGS) or max_history + 1 (SR1: the pair a push evicts survives that push)
+    double init_val = 1.0, smin = 1e-8, smax = 1e8;
+};
+struct LbState {                        // everything a push can change; a plain value: copied, assigned and compared as a whole
+    int m = 0, head = 0, nneg = 0, skipped = 0;
+    double sigma = 1.0, D[LBH_MAX] = {}, L[LBH_MAX * LBH_MAX] = {}, STS[LBH_MAX * LBH_MAX] = {}, E[LBH_MAX] = {}, Qs[LBH_MAX * LBH_MAX] = {};
+};
+static constexpr int LBH_NCOEF = LBH_MAX + 2 * LBH_MAX * LBH_MAX;      // d, C, Lbar of a BFGS push, in this order
+
+inline LbParams lb_params(int type, int max_history, int init, double init_val, double smin, double smax)
+{ return LbParams{type, max_history, max_history + (type == 1 ? 1 : 0), init, init_val, smin, smax}; }
+inline LbState lb_fresh(const LbParams& P) { LbState st; st.sigma = P.init_val; return st; }
+inline int lb_slot(const LbParams& P, const LbState& st, int j) { return (st.head + j) % P.slots; }
+
+enum { LB_PUSH_STORED = 0, LB_PUSH_SKIPPED = 1, LB_PUSH_NOT_PD = 2, LB_PUSH_FAILED = -1 };
+// sS, sY: the dots of s with the st.m stored pairs, oldest first.  coef: LBH_NCOEF doubles (zeroed here; valid on LB_PUSH_STORED only).
+inline int lb_push_bfgs(const LbParams& P, LbState& st, const double* sS, const double* sY, double ss, double sy, double yy, double* coef)
+{
+    if (lb_skip(ss, sy, yy)) { ++st.skipped; return LB_PUSH_SKIPPED; }
+    st.skipped = 0;
+    st.sigma = lb_sigma(P.init, P.init_val, P.smin, P.smax, ss, sy, yy);
+    if (st.m == P.max_history) st.head = lb_slot(P, st, 1);           // the oldest pair leaves
+    st.m = lb_store(st.m, P.max_history, st.D, st.L, st.STS, sS, sY, ss, sy);
+    for (int e = 0; e < LBH_NCOEF; ++e) coef[e] = 0.0;
+    return lb_coefficients(st.m, st.STS, st.L, LBH_MAX, st.D, st.sigma, coef, coef + LBH_MAX, coef + LBH_MAX + LBH_MAX * LBH_MAX, LBH_MAX) ? LB_PUSH_STORED : LB_PUSH_NOT_PD;
+}
+
+inline int lb_push_sr1(const LbParams& P, LbState& st, LbState& backup, bool& backup_valid, const double* sS, const double* sY, double ss, double sy, double yy)
+{
+    if (!std::isfinite(ss) || !std::isfinite(sy) || !std::isfinite(yy)) { ++st.skipped; backup_valid = false; return LB_PUSH_SKIPPED; }
+    LbState c = st;                                                    // the candidate: committed only when the split rule passes
+    c.m = lb_store(st.m, P.max_history, c.D, c.L, c.STS, sS, sY, ss, sy);
+    c.sigma = lb_sr1_sigma(P.init, P.init_val, c.m, ss, sy, yy);
+    for (int e = 0; e < LBH_MAX * LBH_MAX; ++e) { c.Qs[e] = 0.0; if (e < LBH_MAX) c.E[e] = 0.0; }
+    const int r = lb_sr1_coefficients(c.m, c.STS, c.L, LBH_MAX, c.D, c.sigma, c.E, c.Qs, LBH_MAX, &c.nneg);
+    if (r == LB_SR1_FAILED) return LB_PUSH_FAILED;
+    if (r == LB_SR1_SKIP) { ++st.skipped; backup_valid = false; return LB_PUSH_SKIPPED; }
+    if (st.m == P.max_history) c.head = lb_slot(P, st, 1);            // the oldest pair leaves the window; its slot is the spare one now
+    c.skipped = 0;
+    backup = st; backup_valid = true; st = c;
+    return LB_PUSH_STORED;
+}
+
+inline int lb_undo(LbState& st, const LbState& backup, bool& backup_valid)
+{
+    if (!backup_valid) return 0;
+    st = backup; st.skipped = backup.skipped + 1; backup_valid = false;
+    return 1;
 }
 
 } // namespace mi355x

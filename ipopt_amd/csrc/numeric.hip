@@ -34,6 +34,7 @@
 #include <map>
 #include <string>
 #include <algorithm>
+#include <type_traits>
 #include "numeric.h"
 #include "launch_plan.h"
 #include "env_knobs.h"
@@ -465,8 +466,8 @@ public:
             own_pool.clear(); kept_pool = nullptr; kept_pool_doubles = 0;
             own_asm.clear(); asm_.nseg = 0;
             own_pd.clear(); pd_ready = false;
-            own_lr.clear(); lr_set = lr_ok = false;
-            own_lb.clear(); lb_defined = false;
+            lowrank_clear();
+            lbfgs_clear();
             own_handle.clear(); h_vals = nullptr; h_stats = nullptr; ev0 = ev1 = nullptr; V.tvals = nullptr; d_user_scale = nullptr; prof_ev.clear(); prof_used = 0; prof_kind.clear();
             if (stream3) { (void)hipStreamDestroy(stream3); stream3 = nullptr; }
             if (stream2) { (void)hipStreamDestroy(stream2); stream2 = nullptr; }
@@ -1350,13 +1351,13 @@ public:
     bool pd_solve_once(int rhs, int res, double alpha, double beta) {
         DeviceGuard guard(dev);
         if (!pd_ready || rhs < 0 || rhs >= PD_NVEC || res < 0 || res >= PD_NVEC) { err_ = "pd_solve_once: pd_define first / no such vector"; return false; }
-        if (lr_set && (!lr_fits_x("pd_solve_once") || !lr_require_current("pd_solve_once"))) return false;
+        if (lr.set && (!lr_fits_x("pd_solve_once") || !lr_require_current("pd_solve_once"))) return false;
         const int g4 = grid1d(pd_dim4), gb = grid1d(std::max(std::max(pd_.nxl, pd_.nxu), std::max(pd_.nsl, pd_.nsu)));
         hipLaunchKernelGGL(k_pd_reduce, dim3(g4), dim3(256), 0, stream, pd_, (const double*)pd_vec[rhs], pd_aug, 0);
         hipLaunchKernelGGL(k_pd_reduce, dim3(gb), dim3(256), 0, stream, pd_, (const double*)pd_vec[rhs], pd_aug, 1);
         hipLaunchKernelGGL(k_pd_reduce, dim3(gb), dim3(256), 0, stream, pd_, (const double*)pd_vec[rhs], pd_aug, 2);
         if (!solve_device(1, pd_aug, pd_dim4, pd_aug, pd_dim4, false)) return false;
-        if (lr_set && !lr_correct(pd_aug, pd_dim4, 1)) return false;      // W carries B0 only: the Sherman-Morrison correction of the 4-block solution
+        if (lr.set && !lr_correct(pd_aug, pd_dim4, 1)) return false;      // W carries B0 only: the Sherman-Morrison correction of the 4-block solution
         hipLaunchKernelGGL(k_pd_expand, dim3(g4), dim3(256), 0, stream, pd_, (const double*)pd_vec[rhs], (const double*)pd_aug, pd_vec[res], alpha, beta);
         HIPCHK(hipGetLastError());
         return true;
@@ -1365,11 +1366,11 @@ public:
     bool pd_residual(int rhs, int res, int resid, const double* deltas, double* norms) {
         DeviceGuard guard(dev);
         if (!pd_ready || rhs < 0 || rhs >= PD_NVEC || res < 0 || res >= PD_NVEC || resid < 0 || resid >= PD_NVEC) { err_ = "pd_residual: pd_define first / no such vector"; return false; }
-        if (lr_set && !lr_fits_x("pd_residual")) return false;
+        if (lr.set && !lr_fits_x("pd_residual")) return false;
         const int g4 = grid1d(pd_dim4), gb = grid1d(std::max(std::max(pd_.nxl, pd_.nxu), std::max(pd_.nsl, pd_.nsu)));
         hipLaunchKernelGGL(k_zero_u64, dim3(1), dim3(64), 0, stream, pd_norms_d, 4);
         hipLaunchKernelGGL(k_pd_resid_rows, dim3(g4), dim3(256), 0, stream, pd_, (const double*)pd_vec[rhs], (const double*)pd_vec[res], pd_vec[resid], deltas[0], deltas[1], deltas[2], deltas[3]);
-        if (lr_set && !lr_residual(pd_vec[res], pd_vec[resid])) return false;      // x rows += V (V^T res_x) - U (U^T res_x)
+        if (lr.set && !lr_residual(pd_vec[res], pd_vec[resid])) return false;      // x rows += V (V^T res_x) - U (U^T res_x)
         hipLaunchKernelGGL(k_pd_resid_bounds, dim3(gb), dim3(256), 0, stream, pd_, (const double*)pd_vec[rhs], (const double*)pd_vec[res], pd_vec[resid], 1);
         hipLaunchKernelGGL(k_pd_resid_bounds, dim3(gb), dim3(256), 0, stream, pd_, (const double*)pd_vec[rhs], (const double*)pd_vec[res], pd_vec[resid], 2);
         hipLaunchKernelGGL(k_pd_norms, dim3(grid1d(pd_len8)), dim3(256), 0, stream, pd_, (const double*)pd_vec[rhs], (const double*)pd_vec[res], (const double*)pd_vec[resid], pd_len8);
@@ -1387,37 +1388,39 @@ public:
     // running solution instead of the right-hand side).  M1, M2 positive definite <=> K~ has K's inertia.  The update is CURRENT while
     // factor_count -- bumped by every factorisation and every structure edit -- is the one lowrank_update saw.
     long long factor_count = 0;
-    bool lr_set = false, lr_ok = false; long long lr_at = -1;
-    int lr_rows = 0, lr_nv = 0, lr_nu = 0, lr_capv = 0, lr_capu = 0; double lr_update_ms = 0;      // lr_cap*: the columns the buffers were allocated for (>= lr_nv, lr_nu)
-    double *lr_V = nullptr, *lr_U = nullptr, *lr_Z1 = nullptr, *lr_Z2 = nullptr, *lr_part = nullptr, *lr_T = nullptr, *lr_L1 = nullptr, *lr_L2 = nullptr, *lr_h = nullptr;
-    int lr_nslab() const { return std::max(1, (lr_rows + LR_SLAB - 1) / LR_SLAB); }
-    bool lr_current() const { return lr_set && lr_ok && lr_at == factor_count; }
+    struct LowRank {                           // everything of the update but its arena (own_lr): lowrank_clear() is own_lr.clear(); lr = {};
+        bool set = false, ok = false; long long at = -1;
+        int rows = 0, nv = 0, nu = 0, capv = 0, capu = 0; double update_ms = 0;      // cap*: the columns the buffers were allocated for (>= nv, nu)
+        double *V = nullptr, *U = nullptr, *Z1 = nullptr, *Z2 = nullptr, *part = nullptr, *T = nullptr, *L1 = nullptr, *L2 = nullptr, *h = nullptr;
+        int nslab() const { return std::max(1, (rows + LR_SLAB - 1) / LR_SLAB); }
+    } lr;
+    bool lr_current() const { return lr.set && lr.ok && lr.at == factor_count; }
     bool lr_require_current(const char* who) {
         if (lr_current()) return true;
-        err_ = std::string(who) + (!lr_set ? ": no low-rank update set (lowrank_set, then lowrank_update)"
+        err_ = std::string(who) + (!lr.set ? ": no low-rank update set (lowrank_set, then lowrank_update)"
                                    : ": the low-rank update is not current for the factorisation in the handle (call lowrank_update; it must succeed)");
         return false;
     }
     bool lr_fits_x(const char* who) {
-        if (lr_rows <= pd_.nx) return true;
+        if (lr.rows <= pd_.nx) return true;
         err_ = std::string(who) + ": the low-rank update acts on more rows than the x block has (rows <= n_x)"; return false;
     }
-    void lowrank_clear() { own_lr.clear(); lr_set = lr_ok = false; lr_at = -1; lr_rows = lr_nv = lr_nu = lr_capv = lr_capu = 0; lr_update_ms = 0; lr_V = lr_U = lr_Z1 = lr_Z2 = lr_part = lr_T = lr_L1 = lr_L2 = lr_h = nullptr; }
+    void lowrank_clear() { own_lr.clear(); lr = {}; }
     // the buffers of an update of the shape (rows, nv, nu), set and not current: those in place when that is the installed shape (nothing is
     // allocated: an L-BFGS push with a full history installs its columns into them), fresh ones otherwise.  Nothing may be in flight on them.
     // cap > 0 (an SR1 push, whose split nv + nu = m moves from push to push): fresh buffers get room for max(nv, cap) and max(nu, cap) columns, and
     // buffers in place are kept whenever they have room for nv and nu columns -- then a push allocates nothing although the shape changes.
     bool lr_shape(int rows, int nv, int nu, int cap = 0) {
-        const bool fits = cap > 0 ? nv <= lr_capv && nu <= lr_capu : nv == lr_nv && nu == lr_nu;
-        if (lr_set && rows == lr_rows && fits) { lr_nv = nv; lr_nu = nu; lr_ok = false; lr_at = -1; lr_update_ms = 0; return true; }
+        const bool fits = cap > 0 ? nv <= lr.capv && nu <= lr.capu : nv == lr.nv && nu == lr.nu;
+        if (lr.set && rows == lr.rows && fits) { lr.nv = nv; lr.nu = nu; lr.ok = false; lr.at = -1; lr.update_ms = 0; return true; }
         lowrank_clear();
         const size_t n = S->n;
-        lr_rows = rows; lr_nv = nv; lr_nu = nu; lr_capv = std::max(nv, cap); lr_capu = std::max(nu, cap);
+        lr.rows = rows; lr.nv = nv; lr.nu = nu; lr.capv = std::max(nv, cap); lr.capu = std::max(nu, cap);
         DeviceOwner& O = own_lr;
-        if (!O.raw(&lr_V, (size_t)rows * lr_capv) || !O.raw(&lr_U, (size_t)rows * lr_capu) || !O.raw(&lr_Z1, n * lr_capv) || !O.raw(&lr_Z2, n * lr_capu) ||
-            !O.raw(&lr_part, (size_t)lr_nslab() * LR_MAX * LR_MAX) || !O.raw(&lr_T, LR_MAX * LR_MAX) || !O.raw(&lr_L1, LR_MAX * LR_MAX) || !O.raw(&lr_L2, LR_MAX * LR_MAX) ||
-            !O.pinned(&lr_h, LR_MAX * LR_MAX)) { lowrank_clear(); return false; }
-        lr_set = true;
+        if (!O.raw(&lr.V, (size_t)rows * lr.capv) || !O.raw(&lr.U, (size_t)rows * lr.capu) || !O.raw(&lr.Z1, n * lr.capv) || !O.raw(&lr.Z2, n * lr.capu) ||
+            !O.raw(&lr.part, (size_t)lr.nslab() * LR_MAX * LR_MAX) || !O.raw(&lr.T, LR_MAX * LR_MAX) || !O.raw(&lr.L1, LR_MAX * LR_MAX) || !O.raw(&lr.L2, LR_MAX * LR_MAX) ||
+            !O.pinned(&lr.h, LR_MAX * LR_MAX)) { lowrank_clear(); return false; }
+        lr.set = true;
         return true;
     }
     bool lowrank_set(int rows, int nv, const double* Vh, int ldv, int nu, const double* Uh, int ldu) {
@@ -1426,30 +1429,30 @@ public:
         if (multi) { err_ = "lowrank_set: not supported on a multi-GPU handle"; return false; }
         HIPCHK(hipStreamSynchronize(stream));      // (a correction still in flight reads the buffers about to be freed or overwritten)
         if (!lr_shape(rows, nv, nu)) return false;
-        lr_set = false;                            // (until both copies have arrived)
-        if (rows > 0 && nv > 0) HIPCHK(hipMemcpy2D(lr_V, (size_t)rows * sizeof(double), Vh, (size_t)ldv * sizeof(double), (size_t)rows * sizeof(double), nv, hipMemcpyHostToDevice));
-        if (rows > 0 && nu > 0) HIPCHK(hipMemcpy2D(lr_U, (size_t)rows * sizeof(double), Uh, (size_t)ldu * sizeof(double), (size_t)rows * sizeof(double), nu, hipMemcpyHostToDevice));
-        lr_set = true;
+        lr.set = false;                            // (until both copies have arrived)
+        if (rows > 0 && nv > 0) HIPCHK(hipMemcpy2D(lr.V, (size_t)rows * sizeof(double), Vh, (size_t)ldv * sizeof(double), (size_t)rows * sizeof(double), nv, hipMemcpyHostToDevice));
+        if (rows > 0 && nu > 0) HIPCHK(hipMemcpy2D(lr.U, (size_t)rows * sizeof(double), Uh, (size_t)ldu * sizeof(double), (size_t)rows * sizeof(double), nu, hipMemcpyHostToDevice));
+        lr.set = true;
         return true;
     }
-    // G = A^T B over the first lr_rows rows: gy = 1: one p x q block; gy > 1 (q = 1): gy separate columns of B.  Partials into lr_part.
+    // G = A^T B over the first lr.rows rows: gy = 1: one p x q block; gy > 1 (q = 1): gy separate columns of B.  Partials into lr.part.
     void lr_gram(const double* A, long long lda, const double* B, long long ldb, int p, int q, int gy) {
-        hipLaunchKernelGGL(k_lr_gram, dim3(lr_nslab(), gy), dim3(256), 0, stream, A, lda, B, ldb, lr_rows, p, q, lr_part);
+        hipLaunchKernelGGL(k_lr_gram, dim3(lr.nslab(), gy), dim3(256), 0, stream, A, lda, B, ldb, lr.rows, p, q, lr.part);
     }
-    // the p x q Gram A^T B, summed on the device, into the pinned lr_h (synchronises)
+    // the p x q Gram A^T B, summed on the device, into the pinned lr.h (synchronises)
     bool lr_gram_host(const double* A, long long lda, const double* B, long long ldb, int p, int q) {
         lr_gram(A, lda, B, ldb, p, q, 1);
-        hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lr_part, lr_nslab(), (long long)p, (long long)p * q, p, q, (const double*)nullptr, lr_T);
+        hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lr.part, lr.nslab(), (long long)p, (long long)p * q, p, q, (const double*)nullptr, lr.T);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(lr_h, lr_T, (size_t)p * q * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(lr.h, lr.T, (size_t)p * q * sizeof(double), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
         return true;
     }
-    // Z (n x p) <- the columns of A (lr_rows x p) padded with zero rows, on the solver's stream
+    // Z (n x p) <- the columns of A (lr.rows x p) padded with zero rows, on the solver's stream
     bool lr_pad(double* Z, const double* A, int p) {
         const size_t n = S->n;
         HIPCHK(hipMemsetAsync(Z, 0, n * (size_t)p * sizeof(double), stream));
-        if (lr_rows > 0) HIPCHK(hipMemcpy2DAsync(Z, n * sizeof(double), A, (size_t)lr_rows * sizeof(double), (size_t)lr_rows * sizeof(double), p, hipMemcpyDeviceToDevice, stream));
+        if (lr.rows > 0) HIPCHK(hipMemcpy2DAsync(Z, n * sizeof(double), A, (size_t)lr.rows * sizeof(double), (size_t)lr.rows * sizeof(double), p, hipMemcpyDeviceToDevice, stream));
         return true;
     }
     // which: 0 = the update is in force, 1 / 2 = M1 / M2 is not positive definite (K~ has not K's inertia); false: an error
@@ -1457,60 +1460,60 @@ public:
         DeviceGuard guard(dev);
         *which = 0;
         if (!ready) { if (err_.empty()) err_ = "lowrank_update: solver not set up"; return false; }
-        if (!lr_set) { err_ = "lowrank_update: lowrank_set first"; return false; }
-        lr_ok = false;
+        if (!lr.set) { err_ = "lowrank_update: lowrank_set first"; return false; }
+        lr.ok = false;
         const auto t0 = std::chrono::steady_clock::now();
-        const int n = S->n, nv = lr_nv, nu = lr_nu;
+        const int n = S->n, nv = lr.nv, nu = lr.nu;
         double M[LR_MAX * LR_MAX], Cm[LR_MAX * LR_MAX];
         // The inner solves are the existing nrhs > 1 path.  With several solve contexts their columns run on the contexts' streams; solve_device makes
         // the solver's stream wait for every context's `done` event before it returns, and -- timed -- synchronises: what follows here on `stream`
         // (Gram, apply) is ordered behind all columns.
         if (n > 0 && nv > 0) {
-            if (!lr_pad(lr_Z1, lr_V, nv) || !solve_device(nv, lr_Z1, n, lr_Z1, n, true)) return false;
-            if (!lr_gram_host(lr_V, lr_rows, lr_Z1, n, nv, nv)) return false;
-            lr_shifted_sym(lr_h, nv, 1.0, M);
+            if (!lr_pad(lr.Z1, lr.V, nv) || !solve_device(nv, lr.Z1, n, lr.Z1, n, true)) return false;
+            if (!lr_gram_host(lr.V, lr.rows, lr.Z1, n, nv, nv)) return false;
+            lr_shifted_sym(lr.h, nv, 1.0, M);
             if (!lr_cholesky(M, nv)) { *which = 1; return true; }
-            HIPCHK(hipMemcpyAsync(lr_L1, M, (size_t)nv * nv * sizeof(double), hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemcpyAsync(lr.L1, M, (size_t)nv * nv * sizeof(double), hipMemcpyHostToDevice, stream));
             HIPCHK(hipStreamSynchronize(stream));      // (M is pageable and is written again below)
         }
         if (n > 0 && nu > 0) {
-            if (!lr_pad(lr_Z2, lr_U, nu) || !solve_device(nu, lr_Z2, n, lr_Z2, n, true)) return false;      // W1
+            if (!lr_pad(lr.Z2, lr.U, nu) || !solve_device(nu, lr.Z2, n, lr.Z2, n, true)) return false;      // W1
             if (nv > 0) {
-                if (!lr_gram_host(lr_Z1, n, lr_U, lr_rows, nv, nu)) return false;                          // Z1^T U
-                for (int e = 0; e < nv * nu; ++e) Cm[e] = lr_h[e];
+                if (!lr_gram_host(lr.Z1, n, lr.U, lr.rows, nv, nu)) return false;                          // Z1^T U
+                for (int e = 0; e < nv * nu; ++e) Cm[e] = lr.h[e];
                 lr_cholesky_solve(M, nv, Cm, nu);                                                           // C = M1^-1 (Z1^T U)
-                HIPCHK(hipMemcpyAsync(lr_T, Cm, (size_t)nv * nu * sizeof(double), hipMemcpyHostToDevice, stream));
-                hipLaunchKernelGGL(k_lr_apply, dim3((n + 255) / 256), dim3(256), 0, stream, lr_Z2, (long long)n, (const double*)lr_Z1, (long long)n, (const double*)lr_T, (long long)n, nv, nu, -1.0);      // Z2 = W1 - Z1 C
+                HIPCHK(hipMemcpyAsync(lr.T, Cm, (size_t)nv * nu * sizeof(double), hipMemcpyHostToDevice, stream));
+                hipLaunchKernelGGL(k_lr_apply, dim3((n + 255) / 256), dim3(256), 0, stream, lr.Z2, (long long)n, (const double*)lr.Z1, (long long)n, (const double*)lr.T, (long long)n, nv, nu, -1.0);      // Z2 = W1 - Z1 C
                 HIPCHK(hipGetLastError());
-                HIPCHK(hipStreamSynchronize(stream));  // (Cm is pageable; lr_T is written again by the next Gram)
+                HIPCHK(hipStreamSynchronize(stream));  // (Cm is pageable; lr.T is written again by the next Gram)
             }
-            if (!lr_gram_host(lr_U, lr_rows, lr_Z2, n, nu, nu)) return false;
-            lr_shifted_sym(lr_h, nu, -1.0, M);
+            if (!lr_gram_host(lr.U, lr.rows, lr.Z2, n, nu, nu)) return false;
+            lr_shifted_sym(lr.h, nu, -1.0, M);
             if (!lr_cholesky(M, nu)) { *which = 2; return true; }
-            HIPCHK(hipMemcpyAsync(lr_L2, M, (size_t)nu * nu * sizeof(double), hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemcpyAsync(lr.L2, M, (size_t)nu * nu * sizeof(double), hipMemcpyHostToDevice, stream));
             HIPCHK(hipStreamSynchronize(stream));
         }
-        lr_ok = true; lr_at = factor_count;
-        lr_update_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        lr.ok = true; lr.at = factor_count;
+        lr.update_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         return true;
     }
     // the two corrections of nrhs solution columns X (leading dimension ldx), enqueued on the solver's stream: three launches per half, no host round trip
     bool lr_correct(double* X, long long ldx, int nrhs) {
         const long long n = S->n;
-        const int nslab = lr_nslab(), ga = (int)((n + 255) / 256);
+        const int nslab = lr.nslab(), ga = (int)((n + 255) / 256);
         if (n == 0) return true;
         for (int c0 = 0; c0 < nrhs; c0 += LR_MAX) {
             const int nc = std::min(LR_MAX, nrhs - c0);
             double* Xc = X + (long long)c0 * ldx;
-            if (lr_nv > 0) {
-                lr_gram(lr_V, lr_rows, Xc, ldx, lr_nv, 1, nc);
-                hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lr_part, nslab, (long long)nslab * lr_nv, (long long)lr_nv, lr_nv, nc, (const double*)lr_L1, lr_T);
-                hipLaunchKernelGGL(k_lr_apply, dim3(ga), dim3(256), 0, stream, Xc, ldx, (const double*)lr_Z1, n, (const double*)lr_T, n, lr_nv, nc, -1.0);
+            if (lr.nv > 0) {
+                lr_gram(lr.V, lr.rows, Xc, ldx, lr.nv, 1, nc);
+                hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lr.part, nslab, (long long)nslab * lr.nv, (long long)lr.nv, lr.nv, nc, (const double*)lr.L1, lr.T);
+                hipLaunchKernelGGL(k_lr_apply, dim3(ga), dim3(256), 0, stream, Xc, ldx, (const double*)lr.Z1, n, (const double*)lr.T, n, lr.nv, nc, -1.0);
             }
-            if (lr_nu > 0) {
-                lr_gram(lr_U, lr_rows, Xc, ldx, lr_nu, 1, nc);
-                hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lr_part, nslab, (long long)nslab * lr_nu, (long long)lr_nu, lr_nu, nc, (const double*)lr_L2, lr_T);
-                hipLaunchKernelGGL(k_lr_apply, dim3(ga), dim3(256), 0, stream, Xc, ldx, (const double*)lr_Z2, n, (const double*)lr_T, n, lr_nu, nc, 1.0);
+            if (lr.nu > 0) {
+                lr_gram(lr.U, lr.rows, Xc, ldx, lr.nu, 1, nc);
+                hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lr.part, nslab, (long long)nslab * lr.nu, (long long)lr.nu, lr.nu, nc, (const double*)lr.L2, lr.T);
+                hipLaunchKernelGGL(k_lr_apply, dim3(ga), dim3(256), 0, stream, Xc, ldx, (const double*)lr.Z2, n, (const double*)lr.T, n, lr.nu, nc, 1.0);
             }
         }
         HIPCHK(hipGetLastError());
@@ -1518,14 +1521,14 @@ public:
     }
     // resid[0:rows] += V (V^T res[0:rows]) - U (U^T res[0:rows])   (the x rows of the unreduced residual; W holds B0 only)
     bool lr_residual(const double* res, double* resid) {
-        if (lr_rows == 0) return true;
-        const int ga = (lr_rows + 255) / 256;
+        if (lr.rows == 0) return true;
+        const int ga = (lr.rows + 255) / 256;
         for (int half = 0; half < 2; ++half) {
-            const int p = half == 0 ? lr_nv : lr_nu; const double* A = half == 0 ? lr_V : lr_U;
+            const int p = half == 0 ? lr.nv : lr.nu; const double* A = half == 0 ? lr.V : lr.U;
             if (p == 0) continue;
-            lr_gram(A, lr_rows, res, lr_rows, p, 1, 1);
-            hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lr_part, lr_nslab(), (long long)lr_nslab() * p, (long long)p, p, 1, (const double*)nullptr, lr_T);
-            hipLaunchKernelGGL(k_lr_apply, dim3(ga), dim3(256), 0, stream, resid, (long long)lr_rows, A, (long long)lr_rows, (const double*)lr_T, (long long)lr_rows, p, 1, half == 0 ? 1.0 : -1.0);
+            lr_gram(A, lr.rows, res, lr.rows, p, 1, 1);
+            hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lr.part, lr.nslab(), (long long)lr.nslab() * p, (long long)p, p, 1, (const double*)nullptr, lr.T);
+            hipLaunchKernelGGL(k_lr_apply, dim3(ga), dim3(256), 0, stream, resid, (long long)lr.rows, A, (long long)lr.rows, (const double*)lr.T, (long long)lr.rows, p, 1, half == 0 ? 1.0 : -1.0);
         }
         HIPCHK(hipGetLastError());
         return true;
@@ -1558,101 +1561,80 @@ public:
         return true;
     }
     void lowrank_info(int* rows, int* nv, int* nu, int* current, double* update_ms) const {
-        if (rows) *rows = lr_set ? lr_rows : 0; if (nv) *nv = lr_set ? lr_nv : 0; if (nu) *nu = lr_set ? lr_nu : 0;
-        if (current) *current = lr_current() ? 1 : 0; if (update_ms) *update_ms = lr_set ? lr_update_ms : 0.0;
+        if (rows) *rows = lr.set ? lr.rows : 0; if (nv) *nv = lr.set ? lr.nv : 0; if (nu) *nu = lr.set ? lr.nu : 0;
+        if (current) *current = lr_current() ? 1 : 0; if (update_ms) *update_ms = lr.set ? lr.update_ms : 0.0;
     }
 
     // ---------------- limited-memory BFGS: the (s, y) history on the device, V and U formed there (IpLimMemQuasiNewtonUpdater.cpp) ----------------
-    // S, Y (rows x max_history, a ring of column slots; logical column j = slot (lb_head + j) % lb_max) stay on the device until lbfgs_define /
-    // lbfgs_clear; a push moves two vectors: k_lb_dots + k_lr_reduce give the 2 m + 3 dots (ONE download, ONE synchronisation), lbfgs_host.h does the
-    // skip test, sigma, the augment / shift of D, L, S^T S and the coefficients d, C, Lbar, and k_lb_form writes the pair into its slot and V, U into the
-    // low-rank update's own buffers: outcome 0 is lowrank_set(rows, m, V, m, U) with these columns.  Caller's numbering, like own_lr: survives a restructure.
-    // lb_type 1, limited-memory SR1 (:523-671): the same dots, D, L, S^T S; the host works on COPIES (sigma, then the eigen-split of Z,
-    // lb_sr1_coefficients) and commits them only when the split rule passed, so a skipped push moves nothing but the counter; k_lb_form_sr1 forms
-    // V (m - nneg columns) and U (nneg).  One stored push can be taken back (lbfgs_undo: the reference's RestoreInternalDataBackup): the state before
-    // it is kept in lb_bk, and the ring has lb_max + 1 slots, so the pair that push evicted is still in its slot.
-    bool lb_defined = false;
-    int lb_type = 0, lb_slots = 0, lb_nneg = 0;
-    double lb_E[LB_MAX] = {}, lb_Qs[LB_MAX * LB_MAX] = {};
-    struct LbBackup { bool valid = false; int m = 0, head = 0, nneg = 0, skipped = 0; double sig = 1.0, D[LB_MAX] = {}, L[LB_MAX * LB_MAX] = {}, STS[LB_MAX * LB_MAX] = {}, E[LB_MAX] = {}, Qs[LB_MAX * LB_MAX] = {}; } lb_bk;
-    int lb_rows = 0, lb_max = 0, lb_init = 0, lb_m = 0, lb_head = 0, lb_skipped = 0;
-    double lb_init_val = 1.0, lb_smin = 1e-8, lb_smax = 1e8, lb_sig = 1.0, lb_push_ms = 0;
-    double *lb_S = nullptr, *lb_Y = nullptr, *lb_sy = nullptr, *lb_part = nullptr, *lb_T = nullptr, *lb_coef = nullptr, *lb_h = nullptr, *lb_hc = nullptr;
-    double lb_D[LB_MAX] = {}, lb_L[LB_MAX * LB_MAX] = {}, lb_STS[LB_MAX * LB_MAX] = {};
-    static constexpr int LB_NCOEF = LB_MAX + 2 * LB_MAX * LB_MAX;
-    int lb_nslab() const { return std::max(1, (lb_rows + LR_SLAB - 1) / LR_SLAB); }
-    LbRing lb_ring(int m) const { LbRing R; R.m = m; for (int j = 0; j < LB_MAX; ++j) R.slot[j] = (unsigned char)((lb_head + j) % std::max(lb_slots, 1)); return R; }
-    void lb_forget() { lb_m = lb_head = lb_skipped = lb_nneg = 0; lb_sig = lb_init_val; lb_bk.valid = false; }
-    void lbfgs_clear() { own_lb.clear(); lb_defined = false; lb_rows = lb_max = lb_slots = lb_type = 0; lb_push_ms = 0; lb_forget(); lb_S = lb_Y = lb_sy = lb_part = lb_T = lb_coef = lb_h = lb_hc = nullptr; }
+    // S, Y (rows x slots, a ring of column slots; logical column j = slot lb_slot(par, st, j)) stay on the device until lbfgs_define / lbfgs_clear; a
+    // push moves two vectors: k_lb_dots + k_lr_reduce give the 2 m + 3 dots (ONE download, ONE synchronisation), the transition of lbfgs_host.h
+    // (lb_push_bfgs / lb_push_sr1: no device in there) does the skip test, sigma, the augment / shift of D, L, S^T S, the ring head and the coefficients,
+    // and k_lb_form writes the pair into its slot and V, U into the low-rank update's own buffers: outcome 0 is lowrank_set(rows, m, V, m, U) with these
+    // columns.  Caller's numbering, like own_lr: survives a restructure.
+    // par.type 1, limited-memory SR1 (:523-671): the same dots; the transition works on a copy of the state and commits it only when the split rule
+    // passed, so a skipped push moves nothing but the counter; k_lb_form_sr1 forms V (m - nneg columns) and U (nneg).  One stored push can be taken back
+    // (lbfgs_undo: the reference's RestoreInternalDataBackup): the state before it is kept in lb.backup, and the ring has max_history + 1 slots, so the
+    // pair that push evicted is still in its slot.
+    static_assert(LB_MAX == LBH_MAX, "the kernels and lbfgs_host.h agree on the number of pairs");
+    struct History {                           // everything of the history but its arena (own_lb): lbfgs_clear() is own_lb.clear(); lb = {};
+        bool defined = false; int rows = 0; double push_ms = 0;
+        LbParams par; LbState st, backup; bool backup_valid = false;      // backup: the state before the last stored SR1 push, while that can be undone
+        double *S = nullptr, *Y = nullptr, *sy = nullptr, *part = nullptr, *T = nullptr, *coef = nullptr, *h = nullptr, *hc = nullptr;
+        int nslab() const { return std::max(1, (rows + LR_SLAB - 1) / LR_SLAB); }
+    } lb;
+    LbRing lb_ring(int m) const { LbRing R; R.m = m; for (int j = 0; j < LB_MAX; ++j) R.slot[j] = (unsigned char)lb_slot(lb.par, lb.st, j); return R; }      // (a defined history: slots >= 1)
+    void lb_forget() { lb.st = lb_fresh(lb.par); lb.backup_valid = false; }
+    void lbfgs_clear() { own_lb.clear(); lb = {}; }
     bool lbfgs_define(int rows, int max_history, int init, double init_val, double smin, double smax, int type) {
         DeviceGuard guard(dev);
         if (!ready) { if (err_.empty()) err_ = "lbfgs_define: solver not set up"; return false; }
         if (multi) { err_ = "lbfgs_define: not supported on a multi-GPU handle"; return false; }
         HIPCHK(hipStreamSynchronize(stream));
         lbfgs_clear();
-        lb_rows = rows; lb_max = max_history; lb_init = init; lb_init_val = init_val; lb_smin = smin; lb_smax = smax;
-        lb_type = type; lb_slots = max_history + (type == 1 ? 1 : 0);      // (SR1: the evicted pair survives the push that evicts it)
+        lb.rows = rows; lb.par = lb_params(type, max_history, init, init_val, smin, smax); lb_forget();
         DeviceOwner& O = own_lb;
-        if (!O.zeroed(&lb_S, (size_t)rows * lb_slots) || !O.zeroed(&lb_Y, (size_t)rows * lb_slots) || !O.raw(&lb_sy, 2 * (size_t)rows) ||
-            !O.raw(&lb_part, (size_t)lb_nslab() * LB_NOUT) || !O.raw(&lb_T, LB_NOUT) || !O.raw(&lb_coef, LB_NCOEF) ||
-            !O.pinned(&lb_h, LB_NOUT) || !O.pinned(&lb_hc, LB_NCOEF)) { lbfgs_clear(); return false; }
+        if (!O.zeroed(&lb.S, (size_t)rows * lb.par.slots) || !O.zeroed(&lb.Y, (size_t)rows * lb.par.slots) || !O.raw(&lb.sy, 2 * (size_t)rows) ||
+            !O.raw(&lb.part, (size_t)lb.nslab() * LB_NOUT) || !O.raw(&lb.T, LB_NOUT) || !O.raw(&lb.coef, LBH_NCOEF) ||
+            !O.pinned(&lb.h, LB_NOUT) || !O.pinned(&lb.hc, LBH_NCOEF)) { lbfgs_clear(); return false; }
         HIPCHK(hipDeviceSynchronize());            // (the zero fills ran on the default stream: device_owner.h)
-        lb_forget();
-        lb_defined = true;
+        lb.defined = true;
         return true;
     }
     bool lbfgs_reset() {
         DeviceGuard guard(dev);
-        if (!lb_defined) { err_ = "lbfgs_reset: lbfgs_define first"; return false; }
+        if (!lb.defined) { err_ = "lbfgs_reset: lbfgs_define first"; return false; }
         HIPCHK(hipStreamSynchronize(stream));
         lb_forget();
         lowrank_clear();
         return true;
     }
-    template <int KP> void lb_launch_dots(const double* ds, const double* dy) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_dots<KP>), dim3(lb_nslab()), dim3(256), 0, stream, (const double*)lb_S, (const double*)lb_Y, (long long)lb_rows, ds, dy, lb_rows, lb_ring(lb_m), lb_part);
+    // the history kernels are templates on the unroll bound KP = 8 / 16 / 32 >= m: the one place that picks it, f(std::integral_constant<int, KP>)
+    template <class F> static void lb_with_kp(int m, F&& f) {
+        if (m <= 8) f(std::integral_constant<int, 8>{}); else if (m <= 16) f(std::integral_constant<int, 16>{}); else f(std::integral_constant<int, 32>{});
     }
-    template <int KP> void lb_launch_form(const double* ds, const double* dy) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_form<KP>), dim3((lb_rows + 255) / 256), dim3(256), 0, stream, lb_S, lb_Y, (long long)lb_rows, ds, dy, lb_rows, lb_ring(lb_m),
-                           (const double*)lb_coef, lb_sig, lr_V, lr_U, (long long)lb_rows);
+    // ds == nullptr: no new pair, every column comes from its slot (undo).  lr.V, lr.U must have the shape (lb.rows, m - nneg, nneg).
+    void lb_launch_form_sr1(const double* ds, const double* dy) {
+        lb_with_kp(lb.st.m, [&](auto kp) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_form_sr1<decltype(kp)::value>), dim3((lb.rows + 255) / 256), dim3(256), 0, stream, lb.S, lb.Y, (long long)lb.rows,
+                                                              ds, dy, lb.rows, lb_ring(lb.st.m), (const double*)lb.coef, lb.st.sigma, lb.st.nneg, lr.V, lr.U, (long long)lb.rows); });
     }
-    // s == nullptr: no new pair, every column comes from its slot (undo).  lr_V, lr_U must have the shape (lb_rows, lb_m - lb_nneg, lb_nneg).
-    template <int KP> void lb_launch_form_sr1(const double* ds, const double* dy) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_form_sr1<KP>), dim3((lb_rows + 255) / 256), dim3(256), 0, stream, lb_S, lb_Y, (long long)lb_rows, ds, dy, lb_rows, lb_ring(lb_m),
-                           (const double*)lb_coef, lb_sig, lb_nneg, lr_V, lr_U, (long long)lb_rows);
+    void lb_launch_dots(const double* ds, const double* dy) {
+        lb_with_kp(lb.st.m, [&](auto kp) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_dots<decltype(kp)::value>), dim3(lb.nslab()), dim3(256), 0, stream, (const double*)lb.S, (const double*)lb.Y, (long long)lb.rows,
+                                                              ds, dy, lb.rows, lb_ring(lb.st.m), lb.part); });
     }
-    // installs the columns of the current SR1 state (lb_m >= 1, lb_Qs, lb_nneg, lb_sig) as the low-rank update; nothing may be in flight
-    bool lb_install_sr1(const double* ds, const double* dy) {
-        if (!lr_shape(lb_rows, lb_m - lb_nneg, lb_nneg, lb_max)) return false;
-        std::copy(lb_Qs, lb_Qs + LB_MAX * LB_MAX, lb_hc);
-        HIPCHK(hipMemcpyAsync(lb_coef, lb_hc, LB_MAX * LB_MAX * sizeof(double), hipMemcpyHostToDevice, stream));
-        if (lb_m <= 8) lb_launch_form_sr1<8>(ds, dy); else if (lb_m <= 16) lb_launch_form_sr1<16>(ds, dy); else lb_launch_form_sr1<32>(ds, dy);
+    void lb_launch_form(const double* ds, const double* dy) {
+        lb_with_kp(lb.st.m, [&](auto kp) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_form<decltype(kp)::value>), dim3((lb.rows + 255) / 256), dim3(256), 0, stream, lb.S, lb.Y, (long long)lb.rows,
+                                                              ds, dy, lb.rows, lb_ring(lb.st.m), (const double*)lb.coef, lb.st.sigma, lr.V, lr.U, (long long)lb.rows); });
+    }
+    // installs the columns of the current state (st.m >= 1) as the low-rank update: its shape, the coefficients (BFGS: d, C, Lbar, which the transition
+    // wrote to lb.hc; SR1: st.Qs, and as the split nv + nu = m moves from push to push the buffers get room for max_history columns each), the form kernel.
+    // ds == nullptr (SR1 only): undo.  Nothing may be in flight.
+    bool lb_install(const double* ds, const double* dy) {
+        const LbState& st = lb.st; const bool sr1 = lb.par.type == 1;
+        if (!(sr1 ? lr_shape(lb.rows, st.m - st.nneg, st.nneg, lb.par.max_history) : lr_shape(lb.rows, st.m, st.m))) return false;
+        if (sr1) std::copy(st.Qs, st.Qs + LB_MAX * LB_MAX, lb.hc);
+        HIPCHK(hipMemcpyAsync(lb.coef, lb.hc, (size_t)(sr1 ? LB_MAX * LB_MAX : LBH_NCOEF) * sizeof(double), hipMemcpyHostToDevice, stream));
+        if (sr1) lb_launch_form_sr1(ds, dy); else lb_launch_form(ds, dy);
         HIPCHK(hipGetLastError());
-        return true;
-    }
-    // the host half of an SR1 push, behind the download of the dots: *outcome 0 stored and installed, 1 skipped (only the counter moved)
-    bool lb_push_sr1(const double* ds, const double* dy, bool device, int m0, double ss, double sy, double yy, int* outcome) {
-        if (!std::isfinite(ss) || !std::isfinite(sy) || !std::isfinite(yy)) { ++lb_skipped; lb_bk.valid = false; return true; }
-        double D[LB_MAX], L[LB_MAX * LB_MAX], STS[LB_MAX * LB_MAX], E[LB_MAX], Qs[LB_MAX * LB_MAX];
-        std::copy(lb_D, lb_D + LB_MAX, D); std::copy(lb_L, lb_L + LB_MAX * LB_MAX, L); std::copy(lb_STS, lb_STS + LB_MAX * LB_MAX, STS);
-        const int m1 = lb_store(m0, lb_max, D, L, STS, lb_h, lb_h + m0, ss, sy);
-        const double sig = lb_sr1_sigma(lb_init, lb_init_val, m1, ss, sy, yy);
-        std::fill(Qs, Qs + LB_MAX * LB_MAX, 0.0); std::fill(E, E + LB_MAX, 0.0);
-        int nneg = 0;
-        const int r = lb_sr1_coefficients(m1, STS, L, LB_MAX, D, sig, E, Qs, LB_MAX, &nneg);
-        if (r == LB_SR1_FAILED) { err_ = "lbfgs_push: the eigen-solver of the SR1 split did not converge in " + std::to_string(LBH_JACOBI_SWEEPS) + " sweeps"; return false; }
-        if (r == LB_SR1_SKIP) { ++lb_skipped; lb_bk.valid = false; return true; }
-        LbBackup& B = lb_bk;                                               // the state before the commit: what lbfgs_undo restores
-        B.valid = true; B.m = lb_m; B.head = lb_head; B.nneg = lb_nneg; B.skipped = lb_skipped; B.sig = lb_sig;
-        std::copy(lb_D, lb_D + LB_MAX, B.D); std::copy(lb_L, lb_L + LB_MAX * LB_MAX, B.L); std::copy(lb_STS, lb_STS + LB_MAX * LB_MAX, B.STS);
-        std::copy(lb_E, lb_E + LB_MAX, B.E); std::copy(lb_Qs, lb_Qs + LB_MAX * LB_MAX, B.Qs);
-        if (m0 == lb_max) lb_head = (lb_head + 1) % lb_slots;
-        lb_m = m1; lb_sig = sig; lb_nneg = nneg; lb_skipped = 0;
-        std::copy(D, D + LB_MAX, lb_D); std::copy(L, L + LB_MAX * LB_MAX, lb_L); std::copy(STS, STS + LB_MAX * LB_MAX, lb_STS);
-        std::copy(E, E + LB_MAX, lb_E); std::copy(Qs, Qs + LB_MAX * LB_MAX, lb_Qs);
-        if (!lb_install_sr1(ds, dy)) return false;
-        if (device) HIPCHK(hipStreamSynchronize(stream));      // (the caller's vectors are free again when the call returns)
-        *outcome = 0;
         return true;
     }
     // takes the last stored SR1 push back: *undone 1, or 0 when there is nothing to undo (then nothing changes)
@@ -1660,98 +1642,84 @@ public:
         DeviceGuard guard(dev);
         *undone = 0;
         if (!ready) { if (err_.empty()) err_ = "lbfgs_undo: solver not set up"; return false; }
-        if (!lb_defined) { err_ = "lbfgs_undo: lbfgs_define first"; return false; }
-        if (lb_type != 1) { err_ = "lbfgs_undo: only an SR1 history (lbfgs_define_sr1) can take a push back"; return false; }
-        if (!lb_bk.valid) return true;
-        HIPCHK(hipStreamSynchronize(stream));      // (the form kernel of the push reads lb_coef, a correction may read the columns about to be replaced)
-        const LbBackup& B = lb_bk;
-        lb_m = B.m; lb_head = B.head; lb_nneg = B.nneg; lb_sig = B.sig; lb_skipped = B.skipped + 1;
-        std::copy(B.D, B.D + LB_MAX, lb_D); std::copy(B.L, B.L + LB_MAX * LB_MAX, lb_L); std::copy(B.STS, B.STS + LB_MAX * LB_MAX, lb_STS);
-        std::copy(B.E, B.E + LB_MAX, lb_E); std::copy(B.Qs, B.Qs + LB_MAX * LB_MAX, lb_Qs);
-        lb_bk.valid = false;
-        if (lb_m == 0) lowrank_clear();
+        if (!lb.defined) { err_ = "lbfgs_undo: lbfgs_define first"; return false; }
+        if (lb.par.type != 1) { err_ = "lbfgs_undo: only an SR1 history (lbfgs_define_sr1) can take a push back"; return false; }
+        if (!lb.backup_valid) return true;
+        HIPCHK(hipStreamSynchronize(stream));      // (the form kernel of the push reads lb.coef, a correction may read the columns about to be replaced)
+        lb_undo(lb.st, lb.backup, lb.backup_valid);
+        if (lb.st.m == 0) lowrank_clear();
         else {
-            if (!lb_install_sr1(nullptr, nullptr)) return false;
+            if (!lb_install(nullptr, nullptr)) return false;
             HIPCHK(hipStreamSynchronize(stream));
         }
         *undone = 1;
         return true;
     }
     void lbfgs_sr1_info(int* type, int* nneg, int* can_undo, double* E) const {
-        const bool sr1 = lb_defined && lb_type == 1;
-        if (type) *type = lb_defined ? lb_type : 0; if (nneg) *nneg = sr1 ? lb_nneg : 0; if (can_undo) *can_undo = sr1 && lb_bk.valid ? 1 : 0;
-        if (E && sr1) for (int j = 0; j < lb_m; ++j) E[j] = lb_E[j];
+        const bool sr1 = lb.defined && lb.par.type == 1;
+        if (type) *type = lb.defined ? lb.par.type : 0; if (nneg) *nneg = sr1 ? lb.st.nneg : 0; if (can_undo) *can_undo = sr1 && lb.backup_valid ? 1 : 0;
+        if (E && sr1) for (int j = 0; j < lb.st.m; ++j) E[j] = lb.st.E[j];
     }
-    // s, y: host vectors (device = false: uploaded to the staging pair) or device vectors of lb_rows.  *outcome: 0 stored and installed, 1 skipped, 2 stored, M not positive definite
+    // s, y: host vectors (device = false: uploaded to the staging pair) or device vectors of lb.rows.  *outcome: 0 stored and installed, 1 skipped (only the
+    // counter moved), 2 (BFGS) stored, M not positive definite
     bool lbfgs_push(const double* s, const double* y, bool device, int* outcome) {
         DeviceGuard guard(dev);
         *outcome = 1;
         if (!ready) { if (err_.empty()) err_ = "lbfgs_push: solver not set up"; return false; }
-        if (!lb_defined) { err_ = "lbfgs_push: lbfgs_define first"; return false; }
+        if (!lb.defined) { err_ = "lbfgs_push: lbfgs_define first"; return false; }
         const auto t0 = std::chrono::steady_clock::now();
-        const size_t vb = (size_t)lb_rows * sizeof(double);
+        const size_t vb = (size_t)lb.rows * sizeof(double);
         const double *ds = s, *dy = y;
         if (!device) {
-            HIPCHK(hipMemcpyAsync(lb_sy, s, vb, hipMemcpyHostToDevice, stream));
-            HIPCHK(hipMemcpyAsync(lb_sy + lb_rows, y, vb, hipMemcpyHostToDevice, stream));
-            ds = lb_sy; dy = lb_sy + lb_rows;
+            HIPCHK(hipMemcpyAsync(lb.sy, s, vb, hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemcpyAsync(lb.sy + lb.rows, y, vb, hipMemcpyHostToDevice, stream));
+            ds = lb.sy; dy = lb.sy + lb.rows;
         }
-        const int m0 = lb_m, nout = 2 * m0 + 3;
-        if (m0 <= 8) lb_launch_dots<8>(ds, dy); else if (m0 <= 16) lb_launch_dots<16>(ds, dy); else lb_launch_dots<32>(ds, dy);
-        hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lb_part, lb_nslab(), 0LL, (long long)nout, nout, 1, (const double*)nullptr, lb_T);
+        const int m0 = lb.st.m, nout = 2 * m0 + 3;
+        lb_launch_dots(ds, dy);
+        hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lb.part, lb.nslab(), 0LL, (long long)nout, nout, 1, (const double*)nullptr, lb.T);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(lb_h, lb_T, (size_t)nout * sizeof(double), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));      // the one synchronisation of a push (it also ends the form kernel of the push before: lb_hc is free)
-        const double ss = lb_h[2 * m0], sy = lb_h[2 * m0 + 1], yy = lb_h[2 * m0 + 2];
-        auto done = [&] { lb_push_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); return true; };
-        if (lb_type == 1) return lb_push_sr1(ds, dy, device, m0, ss, sy, yy, outcome) && done();
-        if (lb_skip(ss, sy, yy)) { ++lb_skipped; return done(); }
-        lb_skipped = 0;
-        lb_sig = lb_sigma(lb_init, lb_init_val, lb_smin, lb_smax, ss, sy, yy);
-        if (lb_m == lb_max) lb_head = (lb_head + 1) % lb_max;
-        lb_m = lb_store(lb_m, lb_max, lb_D, lb_L, lb_STS, lb_h, lb_h + m0, ss, sy);
-        const LbRing R = lb_ring(lb_m);
-        std::fill(lb_hc, lb_hc + LB_NCOEF, 0.0);
-        if (!lb_coefficients(lb_m, lb_STS, lb_L, LB_MAX, lb_D, lb_sig, lb_hc, lb_hc + LB_MAX, lb_hc + LB_MAX + LB_MAX * LB_MAX, LB_MAX)) {
+        HIPCHK(hipMemcpyAsync(lb.h, lb.T, (size_t)nout * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));      // the one synchronisation of a push (it also ends the form kernel of the push before: lb.hc is free)
+        const double *sS = lb.h, *sY = lb.h + m0, ss = lb.h[2 * m0], sy = lb.h[2 * m0 + 1], yy = lb.h[2 * m0 + 2];
+        const int r = lb.par.type == 1 ? lb_push_sr1(lb.par, lb.st, lb.backup, lb.backup_valid, sS, sY, ss, sy, yy) : lb_push_bfgs(lb.par, lb.st, sS, sY, ss, sy, yy, lb.hc);
+        if (r == LB_PUSH_FAILED) { err_ = "lbfgs_push: the eigen-solver of the SR1 split did not converge in " + std::to_string(LBH_JACOBI_SWEEPS) + " sweeps"; return false; }
+        if (r == LB_PUSH_STORED) {                 // (nothing is in flight behind the synchronisation above)
+            if (!lb_install(ds, dy)) return false;
+        } else if (r == LB_PUSH_NOT_PD) {
             // the reference has stored the pair by now (:484-495): so have we; the installed columns stay what they were
-            double* slot = lb_S + (size_t)R.slot[lb_m - 1] * lb_rows; double* sloty = lb_Y + (size_t)R.slot[lb_m - 1] * lb_rows;
-            HIPCHK(hipMemcpyAsync(slot, ds, vb, hipMemcpyDeviceToDevice, stream));
-            HIPCHK(hipMemcpyAsync(sloty, dy, vb, hipMemcpyDeviceToDevice, stream));
-            if (device) HIPCHK(hipStreamSynchronize(stream));
-            *outcome = 2;
-            return done();
+            const size_t slot = (size_t)lb_slot(lb.par, lb.st, lb.st.m - 1) * lb.rows;
+            HIPCHK(hipMemcpyAsync(lb.S + slot, ds, vb, hipMemcpyDeviceToDevice, stream));
+            HIPCHK(hipMemcpyAsync(lb.Y + slot, dy, vb, hipMemcpyDeviceToDevice, stream));
         }
-        if (!lr_shape(lb_rows, lb_m, lb_m)) return false;      // (nothing is in flight behind the synchronisation above)
-        HIPCHK(hipMemcpyAsync(lb_coef, lb_hc, LB_NCOEF * sizeof(double), hipMemcpyHostToDevice, stream));
-        if (lb_m <= 8) lb_launch_form<8>(ds, dy); else if (lb_m <= 16) lb_launch_form<16>(ds, dy); else lb_launch_form<32>(ds, dy);
-        HIPCHK(hipGetLastError());
-        if (device) HIPCHK(hipStreamSynchronize(stream));      // (the caller's vectors are free again when the call returns)
-        *outcome = 0;
-        return done();
+        if (r != LB_PUSH_SKIPPED && device) HIPCHK(hipStreamSynchronize(stream));      // (the caller's vectors are free again when the call returns)
+        *outcome = r;
+        lb.push_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return true;
     }
     void lbfgs_info(int* rows, int* max_history, int* memory, double* sigma, int* skipped, double* push_ms) const {
-        if (rows) *rows = lb_defined ? lb_rows : 0; if (max_history) *max_history = lb_defined ? lb_max : 0; if (memory) *memory = lb_defined ? lb_m : 0;
-        if (sigma) *sigma = lb_defined ? lb_sig : 0.0; if (skipped) *skipped = lb_defined ? lb_skipped : 0; if (push_ms) *push_ms = lb_defined ? lb_push_ms : 0.0;
+        if (rows) *rows = lb.defined ? lb.rows : 0; if (max_history) *max_history = lb.defined ? lb.par.max_history : 0; if (memory) *memory = lb.defined ? lb.st.m : 0;
+        if (sigma) *sigma = lb.defined ? lb.st.sigma : 0.0; if (skipped) *skipped = lb.defined ? lb.st.skipped : 0; if (push_ms) *push_ms = lb.defined ? lb.push_ms : 0.0;
     }
     // what: 0 S, 1 Y (rows x memory, oldest first), 2 V, 3 U (the installed columns of the low-rank update), 4 D, 5 L, 6 S^T S (memory x memory); column-major, no padding
     bool lbfgs_get(int what, double* out, long long capacity) {
         DeviceGuard guard(dev);
-        if (!lb_defined) { err_ = "lbfgs_get: lbfgs_define first"; return false; }
-        const long long need = what <= 1 ? (long long)lb_rows * lb_m : what == 2 ? (lr_set ? (long long)lr_rows * lr_nv : 0) : what == 3 ? (lr_set ? (long long)lr_rows * lr_nu : 0)
-                             : what == 4 ? lb_m : (long long)lb_m * lb_m;
+        if (!lb.defined) { err_ = "lbfgs_get: lbfgs_define first"; return false; }
+        const int m = lb.st.m;
+        const long long need = what <= 1 ? (long long)lb.rows * m : what == 2 ? (lr.set ? (long long)lr.rows * lr.nv : 0) : what == 3 ? (lr.set ? (long long)lr.rows * lr.nu : 0)
+                             : what == 4 ? m : (long long)m * m;
         if (capacity < need) { err_ = "lbfgs_get: capacity is below the " + std::to_string(need) + " doubles of this array"; return false; }
         HIPCHK(hipStreamSynchronize(stream));
         if (what <= 1) {
-            const LbRing R = lb_ring(lb_m);
-            for (int j = 0; j < lb_m; ++j)
-                HIPCHK(hipMemcpy(out + (size_t)j * lb_rows, (what == 0 ? lb_S : lb_Y) + (size_t)R.slot[j] * lb_rows, (size_t)lb_rows * sizeof(double), hipMemcpyDeviceToHost));
+            for (int j = 0; j < m; ++j)
+                HIPCHK(hipMemcpy(out + (size_t)j * lb.rows, (what == 0 ? lb.S : lb.Y) + (size_t)lb_slot(lb.par, lb.st, j) * lb.rows, (size_t)lb.rows * sizeof(double), hipMemcpyDeviceToHost));
         } else if (what <= 3) {
-            if (need > 0) HIPCHK(hipMemcpy(out, what == 2 ? lr_V : lr_U, (size_t)need * sizeof(double), hipMemcpyDeviceToHost));
+            if (need > 0) HIPCHK(hipMemcpy(out, what == 2 ? lr.V : lr.U, (size_t)need * sizeof(double), hipMemcpyDeviceToHost));
         } else if (what == 4) {
-            for (int j = 0; j < lb_m; ++j) out[j] = lb_D[j];
+            for (int j = 0; j < m; ++j) out[j] = lb.st.D[j];
         } else {
-            const double* A = what == 5 ? lb_L : lb_STS;
-            for (int j = 0; j < lb_m; ++j) for (int i = 0; i < lb_m; ++i) out[i + (size_t)j * lb_m] = A[i + j * LB_MAX];
+            const double* A = what == 5 ? lb.st.L : lb.st.STS;
+            for (int j = 0; j < m; ++j) for (int i = 0; i < m; ++i) out[i + (size_t)j * m] = A[i + j * LB_MAX];
         }
         return true;
     }

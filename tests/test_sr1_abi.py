@@ -4,7 +4,8 @@ unanalysed and a multi-GPU handle, and -- with valid arguments and no device -- 
 nor a device: its split is held to the longdouble specification (tests/support/sr1_spec.py) by the project's rule e_lib <= 64 max(e_64, 2^-52), e the
 largest deviation relative to the largest entry and e_64 the float64 specification's own, on Z^-1 = Qs+ Qs+^T - Qs- Qs-^T and on the two halves
 separately (never column by column: sign and rotation of eigenvectors are not determined); it answers SINGULAR where the split rule says skip.
-The host header itself runs under AddressSanitizer and UBSan in a stand-alone program (tests/support/sr1_host_check.cpp)."""
+The host header itself runs under AddressSanitizer and UBSan in two stand-alone programs: the eigen-split (tests/support/sr1_host_check.cpp) and the
+state machine of a history, BFGS and SR1: push, skip, eviction, the spare slot and undo (tests/support/lbfgs_state_check.cpp)."""
 import ctypes as C
 import os
 import shutil
@@ -150,8 +151,8 @@ def test_the_zero_matrix_is_singular_and_m_33_is_fatal():
     assert C.CDLL(ipopt_amd.library_path()).mi355x_kkt_lbfgs_sr1_coefficients(33, None, None, None, C.c_double(1.0), None, None, None) == kkt.FATAL
 
 
-def test_the_host_header_is_clean_under_address_and_ub_sanitizers(tmp_path):
-    """a stand-alone program with its own main, on the CPU: nothing is loaded into python under a sanitizer"""
+def _run_host_program_under_sanitizers(tmp_path, name):
+    """tests/support/<name>.cpp, a stand-alone program with its own main, on the CPU: nothing is loaded into python under a sanitizer"""
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     if cxx is None:
         pytest.skip("no C++ compiler")
@@ -160,10 +161,19 @@ def test_the_host_header_is_clean_under_address_and_ub_sanitizers(tmp_path):
     if subprocess.run([cxx, *flags, str(probe), "-o", str(tmp_path / "probe")], capture_output=True).returncode != 0 or \
             subprocess.run([str(tmp_path / "probe")], capture_output=True).returncode != 0:
         pytest.skip("the compiler has no sanitizer runtime")
-    exe = tmp_path / "sr1_host_check"
-    build = subprocess.run([cxx, *flags, "-I", os.path.join(ROOT, "ipopt_amd", "csrc"), os.path.join(ROOT, "tests", "support", "sr1_host_check.cpp"), "-o", str(exe)],
+    exe = tmp_path / name
+    build = subprocess.run([cxx, *flags, "-I", os.path.join(ROOT, "ipopt_amd", "csrc"), os.path.join(ROOT, "tests", "support", name + ".cpp"), "-o", str(exe)],
                            capture_output=True, text=True)
     assert build.returncode == 0, build.stderr
     run = subprocess.run([str(exe)], capture_output=True, text=True)
     print(run.stdout, run.stderr)
     assert run.returncode == 0 and run.stdout.strip().endswith("ok")
+
+
+def test_the_host_header_is_clean_under_address_and_ub_sanitizers(tmp_path):
+    _run_host_program_under_sanitizers(tmp_path, "sr1_host_check")
+
+
+def test_the_history_state_machine_on_the_cpu_under_sanitizers(tmp_path):
+    """push, skip, eviction, the SR1 spare slot and undo of lbfgs_host.h against a model kept by the rule alone, D, L, S^T S bitwise against a recomputation"""
+    _run_host_program_under_sanitizers(tmp_path, "lbfgs_state_check")
