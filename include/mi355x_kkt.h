@@ -392,7 +392,22 @@ int  mi355x_kkt_get_symbolic(mi355x_kkt_handle h, int what, int* out, int64_t ca
  *   front), wave_mmax, wave_kmax};  "groups" 11 ints per level of the single-GPU / own-subtree grouped schedule {g0, g1, split, nrb, tiles64, tiles,
  *   la1, la2, p1t, la3, nsplit};  "path_scalars" {pair_solve, la_any, ints of the tile tables, grp_cut_level, solve_group, cb_window};
  *   "inputs" the settings the plan is built with {chain_solve, fuse_dt, fastpiv, asm_pull, leafchain, front_df, tfuse, fuse_upd, selfasm, grouped,
- *   xcd_tiles, lookahead, pair_solve, p1_small, la_wgs, la_min_nt, grp_rbw_max, chain_solve_maxc, fuse_dt_maxwg, la_min_tiles}. */
+ *   xcd_tiles, lookahead, pair_solve, p1_small, la_wgs, la_min_nt, grp_rbw_max, chain_solve_maxc, fuse_dt_maxwg, la_min_tiles, side_small}.
+ *   The factor schedule -- every launch and stream operation of a factorisation between the equilibration and the statistics, in issue order:
+ *   "factor.single.full" / "factor.single.opt" (one GPU: every strict launch / the optimistic schedule), "factor.local", "factor.stage<d>" (multi-rank),
+ *   13 ints per record {op, stream, kind, gx, gy, block, level, b0, lds, a0, a1, a2, a3}:
+ *   op  0 k_leaf_chain, 1 k_front_df, 2 k_front_dpp16, 3 k_front_reg<64,2>, 4 <64,4>, 5 <64,8>, 6 <256,6,true,4>, 7 <256,8,true>, 8 <256,6>, 9 <256,8>,
+ *       10 k_big_assemble, 11 k_big_assemble2, 12 k_grp_fused, 13 k_big_diag_trsm, 14 k_big_diag_reg<4>, 15 <4,1024>, 16 k_big_trsm<false>, 17 <true>,
+ *       18 k_big_schur64, 19 k_big_schur, 20 k_big_schur_p1, 21 k_big_schur_q, and the stream operations 22 fork (event A of (a0, level) recorded on the
+ *       main stream, the look-ahead stream waits for it), 23 fork-done (event B of (a0, level) recorded on the look-ahead stream), 24 join (the main
+ *       stream waits for event B of (a0, a1); level: where the join stands), 25 side-open, 26 side-close (the side stream of `level`);
+ *   stream 0 main, 1 look-ahead, 2 side;  kind: MI355X_KKT_KERNEL_* the profile books the launch under (-1: a stream operation);
+ *   gx, gy: the grid in workgroups -- but op 1: virtual workgroups (clamped to the resident ones at launch), op 19: 128 x 128 tiles, op 11: columns
+ *   (chunks of 16 per workgroup);  block: threads (0: the kernel's own: op 19);  b0: first launch-list entry;  lds: dynamic LDS bytes where the plan
+ *   knows them (ops 3-9, 11; the pivot-block and panel kernels size theirs at launch from a[]);  a0..a3, the kernel's integer arguments, per op:
+ *   0 {chains, last level}  1 {tab0, levels, virtual workgroups, last level}  2 {fronts, top_mode, raise-the-flag}  3-9 {flags}  10 {top_mode}
+ *   11 {top_mode, ldi, maxch}  12 {staged, rbw}  13 {row blocks, kk}  14-17 {kk}  19 {part}  21 {tiles of part 2}  22-24 {event index: 0 the
+ *   single-GPU schedule, 1 + i grouped schedule i;  24: a1 the level of the fork}. */
 int  mi355x_kkt_get_launch_plan(mi355x_kkt_handle h, int nranks, int rank, const char* what, int* out, int64_t capacity, int64_t* count);
 
 /* ---- measurement: device time per kernel kind (hip events around every launch of an eager, graph-less factor + one

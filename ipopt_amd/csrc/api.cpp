@@ -702,6 +702,18 @@ int mi355x_kkt_get_launch_plan(mi355x_kkt_handle h, int nranks, int rank, const 
         std::vector<int> v;
         auto put = [&](std::initializer_list<long long> x) { for (long long e : x) v.push_back((int)e); };
         const std::string w(what);
+        if (w.rfind("factor.", 0) == 0) {      // the factor schedule of one Sched, FACTOR_LAUNCH_INTS ints per record
+            const std::string f = w.substr(7);
+            int which = -1; bool optimistic = false;
+            if (f == "single.opt") { which = 0; optimistic = true; } else if (f == "single.full") which = 0; else if (f == "local") which = 1;
+            else if (f.rfind("stage", 0) == 0 && f.size() > 5) { const int d = atoi(f.c_str() + 5); if (d >= 0 && d < (int)P.stage.size()) which = 2 + d; }
+            if (which < 0 || (which > 0 && nranks == 1)) { h->err = "get_launch_plan: unknown factor schedule"; return MI355X_KKT_FATAL; }
+            for (const FactorLaunch& r : build_factor_schedule(P, h->sym, plan_inputs_from_env(nranks, rank, nranks > 1, 0), which, optimistic))
+                put({r.op, r.stream, r.kind, r.gx, r.gy, r.block, r.lv, r.b0, r.lds, r.a[0], r.a[1], r.a[2], r.a[3]});
+            *count = (int64_t)v.size();
+            if (out) { if ((int64_t)v.size() > cap) { h->err = "get_launch_plan: buffer too small"; return MI355X_KKT_FATAL; } std::copy(v.begin(), v.end(), out); }
+            return MI355X_KKT_SUCCESS;
+        }
         const Sched* sc = w.rfind("single.", 0) == 0 ? &P.single : w.rfind("local.", 0) == 0 ? &P.local : nullptr;
         if (w.rfind("stage", 0) == 0) { const int d = atoi(w.c_str() + 5); if (d >= 0 && d < (int)P.stage.size()) sc = &P.stage[d]; }
         const std::string field = sc ? w.substr(w.find('.') + 1) : w;
@@ -736,7 +748,7 @@ int mi355x_kkt_get_launch_plan(mi355x_kkt_handle h, int nranks, int rank, const 
         else if (w == "path_scalars") put({P.pair_solve, P.la_any, (long long)P.tile_tab.size(), h->sym.grp_cut_level, h->sym.solve_group, h->sym.cb_window});
         else if (w == "inputs") { const PlanInputs in = plan_inputs_from_env(nranks, rank, nranks > 1, 0);
             put({in.chain_solve, in.fuse_dt, in.fastpiv, in.asm_pull, in.leafchain, in.front_df, in.tfuse, in.fuse_upd, in.selfasm, in.grouped, in.xcd_tiles, in.lookahead, in.pair_solve, in.p1_small,
-                 in.la_wgs, in.la_min_nt, in.grp_rbw_max, in.chain_solve_maxc, in.fuse_dt_maxwg, std::min<long long>(in.la_min_tiles, 0x7fffffffll)}); }
+                 in.la_wgs, in.la_min_nt, in.grp_rbw_max, in.chain_solve_maxc, in.fuse_dt_maxwg, std::min<long long>(in.la_min_tiles, 0x7fffffffll), in.side_small}); }
         else { h->err = "get_launch_plan: unknown array"; return MI355X_KKT_FATAL; }
         *count = (int64_t)v.size();
         if (out) { if ((int64_t)v.size() > cap) { h->err = "get_launch_plan: buffer too small"; return MI355X_KKT_FATAL; } std::copy(v.begin(), v.end(), out); }

@@ -16,7 +16,7 @@ PlanInputs plan_inputs_from_env(int nranks, int rank, bool multi, int verbose)
     in.asm_pull = !knob_disabled("asm_pull"); in.leafchain = !knob_disabled("leafchain"); in.front_df = !knob_disabled("front_df");
     in.tfuse = !knob_disabled("tfuse"); in.fuse_upd = !knob_disabled("fuse_upd"); in.selfasm = !knob_disabled("selfasm");
     in.grouped = !knob_disabled("grouped"); in.xcd_tiles = !knob_disabled("xcd_tiles"); in.lookahead = !knob_disabled("lookahead");
-    in.pair_solve = !knob_disabled("pair_solve"); in.p1_small = !knob_disabled("p1_small");
+    in.pair_solve = !knob_disabled("pair_solve"); in.p1_small = !knob_disabled("p1_small"); in.side_small = !knob_disabled("side_small");
     in.la_wgs = (int)std::max(1ll, knob_int("la_wgs", in.la_wgs));
     in.la_min_nt = (int)std::max(3ll, knob_int("la_min_nt", in.la_min_nt));
     in.la_min_tiles = knob_int("la_min_tiles", in.la_min_tiles);     // (tests force 0)
@@ -611,6 +611,186 @@ LaunchPlan build_launch_plan(const Symbolic& Sy, const PlanInputs& in)
         r = std::max(r, front_lds(order_of(Sy, s), cols_of(Sy, s), Sy.sn_class[s] == FC_WAVE ? 32 : (Sy.sn_class[s] == FC_LDS64 ? 64 : 128)));
     }
     return P;
+}
+
+// ---- the factor schedule: which kernel runs, with what grid, LDS size, stream and stream order -- every condition of the factorisation's launches
+//      once, here (DESIGN.md "Where a launch is decided"); numeric.hip run_factor_list walks the list ----
+std::vector<FactorLaunch> build_factor_schedule(const LaunchPlan& P, const Symbolic& Sy, const PlanInputs& in, int which, bool optimistic)
+{
+    std::vector<FactorLaunch> out;
+    const Sched& sc = which == 0 ? P.single : which == 1 ? P.local : P.stage[which - 2];
+    if (sc.ptr.empty()) return out;                      // (a schedule this plan does not have: the multi-rank ones of a single-GPU plan)
+    const int NL = P.nlevels;
+    const bool sg = which == 0;                          // single-GPU schedule: the buckets are sorted by order; leaf chains, data-flow runs, side stream
+    const bool multi = in.multi, single = sg && !multi;
+    const int top_mode = which >= 2 ? 1 : 0;             // the replicated fronts of an exchange step
+    const int gi = top_mode ? 1 + (which - 2) : 0;       // the grouped schedule P.grp[gi] (the multi-GPU schedules have their own group lists)
+    int fork_ev = -1, fork_lv = -1;                      // the look-ahead fork that no join has waited for yet: its events (a[0], lv)
+    auto bucket0 = [&](int lv, int fc) { return sc.base + sc.ptr[(size_t)lv * FC_COUNT + fc]; };      // bucket (lv, fc) of sc is [bucket0(lv, fc), bucket0(lv, fc + 1)) of the launch list
+    auto put = [&](int op, int strm, int kind, int lv, int b0, int gx, int gy, int block, size_t lds, int a0 = 0, int a1 = 0, int a2 = 0, int a3 = 0) {
+        out.push_back(FactorLaunch{op, strm, kind, gx, gy, block, lv, b0, (int)lds, {a0, a1, a2, a3}}); };
+    // The look-ahead fork, behind part 1 on the main stream: A recorded there, part 2 of the fronts [b0, b0 + nb) on the second stream behind A (128 x 128
+    // tiles on 16 wavefronts, or quarter tiles on 4 wavefronts that fit on the CUs a k_grp_fused workgroup occupies: kernels_big.hip.inc k_big_schur_q / _w),
+    // B recorded behind it -- what join() makes the main stream wait for before a later launch may touch what part 2 reads or writes
+    auto fork = [&](int ev, int lv, int b0, int nb, int ntiles) {
+        const int nvirt = ((ntiles + 7) / 8) * 32;
+        const int wgs = (int)std::min<long long>(nvirt, 4ll * in.la_wgs);
+        put(FO_FORK, FS_MAIN, -1, lv, b0, 1, 1, 0, 0, ev);
+        put(FO_SCHUR_Q, FS_LOOKAHEAD, KK_BIG_SCHUR, lv, b0, wgs, nb, 256, 0, ntiles);
+        put(FO_FORK_DONE, FS_LOOKAHEAD, -1, lv, b0, 1, 1, 0, 0, ev);
+        fork_ev = ev; fork_lv = lv;
+    };
+    auto join = [&](int lv) { if (fork_ev >= 0) { put(FO_JOIN, FS_MAIN, -1, lv, 0, 1, 1, 0, 0, fork_ev, fork_lv); fork_ev = -1; } };      // (a[1]: the level of the fork; lv: where the join stands)
+    // The column-chunk kernel pays where a level is MANY fronts of a few hundred rows (short columns: the one-wavefront-per-column kernel runs at the
+    // latency of its load chain there) and every front can take its fast path (at most ASM_MAXCH children to pull, not an in-place link with other
+    // children, no arena): measured 4.1 -> 2.0 ms per factorisation on synth_1e6, but 3.4 -> 8.7 ms on MBndryCntrl_3D 30, whose levels are a
+    // handful of fronts of ~1000 rows with a dozen children each -- there the column kernel has four times the workgroups and no preamble.
+    auto assemble = [&](int strm, int lv, int mm, int nfronts, int b0) {
+        const int ldi = (mm + 15) & ~15;                    // the children's inverse row maps of one front in LDS: ASM_MAXCH x ldi ints (78 KiB at the largest front of synth_1e6)
+        // (... which has to FIT: a level of >= 32 fast-path fronts whose largest order exceeds ~6 780 -- a 3-D problem, or fronts enlarged by a
+        // delayed-pivot edit -- would make the launch fail instead of falling back to the column kernel: ADVICE r04)
+        // Round 5: a front whose contribution block is formed by its update (asmcut) has only its panel columns assembled; a launch of such fronts has no
+        // workgroups behind the largest asmcut.  (MI355X_KKT_ASM2_WIDE: this kernel also for levels of a few dozen fronts with up to ASM_MAXCH = 16 children each
+        // once only their panel columns are assembled -- the MBndryCntrl_3D family; measured slower there than the column kernel, 7.65 against 7.16 ms.)
+        bool v2 = !top_mode;
+        int maxch = 1, ncut = 0, cutmax = 0;
+        for (int q = b0; q < b0 + nfronts && v2; ++q) { v2 = P.asm_fast_ok[q] != 0; maxch = std::max(maxch, (int)P.asm_fast_ok[q]); if (P.asmcut[q]) { ++ncut; cutmax = std::max(cutmax, P.asmcut[q] > 0 ? P.asmcut[q] : 0); } }
+        v2 = v2 && (size_t)maxch * ldi * sizeof(int) <= (size_t)158 * 1024 && (nfronts >= 32 && maxch <= 6);
+        if (!v2) { put(FO_ASSEMBLE, strm, KK_BIG_ASSEMBLE, lv, b0, (mm + 3) / 4, nfronts, 256, 0, top_mode); return; }
+        const int ncols = (ncut == nfronts) ? std::min(mm, cutmax) : mm;      // (every front stops at its asmcut: no workgroups for the columns behind the largest of them)
+        if (ncols <= 0) return;                                               // (every front of the list has its whole block formed by its update: nothing to assemble -- a grid of 0 workgroups is refused by the runtime, met on the multi-rank schedule)
+        put(FO_ASSEMBLE2, strm, KK_BIG_ASSEMBLE, lv, b0, ncols, nfronts, 256, (size_t)maxch * ldi * sizeof(int), top_mode, ldi, maxch);
+    };
+    // the chain groups whose first link sits on level lv: pivot blocks + leading blocks, rows below, rank-(<= 256) updates
+    auto groups = [&](int strm, int lv) {
+        const GrpSched& G = P.grp[gi];
+        const int b0 = G.g0[lv], b1 = G.g1[lv], bs = b0 + G.split[lv];
+        if (b1 == b0) return;
+        {
+            // as many 64-row blocks per row-block workgroup as it takes for the launch to fit the chip (one workgroup per CU)
+            int rbw = 1;
+            while (rbw < in.grp_rbw_max && (b1 - b0) * (4 + (G.nrb[lv] + rbw - 1) / rbw) > 256) rbw *= 2;
+            const int nrbw = (G.nrb[lv] + rbw - 1) / rbw;
+            const int st = ((b1 - b0) * (4 + nrbw) <= 256) ? 1 : 0;
+            put(FO_GRP_FUSED, strm, KK_BIG_DIAG, lv, b0, b1 - b0, 4 + nrbw, 256, 0, st, rbw);
+        }
+        if (bs > b0 && G.tiles64[lv] > 0) put(FO_SCHUR64, strm, KK_BIG_SCHUR, lv, b0, G.tiles64[lv], bs - b0, 256, 0);
+        if (b1 == bs) return;
+        const int nb = b1 - bs;
+        join(lv);      // a full update may touch what an earlier part 2 is still writing
+        if (G.la2[lv] > 0) {      // (also while profile() records its events: the per-kernel times are those of the TIMED schedule, look-ahead stream included)
+            // part 1 in 64 x 64 tiles where the 128 x 128 ones would leave most of the chip idle (k_big_schur_p1); the fronts of the list that are not split
+            // get their whole update from a launch of their own then
+            if (in.p1_small && G.la1[lv] * nb <= 512) {
+                put(FO_SCHUR_P1, strm, KK_BIG_SCHUR, lv, bs, G.p1t[lv], nb, 1024, 0);
+                if (G.nsplit[lv] < nb) put(FO_SCHUR, strm, KK_BIG_SCHUR, lv, bs, G.la3[lv], nb, 0, 0, 4);
+            } else put(FO_SCHUR, strm, KK_BIG_SCHUR, lv, bs, G.la1[lv], nb, 0, 0, 1);
+            fork(1 + gi, lv, bs, nb, G.la2[lv]);
+        } else if (G.tiles[lv] > 0) put(FO_SCHUR, strm, KK_BIG_SCHUR, lv, bs, G.tiles[lv], nb, 0, 0, 0);
+    };
+    // the big-front launches of one level: assembly, pivot blocks and TRSM over the whole list [b0, b1); the trailing update with
+    // 64 x 64 tiles / 256 threads on the fronts [b0, bs) of order <= 1024 (a handful of tiles, K = 16..64 each) and with
+    // 128 x 128 tiles / 1024 threads on [bs, b1)
+    auto big = [&](int strm, int lv, int b0, int bs, int b1, int mm, int kk, int tiles_small, int tiles) {
+        const int nball = b1 - b0;
+        if (!(single && P.lv_asm_skip[lv])) assemble(strm, lv, mm, nball, b0);
+        const int nrb = (mm + 63) / 64;
+        if (in.fuse_dt && (single || multi) && kk <= 64 && nball * (1 + nrb) <= in.fuse_dt_maxwg) {      // (multi-GPU: local subtrees and replicated top alike; the per-kernel profile books the fused launch under the pivot blocks)
+            // few fronts on the level: pivot block + panel solve in one flag-synchronised launch (k_big_diag_trsm)
+            const int ntu = (P.lv_narrow_tiles[lv] > 0 && nball * (1 + nrb + P.lv_narrow_tiles[lv]) <= 256) ? P.lv_narrow_tiles[lv] : 0;      // (one workgroup per CU: the far part of a group-end update may own the rest of the chip)
+            put(FO_DIAG_TRSM, strm, KK_BIG_DIAG, lv, b0, nball, 1 + nrb + ntu, 256, 0, nrb, kk);
+            if (ntu > 0) return;         // ... and so did the narrow updates
+        } else if (kk <= 64) {
+            put(FO_DIAG_REG, strm, KK_BIG_DIAG, lv, b0, nball, 1, 256, 0, kk);
+            put(FO_TRSM, strm, KK_BIG_TRSM, lv, b0, (mm + 63) / 64, nball, 256, 0, kk);
+        } else {
+            put(FO_DIAG_REG_1024, strm, KK_BIG_DIAG, lv, b0, nball, 1, 1024, 0, kk);
+            put(FO_TRSM_WIDE, strm, KK_BIG_TRSM, lv, b0, (mm + 63) / 64, nball, 256, 0, kk);
+        }
+        if (bs > b0 && tiles_small > 0) put(FO_SCHUR64, strm, KK_BIG_SCHUR, lv, b0, tiles_small, bs - b0, 256, 0);
+        if (b1 == bs) return;
+        const int nb = b1 - bs;
+        if (single && P.la_full[lv]) join(lv);       // a full update may touch what an earlier part 2 is still writing
+        if (single && P.la_tiles2[lv] > 0) {
+            put(FO_SCHUR, strm, KK_BIG_SCHUR, lv, bs, P.la_tiles1[lv], nb, 0, 0, 1);
+            fork(0, lv, bs, nb, P.la_tiles2[lv]);
+        } else if (tiles > 0) put(FO_SCHUR, strm, KK_BIG_SCHUR, lv, bs, tiles, nb, 0, 0, 0);
+    };
+    // one (level, class) bucket of fronts
+    auto bucket = [&](int strm, int lv, int fc) {
+        const int b0 = bucket0(lv, fc), b1 = bucket0(lv, fc + 1), nb = b1 - b0;
+        if (nb == 0) return;
+        const size_t rl = P.reg_lds[(size_t)lv * FC_COUNT + fc];
+        if (fc == FC_WAVE) {
+            const int nt = sg ? P.tiny_split[lv] : 0;
+            int fl = top_mode;
+            if (in.fastpiv && P.wave_mmin[lv] <= 16) {      // fronts of order <= 16: four per wavefront on the static-order path first; what it accepts is skipped below
+                const int n16 = sg ? P.tiny16[lv] : nb;
+                // (the kernel raises qstat[4] for a front it rejects only when NO strict launch follows -- optimistic && n16 == nb: behind a strict
+                // launch the rejected front is simply the strict kernel's, and raising the flag there made factor() repeat the whole factorisation
+                // with the full schedule and drop the optimistic one for the life of the handle: ADVICE r04)
+                if (n16 > 0) { put(FO_FRONT_DPP16, strm, KK_FRONT_WAVE, lv, b0, (n16 + 3) / 4, 1, 64, 0, n16, top_mode, (optimistic && n16 == nb) ? 1 : 0); fl |= 2; }
+                // OPTIMISTIC schedule: every front of the bucket has order <= 16 and the static-order kernel accepts (nearly) everything it is given
+                // (LukVlE1 10^6: all 164 000 fronts) -- the strict launch behind it would find nothing to do, 4-8 us each, 21 of them per
+                // factorisation.  It is left out; a front the kernel rejects raises qstat[4] and factor() runs the full schedule again.
+                if (optimistic && n16 == nb) return;
+            }
+            if (nt > 0) put(FO_REG_64_2, strm, KK_FRONT_WAVE, lv, b0, nt, 1, 64, rl, fl);
+            if (nb - nt > 0) put(FO_REG_64_4, strm, KK_FRONT_WAVE, lv, b0 + nt, nb - nt, 1, 64, rl, fl);
+        } else if (fc == FC_LDS64) {
+            put(FO_REG_64_8, strm, KK_FRONT_LDS64, lv, b0, nb, 1, 64, rl, top_mode);
+        } else if (fc == FC_LDS128) {
+            const int nm = sg ? P.mid_split[lv] : 0;
+            const int fl = top_mode | (in.fastpiv ? 2 : 0);
+            // (measured and not kept, r05: in the optimistic schedule the strict launch only on the fronts with > 16 pivots and on a device-built list of
+            // the fronts the static-order launch rejected -- 342 of them on synth_1e6 -- instead of the whole bucket: 18.21 against 18.16 ms.  The
+            // 60-150 us of the strict launches are those fronts' own latency chains, not the workgroups that find nothing to do.)
+            if (in.fastpiv) {      // fronts with <= 16 pivots: static-order path first; what it accepts is skipped by the launch behind it
+                // (<256, 6, true> cut to 128 VGPRs = 4 workgroups per CU: 2.24 -> 2.13 ms of front_lds128 on synth_1e6; the same cut of <256, 8, true> gained nothing and is gone)
+                if (nm > 0) put(FO_REG_256_6_FAST4, strm, KK_FRONT_LDS128, lv, b0, nm, 1, 256, P.mid_lds[lv], top_mode);
+                if (nb - nm > 0) put(FO_REG_256_8_FAST, strm, KK_FRONT_LDS128, lv, b0 + nm, nb - nm, 1, 256, rl, top_mode);
+            }
+            if (nm > 0) put(FO_REG_256_6, strm, KK_FRONT_LDS128, lv, b0, nm, 1, 256, P.mid_lds[lv], fl);
+            if (nb - nm > 0) put(FO_REG_256_8, strm, KK_FRONT_LDS128, lv, b0 + nm, nb - nm, 1, 256, rl, fl);
+        } else {
+            const int mm = sc.maxm[lv], kk = sc.maxk[lv];
+            if ((single || multi) && P.grouped && lv >= Sy.grp_cut_level) {
+                // the chain groups whose first link sits on this level, one launch each
+                if (!(single && P.lv_asm_skip[lv])) assemble(strm, lv, mm, nb, b0);
+                groups(strm, lv);
+            } else if (!single) { const bool sm = mm <= 640; big(strm, lv, b0, sm ? b1 : b0, b1, mm, kk, sm ? sc.tiles64[lv] : 0, sm ? 0 : sc.tiles[lv]); }
+            else big(strm, lv, b0, b0 + P.big_split[lv], b1, mm, kk, P.part_tiles[0][lv], P.part_tiles[1][lv]);
+        }
+    };
+    const int lc = (sg && optimistic && P.lc_levels > 0) ? P.lc_levels : 0;      // the leaf chains: one launch for their levels (optimistic schedule only: no strict kernel behind it)
+    if (lc > 0) put(FO_LEAF_CHAIN, FS_MAIN, KK_FRONT_WAVE, 0, bucket0(0, FC_WAVE), (P.lc_nchains + 3) / 4, 1, 64, 0, P.lc_nchains, lc - 1);
+    for (int lv = lc; lv < NL; ++lv) {
+        if (sg && optimistic && P.df_run_at[lv] >= 0) {      // a run of levels of one-wavefront fronts: one persistent data-flow launch (optimistic schedule only: no strict kernels behind it)
+            const DfRun& R = P.df_runs[P.df_run_at[lv]];
+            put(FO_FRONT_DF, FS_MAIN, KK_FRONT_WAVE, lv, bucket0(lv, FC_WAVE), R.nq, 1, 64, 0, R.tab0, R.nlev, R.nq, R.lv1);
+            lv = R.lv1; continue;
+        }
+        // recycled contribution blocks (symbolic.cpp step 12a): whatever earlier levels put on the look-ahead streams is through before a level >= lv may
+        // write into the space of a block they read.  (The runs above and the leaf-chain prefix skip this join: ADVICE.md item 1.)
+        if (sg && Sy.cb_window > 0 && lv % Sy.cb_window == 0) join(lv);
+        int lvl_fronts = 0, lvl_max = 0;
+        for (int fc = 0; fc < FC_COUNT; ++fc) { const int nb = bucket0(lv, fc + 1) - bucket0(lv, fc); lvl_fronts += nb; lvl_max = std::max(lvl_max, nb); }
+        bool side_open = false;
+        for (int fc = 0; fc < FC_COUNT; ++fc) {
+            const int nb = bucket0(lv, fc + 1) - bucket0(lv, fc);
+            if (nb == 0) continue;
+            // A handful of small fronts on a level whose bulk is elsewhere (synth_1e6: 3 fronts of order <= 128 next to 2 045 big ones; one front of order <= 64
+            // next to 943 of order <= 128) is a launch of 1-3 workgroups running their strict pivot loops for 40-90 us with the chip idle.  The buckets of one
+            // level are independent: in the eager (multi-stream) schedule such a bucket goes to the side stream, next to the level's main launches.
+            // (the eager schedule only: a multi-stream hipGraph is what factor_once() avoids; not next to the three-stream chain look-ahead)
+            const bool side = sg && in.side_small && P.la_any && !multi && fc != FC_BIG && nb <= SIDE_MAX_FRONTS && lvl_max >= 8 * nb && lvl_fronts > nb;
+            if (side && !side_open) { put(FO_SIDE_OPEN, FS_MAIN, -1, lv, 0, 1, 1, 0, 0); side_open = true; }      // behind the level below
+            bucket(side ? FS_SIDE : FS_MAIN, lv, fc);
+        }
+        if (side_open) put(FO_SIDE_CLOSE, FS_SIDE, -1, lv, 0, 1, 1, 0, 0);      // the level above reads what they wrote
+    }
+    join(NL);      // (no fork outlives its list: the multi-rank schedules never fork -- build_launch_plan splits no update there -- and the single-GPU one ends here)
+    return out;
 }
 
 } // namespace mi355x

@@ -16,6 +16,7 @@ struct PlanInputs {
     int verbose = 0;
     bool chain_solve = true, fuse_dt = true, fastpiv = true, asm_pull = true, leafchain = true, front_df = true, tfuse = true, fuse_upd = true,
          selfasm = true, grouped = true, xcd_tiles = true, lookahead = true, pair_solve = true, p1_small = true;
+    bool side_small = true;              // a handful of small fronts beside a level's bulk go to the side stream (build_factor_schedule)
     int la_wgs = 1 << 20, la_min_nt = 8, grp_rbw_max = 8, chain_solve_maxc = 128, fuse_dt_maxwg = 448;
     long long la_min_tiles = 4000;
     double fastpiv_floor = 1e-4;         // (0.01 up to r03a: 9 % of the synth_1e6 blocks then took the strict loop and set the pace of their level: 23.1 -> 22.0 ms)
@@ -41,6 +42,32 @@ struct JoinList { int base = 0, count = 0, maxm = 0, who = -1; };
 struct RangeSeg { int d, glo, gsz; long long abeg, aend, tbeg, tend; };      // the part of a step of every range of ranks [glo, glo + gsz)
 // runs of consecutive tree levels that hold nothing but one-wavefront fronts (order <= 32): one persistent data-flow launch each (k_front_df)
 struct DfRun { int lv0, lv1, tab0, nlev, nq; };
+
+// kernel kinds for the profiling entry point (order = include/mi355x_kkt.h MI355X_KKT_KERNEL_*)
+enum KernelKind { KK_GATHER_SCALE = 0, KK_FRONT_WAVE, KK_FRONT_LDS64, KK_FRONT_LDS128, KK_BIG_ASSEMBLE, KK_BIG_DIAG, KK_BIG_TRSM,
+                  KK_BIG_SCHUR, KK_STATS, KK_SOLVE_PERM, KK_FWD_WAVE, KK_FWD_LDS, KK_FWD_BIG, KK_BWD_WAVE, KK_BWD_LDS, KK_BWD_BIG, KK_FWD_BIG_UPD, KK_BWD_BIG_DOT, KK_COUNT };
+// One record of a factor schedule: a kernel instantiation the factorisation launches, or a stream operation.  The values are exported
+// (mi355x_kkt_get_launch_plan "factor.*", include/mi355x_kkt.h): append, do not renumber.
+enum FactorOp { FO_LEAF_CHAIN = 0, FO_FRONT_DF, FO_FRONT_DPP16, FO_REG_64_2, FO_REG_64_4, FO_REG_64_8, FO_REG_256_6_FAST4, FO_REG_256_8_FAST, FO_REG_256_6, FO_REG_256_8,
+                FO_ASSEMBLE, FO_ASSEMBLE2, FO_GRP_FUSED, FO_DIAG_TRSM, FO_DIAG_REG, FO_DIAG_REG_1024, FO_TRSM, FO_TRSM_WIDE, FO_SCHUR64, FO_SCHUR, FO_SCHUR_P1, FO_SCHUR_Q,
+                FO_FORK,            // event A of (a[0], lv) recorded on the main stream, the look-ahead stream waits for it
+                FO_FORK_DONE,       // event B of (a[0], lv) recorded on the look-ahead stream
+                FO_JOIN,            // the main stream waits for event B of (a[0], lv)
+                FO_SIDE_OPEN,       // the side stream waits for what the main stream holds so far (side event F of level lv)
+                FO_SIDE_CLOSE,      // the main stream waits for the side stream (side event J of level lv)
+                FO_COUNT };
+enum FactorStream { FS_MAIN = 0, FS_LOOKAHEAD = 1, FS_SIDE = 2 };
+// gx, gy: the grid in workgroups, but for FO_FRONT_DF (gx: virtual workgroups; the executor clamps to what is resident), FO_SCHUR (gx: 128 x 128 tiles)
+// and FO_ASSEMBLE2 (gx: columns) -- the kernel's own compile-time geometry (SCHUR_GM, ASM_CH) turns those into workgroups in the executor; block = 0:
+// the kernel's own (FO_SCHUR: SCHUR_NT).  lds: dynamic LDS bytes where the plan knows them; the pivot-block and panel kernels size theirs from a[] with
+// the functions beside their device layouts (diag_lds_bytes, trsm_lds_bytes).  Events are named by (a[0] = index into the executor's look-ahead
+// events: 0 the single-GPU schedule, 1 + i the grouped schedule P.grp[i]; lv -- FO_JOIN: a[1], the level of the fork it waits for), never by handle.  a[]: the kernel's integer arguments behind b0, per op:
+//   LEAF_CHAIN {chains, last level}  FRONT_DF {tab0, levels, virtual workgroups, last level}  FRONT_DPP16 {fronts, top_mode, raise-the-flag}  REG_* {flags}
+//   ASSEMBLE {top_mode}  ASSEMBLE2 {top_mode, ldi, maxch}  GRP_FUSED {staged, rbw}  DIAG_TRSM {row blocks, kk}  DIAG_REG* {kk}  TRSM* {kk}
+//   SCHUR {part}  SCHUR_Q {tiles of part 2}
+struct FactorLaunch { int op, stream, kind, gx, gy, block, lv, b0, lds, a[4]; };      // kind: KernelKind (-1: a stream operation); b0: first launch-list entry
+constexpr int FACTOR_LAUNCH_INTS = 13;       // the exported row: the fields in this order
+constexpr int SIDE_MAX_FRONTS = 16;
 
 struct ExchangeLayout {
     std::vector<long long> aoff, troff;                  // per front: its arena square / top-rhs accumulator, or -1
@@ -89,7 +116,13 @@ struct LaunchPlan {
     std::vector<FrontMeta> fmeta; std::vector<ChildMeta> cmeta; std::vector<GroupLink> gtab; std::vector<int> relinv;
     std::vector<long long> panel_off, cb_off;            // remapped pool offsets
     std::vector<int> stat_owner, col_owner;
+    // the factor schedules this handle can run (NumericImpl::setup: build_factor_schedule): one GPU, [0] the full one, [1] the optimistic one; multi-rank
+    std::vector<FactorLaunch> factor_single[2], factor_local; std::vector<std::vector<FactorLaunch>> factor_stage;
 };
 LaunchPlan build_launch_plan(const Symbolic& Sy, const PlanInputs& in);
+// The factor schedule of one Sched as a flat list: every launch and every stream operation of the factorisation between the equilibration and the
+// statistics, in the order the executor (numeric.hip run_factor_list) issues them.  which: 0 = P.single, 1 = P.local, 2 + d = P.stage[d] (top_mode
+// and the grouped schedule P.grp[...] follow from it).  optimistic: the schedule without the strict launches the static-order kernels make idle.
+std::vector<FactorLaunch> build_factor_schedule(const LaunchPlan& P, const Symbolic& Sy, const PlanInputs& in, int which, bool optimistic);
 
 } // namespace mi355x

@@ -45,9 +45,7 @@
 
 namespace mi355x {
 
-// kernel kinds for the profiling entry point (order = include/mi355x_kkt.h MI355X_KKT_KERNEL_*)
-enum KernelKind { KK_GATHER_SCALE = 0, KK_FRONT_WAVE, KK_FRONT_LDS64, KK_FRONT_LDS128, KK_BIG_ASSEMBLE, KK_BIG_DIAG, KK_BIG_TRSM,
-                  KK_BIG_SCHUR, KK_STATS, KK_SOLVE_PERM, KK_FWD_WAVE, KK_FWD_LDS, KK_FWD_BIG, KK_BWD_WAVE, KK_BWD_LDS, KK_BWD_BIG, KK_FWD_BIG_UPD, KK_BWD_BIG_DOT, KK_COUNT };
+// (the kernel kinds of the profiling entry point, KK_*: launch_plan.h)
 #define DBGSTAMP(slot) do { if (V.dbg && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { V.dbg[2 * (slot)] = clock64(); V.dbg[2 * (slot) + 1] = wall_clock64(); } } while (0)
 #define DBGT(i) do { if (V.dbg && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) V.dbg[16 + (i)] = clock64(); } while (0)
 // (MI355X_KKT_TRACE=launches: development -- name the launch whose configuration the runtime refuses instead of the "invalid configuration argument" the next HIPCHK would report)
@@ -241,15 +239,13 @@ public:
         for (int i = 0; i < S->n; ++i) out[S->perm[i]] = sp[i];
         return true;
     }
-    PlanInputs knobs;          // the settings the plan was built with (the launch code reads the launch-time ones from here)
     LaunchPlan P;              // every launch of the factorisation and the solves, and the tables behind them (launch_plan.cpp)
     // look-ahead events per level with a part 2 (part 1 done on the main stream / part 2 done on the second): [0] the single-GPU schedule, [1 + i] grouped schedule P.grp[i]
     struct LaEvents { std::vector<hipEvent_t> A, B; };
     std::vector<LaEvents> la_ev;
-    int grp_step = 0;                          // multi-GPU: the exchange step launch_fronts is working on
     size_t strace_n = 0; struct TraceDesc { int chain, w, nlinks, tail; }; std::vector<TraceDesc> strace_desc;
-    hipStream_t stream3 = nullptr;             // third stream: the side buckets of small fronts next to a level's main launches (enqueue_factor)
-    hipStream_t stream2 = nullptr; bool la_pending = false; hipEvent_t la_last = nullptr;      // second stream: part 2 of the split group-end updates
+    hipStream_t stream3 = nullptr;             // third stream: the side buckets of small fronts next to a level's main launches (FS_SIDE)
+    hipStream_t stream2 = nullptr;             // second stream: part 2 of the split group-end updates
     bool multi = false;
 
     // ---- device-side value assembly: per segment a device source buffer + a pinned staging buffer of the same length ----
@@ -460,7 +456,7 @@ public:
         destroy_factor_graphs(); scale_valid = false; asm_dirty = true;
         if (g_solve) { (void)hipGraphExecDestroy(g_solve); g_solve = nullptr; }
         own_struct.clear(); d_rhs = nullptr; d_rhs_cap = 0;
-        la_ev.clear(); side_evF.clear(); side_evJ.clear(); la_last = nullptr; la_pending = false;
+        la_ev.clear(); side_evF.clear(); side_evJ.clear();
         own_match.clear(); MV = MatchView{};
         if (!keep) {
             own_pool.clear(); kept_pool = nullptr; kept_pool_doubles = 0;
@@ -589,9 +585,11 @@ public:
         }
         lap("pool");
         // 3. the launch plan (launch_plan.cpp: host only)
-        knobs = in;
         P = build_launch_plan(Sy, in);
         if (!P.error.empty()) { err_ = P.error; return false; }
+        // ... and the factor schedules this handle can run: one GPU, the full and the optimistic one (factor() picks); multi-rank, own subtrees and every step
+        if (!multi) for (int o = 0; o < 2; ++o) P.factor_single[o] = build_factor_schedule(P, Sy, in, 0, o != 0);
+        else { P.factor_local = build_factor_schedule(P, Sy, in, 1, false); for (int d = 0; d < P.ndepth; ++d) P.factor_stage.push_back(build_factor_schedule(P, Sy, in, 2 + d, false)); }
         V.fastpiv = in.fastpiv ? 1 : 0; V.asm_pull = in.asm_pull ? 1 : 0; V.fastu = in.fastpiv_floor;
         df_grid_cap = 0;
         if (!P.df_runs.empty()) {
@@ -657,6 +655,32 @@ public:
                 if (la2[lv] > 0 && (!own_struct.event(&la_ev[i].A[lv], hipEventDisableTiming) || !own_struct.event(&la_ev[i].B[lv], hipEventDisableTiming))) return false;
         }
         // 7. kernel attributes: allow the large dynamic LDS sizes
+        if (!allow_large_lds()) return false;      // (the list sits beside the switch that launches them: run_factor_list)
+        // hipMemset runs on the legacy default stream; the solver's streams are non-blocking, i.e. NOT ordered behind it: without this the first
+        // sweeps of a small system could meet flags / tagged messages left in recycled device memory by an earlier handle (or process) before
+        // the zero fill has landed
+        HIPCHK(hipDeviceSynchronize());
+        lap("kernel attributes, zero fills landed");
+        ready = true;
+        if (keep && comm_kind == 2) make_subcomms();
+        return true;
+    }
+
+    static int schur_grid(int tiles) { return SCHUR_GM == 2 ? 16 * ((tiles + 7) / 8) : tiles; }      // workgroups of a k_big_schur launch over `tiles` 128 x 128 tiles (kernels_big.hip.inc: SCHUR_HALVES)
+    int grid1d(long long n) const { long long g = (n + 255) / 256; return (int)std::min<long long>(std::max<long long>(g, 1), 2048); }
+
+
+    // A schedule is a Sched of the plan (P.single, P.local, P.stage[d]) handed to a walker; what only the single-GPU schedule takes -- buckets
+    // sorted by order and their splits, pair kernels, leaf chains -- is asked of the Sched, in the walker (DESIGN.md "Where a launch is decided")
+    bool is_single(const Sched& sc) const { return &sc == &P.single; }
+    static int bucket0(const Sched& sc, int lv, int fc) { return sc.base + sc.ptr[(size_t)lv * FC_COUNT + fc]; }      // bucket (lv, fc) of sc is [bucket0(lv, fc), bucket0(lv, fc + 1)) of the launch list
+    // ---- the factor executor: walks a list of launch_plan.cpp build_factor_schedule.  Nothing is decided here: the switch maps a FactorOp to its kernel
+    //      symbol (the only place that does), sizes the LDS of the pivot-block and panel kernels with the functions beside their device layouts, and
+    //      owns what depends on the device -- the streams, the events, the clamp of k_front_df to the resident workgroups. ----
+    const DfLevel* d_dftab = nullptr; int df_grid_cap = 0;      // k_front_df: the levels of the runs (P.df_tab), the largest grid whose workgroups are all resident
+    std::vector<hipEvent_t> side_evF, side_evJ;                // per level, created when a list first opens the side stream there
+    // the instantiations that need the large dynamic-LDS attribute (setup step 7), in the order of the switch below: a new case there belongs here too
+    bool allow_large_lds() {
         HIPCHK(hipFuncSetAttribute((const void*)k_big_diag_reg<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         HIPCHK(hipFuncSetAttribute((const void*)(k_big_diag_reg<4, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         HIPCHK(hipFuncSetAttribute((const void*)(k_front_reg<64, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -671,174 +695,51 @@ public:
         HIPCHK(hipFuncSetAttribute((const void*)k_big_diag_trsm, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         HIPCHK(hipFuncSetAttribute((const void*)k_grp_fused, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         HIPCHK(hipFuncSetAttribute((const void*)k_big_assemble2, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));      // (+ 1.3 KB of static LDS: the per-child tables)
-        // hipMemset runs on the legacy default stream; the solver's streams are non-blocking, i.e. NOT ordered behind it: without this the first
-        // sweeps of a small system could meet flags / tagged messages left in recycled device memory by an earlier handle (or process) before
-        // the zero fill has landed
-        HIPCHK(hipDeviceSynchronize());
-        lap("kernel attributes, zero fills landed");
-        ready = true;
-        if (keep && comm_kind == 2) make_subcomms();
         return true;
     }
-
-    static size_t trsm_lds(int kk) { return trsm_lds_bytes(kk, false); }
-    static int schur_grid(int tiles) { return SCHUR_GM == 2 ? 16 * ((tiles + 7) / 8) : tiles; }      // workgroups of a k_big_schur launch over `tiles` 128 x 128 tiles (kernels_big.hip.inc: SCHUR_HALVES)
-    int grid1d(long long n) const { long long g = (n + 255) / 256; return (int)std::min<long long>(std::max<long long>(g, 1), 2048); }
-
-
-    // A schedule is a Sched of the plan (P.single, P.local, P.stage[d]) handed to a walker; what only the single-GPU schedule takes -- buckets
-    // sorted by order and their splits, pair kernels, leaf chains -- is asked of the Sched, in the walker (DESIGN.md "Where a launch is decided")
-    bool is_single(const Sched& sc) const { return &sc == &P.single; }
-    static int bucket0(const Sched& sc, int lv, int fc) { return sc.base + sc.ptr[(size_t)lv * FC_COUNT + fc]; }      // bucket (lv, fc) of sc is [bucket0(lv, fc), bucket0(lv, fc + 1)) of the launch list
-    // one (level, class) bucket of fronts
-    bool launch_bucket(const Sched& sc, int lv, int fc, int top_mode) {
-        const int b0 = bucket0(sc, lv, fc), b1 = bucket0(sc, lv, fc + 1), nb = b1 - b0;
-        if (nb == 0) return true;
-        const bool sg = is_single(sc);                            // single-GPU schedule: the buckets are sorted by order
-        const size_t rl = P.reg_lds[(size_t)lv * FC_COUNT + fc];
-        if (fc == FC_WAVE) {
-            const int nt = sg ? P.tiny_split[lv] : 0;
-            int fl = top_mode;
-            if (V.fastpiv && P.wave_mmin[lv] <= 16) {      // fronts of order <= 16: four per wavefront on the static-order path first; what it accepts is skipped below
-                const int n16 = sg ? P.tiny16[lv] : nb;
-                // (the kernel raises qstat[4] for a front it rejects only when NO strict launch follows -- optimistic && n16 == nb: behind a strict
-                // launch the rejected front is simply the strict kernel's, and raising the flag there made factor() repeat the whole factorisation
-                // with the full schedule and drop the optimistic one for the life of the handle: ADVICE r04)
-                if (n16 > 0) { LAUNCH(KK_FRONT_WAVE, k_front_dpp16, dim3((n16 + 3) / 4), dim3(64), 0, stream, V, b0, n16, top_mode, (optimistic && n16 == nb) ? 1 : 0); fl |= 2; }
-                // OPTIMISTIC schedule: every front of the bucket has order <= 16 and the static-order kernel accepts (nearly) everything it is given
-                // (LukVlE1 10^6: all 164 000 fronts) -- the strict launch behind it would find nothing to do, 4-8 us each, 21 of them per
-                // factorisation.  It is left out; a front the kernel rejects raises qstat[4] and factor() runs the full schedule again.
-                if (optimistic && n16 == nb) return true;
+    bool run_factor_list(const std::vector<FactorLaunch>& list) {
+        for (const FactorLaunch& r : list) {
+            const hipStream_t q = r.stream == FS_MAIN ? stream : r.stream == FS_LOOKAHEAD ? stream2 : stream3;
+            const dim3 grid(r.gx, r.gy), block(r.block);
+            const size_t lds = (size_t)r.lds;
+            const int* a = r.a;
+            switch (r.op) {
+            // the large dynamic-LDS instantiations, in the order of allow_large_lds()
+            case FO_DIAG_REG:        LAUNCH_ON(r.kind, q, k_big_diag_reg<4>, grid, block, diag_lds_bytes(a[0], 64), q, V, r.b0); break;
+            case FO_DIAG_REG_1024:   LAUNCH_ON(r.kind, q, (k_big_diag_reg<4, 1024>), grid, block, diag_lds_bytes(a[0], 128), q, V, r.b0); break;
+            case FO_REG_64_2:        LAUNCH_ON(r.kind, q, (k_front_reg<64, 2>), grid, block, lds, q, V, r.b0, a[0]); break;
+            case FO_REG_64_4:        LAUNCH_ON(r.kind, q, (k_front_reg<64, 4>), grid, block, lds, q, V, r.b0, a[0]); break;
+            case FO_REG_64_8:        LAUNCH_ON(r.kind, q, (k_front_reg<64, 8>), grid, block, lds, q, V, r.b0, a[0]); break;
+            case FO_REG_256_8:       LAUNCH_ON(r.kind, q, (k_front_reg<256, 8>), grid, block, lds, q, V, r.b0, a[0]); break;
+            case FO_REG_256_6:       LAUNCH_ON(r.kind, q, (k_front_reg<256, 6>), grid, block, lds, q, V, r.b0, a[0]); break;
+            case FO_REG_256_8_FAST:  LAUNCH_ON(r.kind, q, (k_front_reg<256, 8, true>), grid, block, lds, q, V, r.b0, a[0]); break;
+            case FO_REG_256_6_FAST4: LAUNCH_ON(r.kind, q, (k_front_reg<256, 6, true, 4>), grid, block, lds, q, V, r.b0, a[0]); break;
+            case FO_TRSM:            LAUNCH_ON(r.kind, q, k_big_trsm<false>, grid, block, trsm_lds_bytes(a[0], false), q, V, r.b0, 0); break;
+            case FO_TRSM_WIDE:       LAUNCH_ON(r.kind, q, k_big_trsm<true>, grid, block, trsm_lds_bytes(a[0], false), q, V, r.b0, 0); break;
+            case FO_DIAG_TRSM:       LAUNCH_ON(r.kind, q, k_big_diag_trsm, grid, block, std::max(diag_lds_bytes(a[1], 64), trsm_lds_bytes(a[1], true)), q, V, r.b0, a[0]); break;
+            case FO_GRP_FUSED:       LAUNCH_ON(r.kind, q, k_grp_fused, grid, block, std::max(diag_lds_bytes(64, 64), GRP_DB_BYTES + trsm_lds_bytes(64, a[0] != 0)), q, V, r.b0, a[0], a[1], 0); break;
+            case FO_ASSEMBLE2:       LAUNCH_ON(r.kind, q, k_big_assemble2, dim3((r.gx + ASM_CH - 1) / ASM_CH, r.gy), block, lds, q, V, r.b0, a[0], a[1], a[2]); break;
+            // the rest, in schedule order
+            case FO_LEAF_CHAIN:      LAUNCH_ON(r.kind, q, k_leaf_chain, grid, block, 0, q, V, a[0]); break;
+            case FO_FRONT_DF:        LAUNCH_ON(r.kind, q, k_front_df, dim3(std::min(r.gx, df_grid_cap)), block, 0, q, V, d_dftab + a[0], a[1], a[2]); break;      // (every workgroup of the launch must be resident: they wait for each other)
+            case FO_FRONT_DPP16:     LAUNCH_ON(r.kind, q, k_front_dpp16, grid, block, 0, q, V, r.b0, a[0], a[1], a[2]); break;
+            case FO_ASSEMBLE:        LAUNCH_ON(r.kind, q, k_big_assemble, grid, block, 0, q, V, r.b0, a[0]); break;
+            case FO_SCHUR64:         LAUNCH_ON(r.kind, q, k_big_schur64, grid, block, 0, q, V, r.b0, 0); break;
+            case FO_SCHUR:           LAUNCH_ON(r.kind, q, k_big_schur, dim3(schur_grid(r.gx), r.gy), dim3(SCHUR_NT), 0, q, V, r.b0, a[0], 0, 0); break;
+            case FO_SCHUR_P1:        LAUNCH_ON(r.kind, q, k_big_schur_p1, grid, block, 0, q, V, r.b0); break;
+            case FO_SCHUR_Q:         LAUNCH_ON(r.kind, q, k_big_schur_q, grid, block, 0, q, V, r.b0, a[0]); break;
+            // the stream operations
+            case FO_FORK:      HIPCHK(hipEventRecord(la_ev[a[0]].A[r.lv], stream)); HIPCHK(hipStreamWaitEvent(stream2, la_ev[a[0]].A[r.lv], 0)); break;
+            case FO_FORK_DONE: HIPCHK(hipEventRecord(la_ev[a[0]].B[r.lv], stream2)); break;
+            case FO_JOIN:      HIPCHK(hipStreamWaitEvent(stream, la_ev[a[0]].B[a[1]], 0)); break;
+            case FO_SIDE_OPEN:
+                if ((int)side_evF.size() < S->num_levels) { side_evF.resize(S->num_levels, nullptr); side_evJ.resize(S->num_levels, nullptr); }
+                if (!side_evF[r.lv] && (!own_struct.event(&side_evF[r.lv], hipEventDisableTiming) || !own_struct.event(&side_evJ[r.lv], hipEventDisableTiming))) return false;
+                HIPCHK(hipEventRecord(side_evF[r.lv], stream)); HIPCHK(hipStreamWaitEvent(stream3, side_evF[r.lv], 0)); break;
+            case FO_SIDE_CLOSE: HIPCHK(hipEventRecord(side_evJ[r.lv], stream3)); HIPCHK(hipStreamWaitEvent(stream, side_evJ[r.lv], 0)); break;
+            default: err_ = "internal: unknown record in a factor schedule"; return false;
             }
-            if (nt > 0) LAUNCH(KK_FRONT_WAVE, (k_front_reg<64, 2>), dim3(nt), dim3(64), rl, stream, V, b0, fl);
-            if (nb - nt > 0) LAUNCH(KK_FRONT_WAVE, (k_front_reg<64, 4>), dim3(nb - nt), dim3(64), rl, stream, V, b0 + nt, fl);
-        } else if (fc == FC_LDS64) {
-            LAUNCH(KK_FRONT_LDS64, (k_front_reg<64, 8>), dim3(nb), dim3(64), rl, stream, V, b0, top_mode);
-        } else if (fc == FC_LDS128) {
-            const int nm = sg ? P.mid_split[lv] : 0;
-            const int fl = top_mode | (V.fastpiv ? 2 : 0);
-            // (measured and not kept, r05: in the optimistic schedule the strict launch only on the fronts with > 16 pivots and on a device-built list of
-            // the fronts the static-order launch rejected -- 342 of them on synth_1e6 -- instead of the whole bucket: 18.21 against 18.16 ms.  The
-            // 60-150 us of the strict launches are those fronts' own latency chains, not the workgroups that find nothing to do.)
-            if (V.fastpiv) {      // fronts with <= 16 pivots: static-order path first; what it accepts is skipped by the launch behind it
-                // (<256, 6, true> cut to 128 VGPRs = 4 workgroups per CU: 2.24 -> 2.13 ms of front_lds128 on synth_1e6; the same cut of <256, 8, true> gained nothing and is gone)
-                if (nm > 0) LAUNCH(KK_FRONT_LDS128, (k_front_reg<256, 6, true, 4>), dim3(nm), dim3(256), P.mid_lds[lv], stream, V, b0, top_mode);
-                if (nb - nm > 0) LAUNCH(KK_FRONT_LDS128, (k_front_reg<256, 8, true>), dim3(nb - nm), dim3(256), rl, stream, V, b0 + nm, top_mode);
-            }
-            if (nm > 0) LAUNCH(KK_FRONT_LDS128, (k_front_reg<256, 6>), dim3(nm), dim3(256), P.mid_lds[lv], stream, V, b0, fl);
-            if (nb - nm > 0) LAUNCH(KK_FRONT_LDS128, (k_front_reg<256, 8>), dim3(nb - nm), dim3(256), rl, stream, V, b0 + nm, fl);
-        } else {
-            const bool single = sg && !multi;
-            const int mm = sc.maxm[lv], kk = sc.maxk[lv];
-            if ((single || multi) && P.grouped && lv >= S->grp_cut_level) {
-                // the chain groups whose first link sits on this level, one launch each (the multi-GPU schedules have their own group lists)
-                if (!(single && P.lv_asm_skip[lv])) launch_assemble(mm, nb, b0, top_mode);
-                return launch_groups(lv, top_mode ? 1 + grp_step : 0);
-            }
-            if (!single) { const bool sm = mm <= 640; return launch_big(lv, b0, sm ? b1 : b0, b1, top_mode, mm, kk, sm ? sc.tiles64[lv] : 0, sm ? 0 : sc.tiles[lv], false); }
-            return launch_big(lv, b0, b0 + P.big_split[lv], b1, top_mode, mm, kk, P.part_tiles[0][lv], P.part_tiles[1][lv], true);
         }
-        return true;
-    }
-    // the chain groups whose first link sits on level lv: pivot blocks + leading blocks, rows below, rank-(<= 256) updates
-    bool launch_groups(int lv, int gi) {      // gi: the grouped schedule P.grp[gi]
-        const GrpSched& G = P.grp[gi]; const LaEvents& E = la_ev[1 + gi];
-        const int b0 = G.g0[lv], b1 = G.g1[lv], bs = b0 + G.split[lv];
-        if (b1 == b0) return true;
-        {
-            // as many 64-row blocks per row-block workgroup as it takes for the launch to fit the chip (one workgroup per CU)
-            int rbw = 1;
-            while (rbw < knobs.grp_rbw_max && (b1 - b0) * (4 + (G.nrb[lv] + rbw - 1) / rbw) > 256) rbw *= 2;
-            const int nrbw = (G.nrb[lv] + rbw - 1) / rbw;
-            const int st = ((b1 - b0) * (4 + nrbw) <= 256) ? 1 : 0;
-            const size_t lds = std::max(diag_lds_bytes(64, 64), GRP_DB_BYTES + trsm_lds_bytes(64, st != 0));
-            LAUNCH(KK_BIG_DIAG, k_grp_fused, dim3(b1 - b0, 4 + nrbw), dim3(256), lds, stream, V, b0, st, rbw, 0);
-        }
-        if (bs > b0 && G.tiles64[lv] > 0) LAUNCH(KK_BIG_SCHUR, k_big_schur64, dim3(G.tiles64[lv], bs - b0), dim3(256), 0, stream, V, b0, 0);
-        if (b1 == bs) return true;
-        const int nb = b1 - bs;
-        if (!la_join()) return false;      // a full update may touch what an earlier part 2 is still writing
-        if (G.la2[lv] > 0) {      // (also while profile() records its events: the per-kernel times are those of the TIMED schedule, look-ahead stream included)
-            // part 1 in 64 x 64 tiles where the 128 x 128 ones would leave most of the chip idle (k_big_schur_p1); the fronts of the list that are not split
-            // get their whole update from a launch of their own then
-            if (knobs.p1_small && G.la1[lv] * nb <= 512) {
-                LAUNCH(KK_BIG_SCHUR, k_big_schur_p1, dim3(G.p1t[lv], nb), dim3(1024), 0, stream, V, bs);
-                if (G.nsplit[lv] < nb) LAUNCH(KK_BIG_SCHUR, k_big_schur, dim3(schur_grid(G.la3[lv]), nb), dim3(SCHUR_NT), 0, stream, V, bs, 4, 0, 0);
-            } else LAUNCH(KK_BIG_SCHUR, k_big_schur, dim3(schur_grid(G.la1[lv]), nb), dim3(SCHUR_NT), 0, stream, V, bs, 1, 0, 0);
-            return la_fork(E.A[lv], E.B[lv], bs, nb, G.la2[lv]);
-        } else if (G.tiles[lv] > 0) LAUNCH(KK_BIG_SCHUR, k_big_schur, dim3(schur_grid(G.tiles[lv]), nb), dim3(SCHUR_NT), 0, stream, V, bs, 0, 0, 0);
-        return true;
-    }
-    // A handful of small fronts on a level whose bulk is elsewhere (synth_1e6: 3 fronts of order <= 128 next to 2 045 big ones; one front of order <= 64
-    // next to 943 of order <= 128) is a launch of 1-3 workgroups running their strict pivot loops for 40-90 us with the chip idle.  The buckets of one level
-    // are independent: in the eager (multi-stream) schedule such a bucket goes to the third stream, next to the level's main launches.
-    std::vector<hipEvent_t> side_evF, side_evJ; bool side_on = !knob_disabled("side_small"); static constexpr int SIDE_MAX_FRONTS = 16;
-    const DfLevel* d_dftab = nullptr; int df_grid_cap = 0;      // k_front_df: the levels of the runs (P.df_tab), the largest grid whose workgroups are all resident
-    // part 2 of the split updates (second stream, next to the following group's pivot chain): 128 x 128 tiles on 16 wavefronts, or quarter tiles on 4
-    // wavefronts that fit on the CUs a k_grp_fused workgroup occupies (kernels_big.hip.inc: k_big_schur_q / _w)
-    // The look-ahead fork, behind part 1 on the main stream: A recorded there, part 2 of the fronts [b0, b0 + nb) on the second stream behind A, B recorded
-    // behind it -- what la_join() makes the main stream wait for before a later launch may touch what part 2 reads or writes
-    bool la_fork(hipEvent_t A, hipEvent_t B, int b0, int nb, int ntiles) {
-        const int nvirt = ((ntiles + 7) / 8) * 32;
-        const int wgs = (int)std::min<long long>(nvirt, 4ll * knobs.la_wgs);
-        HIPCHK(hipEventRecord(A, stream));
-        HIPCHK(hipStreamWaitEvent(stream2, A, 0));
-        LAUNCH_ON(KK_BIG_SCHUR, stream2, k_big_schur_q, dim3(wgs, nb), dim3(256), 0, stream2, V, b0, ntiles);
-        HIPCHK(hipEventRecord(B, stream2));
-        la_last = B; la_pending = true;
-        return true;
-    }
-    bool la_join() { if (la_pending) { HIPCHK(hipStreamWaitEvent(stream, la_last, 0)); la_pending = false; } return true; }
-    // The column-chunk kernel pays where a level is MANY fronts of a few hundred rows (short columns: the one-wavefront-per-column kernel runs at the
-    // latency of its load chain there) and every front can take its fast path (at most ASM_MAXCH children to pull, not an in-place link with other
-    // children, no arena): measured 4.1 -> 2.0 ms per factorisation on synth_1e6, but 3.4 -> 8.7 ms on MBndryCntrl_3D 30, whose levels are a
-    // handful of fronts of ~1000 rows with a dozen children each -- there the column kernel has four times the workgroups and no preamble.
-    void launch_assemble(int mm, int nfronts, int b0, int top_mode) {
-        const int ldi = (mm + 15) & ~15;                    // the children's inverse row maps of one front in LDS: ASM_MAXCH x ldi ints (78 KiB at the largest front of synth_1e6)
-        // (... which has to FIT: a level of >= 32 fast-path fronts whose largest order exceeds ~6 780 -- a 3-D problem, or fronts enlarged by a
-        // delayed-pivot edit -- would make the launch fail instead of falling back to the column kernel: ADVICE r04)
-        // Round 5: a front whose contribution block is formed by its update (asmcut) has only its panel columns assembled; a launch of such fronts has no
-        // workgroups behind the largest asmcut.  (MI355X_KKT_ASM2_WIDE: this kernel also for levels of a few dozen fronts with up to ASM_MAXCH = 16 children each
-        // once only their panel columns are assembled -- the MBndryCntrl_3D family; measured slower there than the column kernel, 7.65 against 7.16 ms.)
-        bool v2 = !top_mode;
-        int maxch = 1, ncut = 0, cutmax = 0;
-        for (int q = b0; q < b0 + nfronts && v2; ++q) { v2 = P.asm_fast_ok[q] != 0; maxch = std::max(maxch, (int)P.asm_fast_ok[q]); if (P.asmcut[q]) { ++ncut; cutmax = std::max(cutmax, P.asmcut[q] > 0 ? P.asmcut[q] : 0); } }
-        v2 = v2 && (size_t)maxch * ldi * sizeof(int) <= (size_t)158 * 1024 && (nfronts >= 32 && maxch <= 6);
-        if (!v2) { LAUNCH(KK_BIG_ASSEMBLE, k_big_assemble, dim3((mm + 3) / 4, nfronts), dim3(256), 0, stream, V, b0, top_mode); return; }
-        const int ncols = (ncut == nfronts) ? std::min(mm, cutmax) : mm;      // (every front stops at its asmcut: no workgroups for the columns behind the largest of them)
-        if (ncols <= 0) return;                                               // (every front of the list has its whole block formed by its update: nothing to assemble -- a grid of 0 workgroups is refused by the runtime, met on the multi-rank schedule)
-        LAUNCH(KK_BIG_ASSEMBLE, k_big_assemble2, dim3((ncols + ASM_CH - 1) / ASM_CH, nfronts), dim3(256), (size_t)maxch * ldi * sizeof(int), stream, V, b0, top_mode, ldi, maxch);
-    }
-    // the big-front launches of one level: assembly, pivot blocks and TRSM over the whole list [b0, b1); the trailing update with
-    // 64 x 64 tiles / 256 threads on the fronts [b0, bs) of order <= 1024 (a handful of tiles, K = 16..64 each) and with
-    // 128 x 128 tiles / 1024 threads on [bs, b1)
-    bool launch_big(int lv, int b0, int bs, int b1, int top_mode, int mm, int kk, int tiles_small, int tiles, bool single) {
-        const int nball = b1 - b0;
-        if (!(single && P.lv_asm_skip[lv])) launch_assemble(mm, nball, b0, top_mode);
-        const int nrb = (mm + 63) / 64;
-        if (knobs.fuse_dt && (single || multi) && kk <= 64 && nball * (1 + nrb) <= knobs.fuse_dt_maxwg) {      // (multi-GPU: local subtrees and replicated top alike; the per-kernel profile books the fused launch under the pivot blocks)
-            // few fronts on the level: pivot block + panel solve in one flag-synchronised launch (k_big_diag_trsm)
-            const size_t lds = std::max(diag_lds_bytes(kk, 64),
-                                        trsm_lds_bytes(kk, true));
-            const int ntu = (P.lv_narrow_tiles[lv] > 0 && nball * (1 + nrb + P.lv_narrow_tiles[lv]) <= 256) ? P.lv_narrow_tiles[lv] : 0;      // (one workgroup per CU: the far part of a group-end update may own the rest of the chip)
-            LAUNCH(KK_BIG_DIAG, k_big_diag_trsm, dim3(nball, 1 + nrb + ntu), dim3(256), lds, stream, V, b0, nrb);
-            if (ntu > 0) return true;         // ... and so did the narrow updates
-            goto updates;
-        }
-        if (kk <= 64) LAUNCH(KK_BIG_DIAG, k_big_diag_reg<4>, dim3(nball), dim3(256), diag_lds_bytes(kk, 64), stream, V, b0);
-        else          LAUNCH(KK_BIG_DIAG, (k_big_diag_reg<4, 1024>), dim3(nball), dim3(1024), diag_lds_bytes(kk, 128), stream, V, b0);
-        if (kk <= 64) LAUNCH(KK_BIG_TRSM, k_big_trsm<false>, dim3((mm + 63) / 64, nball), dim3(256), trsm_lds(kk), stream, V, b0, 0);
-        else          LAUNCH(KK_BIG_TRSM, k_big_trsm<true>, dim3((mm + 63) / 64, nball), dim3(256), trsm_lds(kk), stream, V, b0, 0);
-      updates:
-        if (bs > b0 && tiles_small > 0) LAUNCH(KK_BIG_SCHUR, k_big_schur64, dim3(tiles_small, bs - b0), dim3(256), 0, stream, V, b0, 0);
-        if (b1 == bs) return true;
-        const int nb = b1 - bs;
-        b0 = bs;
-        if (single && P.la_full[lv] && !la_join()) return false;       // a full update may touch what an earlier part 2 is still writing
-        if (single && P.la_tiles2[lv] > 0) {
-            LAUNCH(KK_BIG_SCHUR, k_big_schur, dim3(schur_grid(P.la_tiles1[lv]), nb), dim3(SCHUR_NT), 0, stream, V, b0, 1, 0, 0);
-            return la_fork(la_ev[0].A[lv], la_ev[0].B[lv], b0, nb, P.la_tiles2[lv]);
-        } else if (tiles > 0) LAUNCH(KK_BIG_SCHUR, k_big_schur, dim3(schur_grid(tiles), nb), dim3(SCHUR_NT), 0, stream, V, b0, 0, 0, 0);
         return true;
     }
 
@@ -876,38 +777,7 @@ public:
         LAUNCH(KK_STATS, k_factor_prologue, dim3(grid1d(n)), dim3(256), 0, stream, V);
         LAUNCH(KK_GATHER_SCALE, k_gather_values, dim3(grid1d(Sy.nnz_a)), dim3(256), 0, stream, V);
         enqueue_scaling();
-        const int lc = (optimistic && P.lc_levels > 0) ? P.lc_levels : 0;      // the leaf chains: one launch for their levels (optimistic schedule only: no strict kernel behind it)
-        if (lc > 0) LAUNCH(KK_FRONT_WAVE, k_leaf_chain, dim3((P.lc_nchains + 3) / 4), dim3(64), 0, stream, V, P.lc_nchains);
-        for (int lv = lc; lv < Sy.num_levels; ++lv) {
-            if (optimistic && P.df_run_at[lv] >= 0) {      // a run of levels of one-wavefront fronts: one persistent data-flow launch (optimistic schedule only: no strict kernels behind it)
-                const DfRun& R = P.df_runs[P.df_run_at[lv]];
-                LAUNCH(KK_FRONT_WAVE, k_front_df, dim3(std::min(R.nq, df_grid_cap)), dim3(64), 0, stream, V, d_dftab + R.tab0, R.nlev, R.nq);
-                lv = R.lv1; continue;
-            }
-            // recycled contribution blocks (symbolic.cpp step 12a): whatever earlier levels put on the look-ahead streams is through before a level >= lv may
-            // write into the space of a block they read.  (The runs above and the leaf-chain prefix skip this join: ADVICE.md item 1.)
-            if (Sy.cb_window > 0 && lv % Sy.cb_window == 0 && !la_join()) return false;
-            int lvl_fronts = 0, lvl_max = 0;
-            for (int fc = 0; fc < FC_COUNT; ++fc) { const int nb = bucket0(P.single, lv, fc + 1) - bucket0(P.single, lv, fc); lvl_fronts += nb; lvl_max = std::max(lvl_max, nb); }
-            bool side_open = false;
-            for (int fc = 0; fc < FC_COUNT; ++fc) {
-                const int nb = bucket0(P.single, lv, fc + 1) - bucket0(P.single, lv, fc);
-                if (nb == 0) continue;
-                // (the eager schedule only: a multi-stream hipGraph is what factor_once() avoids; not next to the three-stream chain look-ahead)
-                const bool side = side_on && P.la_any && !multi && fc != FC_BIG && nb <= SIDE_MAX_FRONTS && lvl_max >= 8 * nb && lvl_fronts > nb;
-                if (side) {      // the bucket goes to the third stream: the same call with the streams swapped around it
-                    if ((int)side_evF.size() < Sy.num_levels) { side_evF.resize(Sy.num_levels, nullptr); side_evJ.resize(Sy.num_levels, nullptr); }
-                    if (!side_evF[lv] && (!own_struct.event(&side_evF[lv], hipEventDisableTiming) || !own_struct.event(&side_evJ[lv], hipEventDisableTiming))) return false;
-                    if (!side_open) { HIPCHK(hipEventRecord(side_evF[lv], stream)); HIPCHK(hipStreamWaitEvent(stream3, side_evF[lv], 0)); side_open = true; }      // behind the level below
-                    std::swap(stream, stream3);
-                }
-                const bool ok = launch_bucket(P.single, lv, fc, 0);
-                if (side) std::swap(stream, stream3);
-                if (!ok) return false;
-            }
-            if (side_open) { HIPCHK(hipEventRecord(side_evJ[lv], stream3)); HIPCHK(hipStreamWaitEvent(stream, side_evJ[lv], 0)); }      // the level above reads what they wrote
-        }
-        if (!la_join()) return false;
+        if (!run_factor_list(P.factor_single[optimistic ? 1 : 0])) return false;
         LAUNCH(KK_STATS, k_zero_i32, dim3(1), dim3(64), 0, stream, d_stats, 4);
         LAUNCH(KK_STATS, k_reduce_stats, dim3(std::min(64, (Sy.num_sn + 255) / 256)), dim3(256), 0, stream, V.fstat, V.apfail, V.sn_owner, Sy.num_sn, -2, d_stats);
         HIPCHK(hipGetLastError());
@@ -915,7 +785,7 @@ public:
     }
 
     bool norestore_on = !knob_disabled("norestore");      // (development knob: keep the safety copies of the pivot blocks in the optimistic schedule too)
-    bool optimistic = false;                 // (set per factorisation: see launch_bucket)
+    bool optimistic = false;                 // (set per factorisation: which of P.factor_single runs)
     bool optimistic_ok = true;               // the optimistic schedule may be tried (false while a back-off runs: see factor())
     int  opt_backoff = 0, opt_wait = 0;      // after a fall-back: opt_wait factorisations on the full schedule, then one more optimistic try; every repeat doubles the wait (8 .. 256)
     hipGraphExec_t g_factor_full = nullptr;  // the schedule with every strict launch (g_factor: the optimistic one)
@@ -1725,9 +1595,8 @@ public:
     }
 
     // ---------------- multi-GPU orchestration (eager launches) ----------------
-    bool launch_fronts(const Sched& sc, int top_mode) {
-        for (int lv = 0; lv < S->num_levels; ++lv)
-            for (int fc = 0; fc < FC_COUNT; ++fc) if (!launch_bucket(sc, lv, fc, top_mode)) return false;
+    bool launch_fronts(const std::vector<FactorLaunch>& list) {
+        if (!run_factor_list(list)) return false;
         HIPCHK(hipGetLastError());
         return true;
     }
@@ -1758,15 +1627,14 @@ public:
         hipLaunchKernelGGL(k_factor_prologue, dim3(grid1d(S->n)), dim3(256), 0, stream, V);
         hipLaunchKernelGGL(k_gather_values, dim3(grid1d(S->nnz_a)), dim3(256), 0, stream, V);
         enqueue_scaling();
-        if (!launch_fronts(P.local, 0)) return false;
+        if (!launch_fronts(P.factor_local)) return false;
         HIPCHK(hipMemsetAsync(V.arena, 0, (size_t)P.ex.arena_doubles * sizeof(double), stream));
         return report_to_arena(0);
     }
     // replicated fronts of exchange step d held by this rank (their arena squares have been summed); afterwards the first rank of the range
     // reports what they contribute to the fronts of the wider ranges above
     bool enqueue_factor_step(int d) {
-        grp_step = d;
-        if (!launch_fronts(P.stage[d], 1)) return false;
+        if (!launch_fronts(P.factor_stage[d])) return false;
         return d > 0 ? report_to_arena(1 + d) : true;
     }
     bool enqueue_stats() {

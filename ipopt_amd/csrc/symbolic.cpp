@@ -932,7 +932,7 @@ static bool finish_analysis(Symbolic& S, const SymbolicOptions& opt, const std::
         //      ICNTL(14) sizes exactly that workspace).  The addresses stay STATIC (the factorisation remains one replayable launch sequence): the plan is made here, once,
         //      over the LEVEL schedule.  A block of a BIG front that hosts no in-place chain is written at its front's level and dead once the front that extend-adds it (its
         //      parent in the assembly tree) has been formed -- plus a WINDOW of levels, because launches of a level may still run on the look-ahead streams while the next
-        //      levels are enqueued: the numeric schedule joins those streams into the main one at every level that is a multiple of the window (numeric.hip, enqueue_factor),
+        //      levels are enqueued: the numeric schedule joins those streams into the main one at every level that is a multiple of the window (launch_plan.cpp, build_factor_schedule),
         //      so whatever was launched at level l has completed before anything of level >= l + window starts.  Blocks that host a chain hold that chain's panels (factor
         //      storage) and stay; blocks of small fronts stay too (a few per cent of the pool; the data-flow launches over several levels tag them by epoch).  First fit over
         //      the free list, blocks sorted by (level, size descending).  One GPU only (a rank's own subtrees report to the arena after ALL its levels).
@@ -989,7 +989,7 @@ static bool finish_analysis(Symbolic& S, const SymbolicOptions& opt, const std::
                 }
                 roff[s] = off;
                 // written at level lv, read at level cons[s]; everything launched there has completed before level cons[s] + WINDOW starts being enqueued -- rounded up to the
-                // next join: free from the first multiple of WINDOW that is >= cons + 1 ... + WINDOW covers it (see enqueue_factor)
+                // next join: free from the first multiple of WINDOW that is >= cons + 1 ... + WINDOW covers it (see build_factor_schedule)
                 live.insert({std::min(cons[s], S.num_levels) + WINDOW + 1, {off, need}});
             }
             const int64_t saved = cand_total - rpeak;

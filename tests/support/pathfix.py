@@ -60,8 +60,8 @@ TABLE = [
     ("asm_pull", "grid48x44", "inferred", ROUNDING,
      "panel columns: the pull form writes (sum of the children) and adds the A entries behind it, the scatter form zero-fills, adds the A entries FIRST and the children behind them"),
     ("lookahead", "clique_grid", "plan", BITWISE, "part 1 / part 2 of a split update are the same tiles on two streams (test_lookahead_split_updates_are_exact_and_reproducible)"),
-    ("p1_small", "clique_grid", "inferred", BITWISE, "part 1 in 64 x 64 tiles: the same k order per entry as the 128 x 128 tiles"),
-    ("side_small", "clique_grid", "inferred", BITWISE, "stream only: the same launches on a third stream"),
+    ("p1_small", "clique_grid", "plan", BITWISE, "part 1 in 64 x 64 tiles: the same k order per entry as the 128 x 128 tiles"),
+    ("side_small", "clique_grid", "plan", BITWISE, "stream only: the same launches on a third stream"),
     ("norestore", "clique_grid", "inferred", BITWISE, "only the safety copy of a pivot block is left out; no pivot block of this fixture is rejected"),
     ("front_df", "lukvl1000", "plan", ROUNDING,
      "the fronts of order 17 .. 32: k_front_df eliminates them in natural order on one wavefront (front_lds32_body: pivot reciprocal, rank-1 updates by half-wavefronts), the per-level schedule hands them to the strict k_front_reg<64, 4> (pivot search, register tiles) -- the same pivot statistics here, another operation order per entry; the fronts of order <= 16 run front_dpp16_body either way"),

@@ -2,6 +2,11 @@
 trailing update, the XCD tile tables, the fused pivot-block + panel-solve launch ... -- shows with these facts that its fixture runs it: a later change
 of the ordering or of a threshold then fails a CPU test instead of silently emptying a GPU one.
 
+What the FACTORISATION launches is counted, not restated: the exported factor schedules ("factor.single.full" / "factor.single.opt", one record per
+launch and stream operation, built by launch_plan.cpp build_factor_schedule and walked as they are by numeric.hip) hold every launch decision once.  The
+solve-side facts -- pair_levels, pair16_levels, leafchain_solve -- still restate numeric.hip solve_sweep / solve_level: the solve walkers are the
+follow-up of the same shape.
+
 reach(solver) is evaluated under the MI355X_KKT_DISABLE / MI355X_KKT_TUNE settings of the moment (the plan is rebuilt from the environment at every
 query), so one analysed handle gives the facts of both legs of an A/B test.  Every fact is a count (0 = not reached)."""
 import numpy as np
@@ -9,10 +14,17 @@ import numpy as np
 FC_WAVE, FC_LDS64, FC_LDS128, FC_BIG, FC_COUNT = 0, 1, 2, 3, 4
 BIT_TFUSE, BIT_SELFASM, BIT_SOLO, BIT_SPLIT, BIT_TTAB, BIT_TTAB2, BIT_ASMCUT, BIT_ASMFAST, BIT_ALIAS = (1 << i for i in range(9))
 INPUTS = ["chain_solve", "fuse_dt", "fastpiv", "asm_pull", "leafchain", "front_df", "tfuse", "fuse_upd", "selfasm", "grouped", "xcd_tiles", "lookahead",
-          "pair_solve", "p1_small", "la_wgs", "la_min_nt", "grp_rbw_max", "chain_solve_maxc", "fuse_dt_maxwg", "la_min_tiles"]
+          "pair_solve", "p1_small", "la_wgs", "la_min_nt", "grp_rbw_max", "chain_solve_maxc", "fuse_dt_maxwg", "la_min_tiles", "side_small"]
 PLAN_ARRAYS = ["scalars", "path_scalars", "inputs", "level_list", "path_bits", "asm_fast_ok", "asmcut", "levels", "groups", "tiny16", "tiny_split", "mid_split",
                "big_split", "lc_ptr", "lc_fronts", "df_runs", "chain_segs", "chain_links", "chain_descs", "single.ptr", "single.maxm", "single.maxk",
-               "single.last0", "single.last1", "single.allsolo"]
+               "single.last0", "single.last1", "single.allsolo", "factor.single.full", "factor.single.opt"]
+# the records of a factor schedule (include/mi355x_kkt.h): columns of the exported rows, ops, streams
+REC = 13
+OP, STREAM, KIND, GX, GY, BLOCK, LV, B0, LDS, A0, A1, A2, A3 = range(REC)
+(FO_LEAF_CHAIN, FO_FRONT_DF, FO_FRONT_DPP16, FO_REG_64_2, FO_REG_64_4, FO_REG_64_8, FO_REG_256_6_FAST4, FO_REG_256_8_FAST, FO_REG_256_6, FO_REG_256_8,
+ FO_ASSEMBLE, FO_ASSEMBLE2, FO_GRP_FUSED, FO_DIAG_TRSM, FO_DIAG_REG, FO_DIAG_REG_1024, FO_TRSM, FO_TRSM_WIDE, FO_SCHUR64, FO_SCHUR, FO_SCHUR_P1, FO_SCHUR_Q,
+ FO_FORK, FO_FORK_DONE, FO_JOIN, FO_SIDE_OPEN, FO_SIDE_CLOSE, FO_COUNT) = range(28)
+FS_MAIN, FS_LOOKAHEAD, FS_SIDE = 0, 1, 2
 
 
 def plan_arrays(s):
@@ -34,14 +46,12 @@ def reach(s):
     lp = s.symbolic(13, nl * FC_COUNT + 1)
     nchild = np.bincount(parent[parent >= 0], minlength=nsn)
     A = plan_arrays(s)
-    L, bits, fast_ok, asmcut = A["level_list"], A["path_bits"], A["asm_fast_ok"], A["asmcut"]
+    L, bits, asmcut = A["level_list"], A["path_bits"], A["asmcut"]
     scal, ps = A["scalars"], A["path_scalars"]
     inp = dict(zip(INPUTS, (int(x) for x in A["inputs"])))
-    lev = A["levels"].reshape(-1, 10); grp = A["groups"].reshape(-1, 11)
-    la_tiles2, asm_skip, narrow = lev[:, 1], lev[:, 3], lev[:, 4]
-    part0, part1, wave_mmax, wave_kmax = lev[:, 5], lev[:, 6], lev[:, 8], lev[:, 9]
-    maxm, maxk = A["single.maxm"], A["single.maxk"]
-    pair_solve, la_any, ttab_len, grp_cut = int(ps[0]), int(ps[1]), int(ps[2]), int(ps[3])
+    wave_mmax = A["levels"].reshape(-1, 10)[:, 8]
+    maxk = A["single.maxk"]
+    pair_solve, la_any, ttab_len = int(ps[0]), int(ps[1]), int(ps[2])
     lc_levels, grouped = int(scal[2]), int(scal[5])
     big = cls == FC_BIG
     upd = order - cols
@@ -70,79 +80,28 @@ def reach(s):
     F["leafchain_solve"] = lcs
     F["pair_levels"] = sum(1 for lv in range(lcs, nl) if pair_solve and not in_seg[lv] and lp[lv * FC_COUNT + 1] > lp[lv * FC_COUNT])
     F["pair16_levels"] = sum(1 for lv in range(lcs, nl) if pair_solve and not in_seg[lv] and lp[lv * FC_COUNT + 1] > lp[lv * FC_COUNT] and wave_mmax[lv] <= 16)
-    fused = asm2 = narrow_fused = aff = grp_launch = schur128 = schur64 = asm_col = la_fork = p1_small = 0
-    for lv in range(nl):
-        b0, b1 = int(lp[lv * FC_COUNT + FC_BIG]), int(lp[lv * FC_COUNT + FC_BIG + 1])
-        nball = b1 - b0
-        if nball == 0:
-            continue
-        mm, kk = int(maxm[lv]), int(maxk[lv])
-        if not asm_skip[lv]:
-            # restates numeric.hip launch_assemble: `v2 = v2 && maxch * ldi * sizeof(int) <= 158 KiB && (nfronts >= 32 && maxch <= 6)` with v2 = every asm_fast_ok != 0
-            ok = fast_ok[b0:b1]
-            maxch, ldi = max(1, int(ok.max())), (mm + 15) & ~15
-            if np.all(ok != 0) and maxch * ldi * 4 <= 158 * 1024 and nball >= 32 and maxch <= 6:
-                asm2 += 1
-            else:
-                asm_col += 1
-        if grouped and lv >= grp_cut:                       # launch_bucket: the chain groups whose first link sits here (launch_groups)
-            g0, g1, gsplit = int(grp[lv, 0]), int(grp[lv, 1]), int(grp[lv, 2])
-            if g1 > g0:
-                grp_launch += 1
-                if gsplit > 0 and grp[lv, 4] > 0:
-                    schur64 += 1
-                    aff += gsplit >= 16
-                if g1 - g0 > gsplit:
-                    schur128 += 1
-                    if grp[lv, 7] > 0:                      # launch_groups `G.la2[lv] > 0`: part 1 on the main stream, part 2 forked to the second one
-                        la_fork += 1
-                        p1_small += bool(inp["p1_small"] and grp[lv, 6] * (g1 - g0 - gsplit) <= 512)      # (... `knobs.p1_small && G.la1[lv] * nb <= 512`: k_big_schur_p1)
-            continue
-        nrb = (mm + 63) // 64
-        bs = int(A["big_split"][lv])
-        # restates numeric.hip launch_big: `knobs.fuse_dt && (single || multi) && kk <= 64 && nball * (1 + nrb) <= knobs.fuse_dt_maxwg`
-        if inp["fuse_dt"] and kk <= 64 and nball * (1 + nrb) <= inp["fuse_dt_maxwg"]:
-            fused += 1
-            if narrow[lv] > 0 and nball * (1 + nrb + int(narrow[lv])) <= 256:      # (... `ntu`: the narrow updates ride in that launch)
-                narrow_fused += 1
-                continue
-        else:
-            aff += nball >= 16                               # k_big_trsm over nball fronts (xcd_affine acts on >= 16 fronts)
-        if bs > 0 and part0[lv] > 0:
-            schur64 += 1
-            aff += bs >= 16                                  # k_big_schur64 over bs fronts
-        if nball > bs:
-            schur128 += 1
-            la_fork += bool(la_tiles2[lv] > 0)               # launch_big `single && P.la_tiles2[lv] > 0`
-    F["fused_diag_trsm_level"] = fused; F["narrow_fused_level"] = narrow_fused; F["assemble2_level"] = asm2; F["assemble_column_level"] = asm_col
+    full, opt = A["factor.single.full"].reshape(-1, REC), A["factor.single.opt"].reshape(-1, REC)
+    n_of = lambda recs, *ops: int(np.sum(np.isin(recs[:, OP], ops)))
+    F["fused_diag_trsm_level"] = n_of(full, FO_DIAG_TRSM)
+    F["narrow_fused_level"] = int(np.sum((full[:, OP] == FO_DIAG_TRSM) & (full[:, GY] > 1 + full[:, A0])))      # (workgroups behind the pivot block and the row blocks: the narrow updates)
+    F["assemble2_level"] = n_of(full, FO_ASSEMBLE2); F["assemble_column_level"] = n_of(full, FO_ASSEMBLE)
     # (the split bit alone launches nothing: only the 128 x 128 update of fronts above 1024 rows reads it)
-    F["lookahead_fork_level"] = int(la_fork); F["p1_small_level"] = int(p1_small)
-    F["xcd_affine_launch"] = int(aff); F["group_launch_level"] = grp_launch; F["schur128_level"] = schur128; F["schur64_level"] = schur64
+    F["lookahead_fork_level"] = n_of(full, FO_FORK); F["p1_small_level"] = n_of(full, FO_SCHUR_P1)
+    # xcd_affine acts in k_big_trsm and k_big_schur64 on launches over >= 16 fronts
+    F["xcd_affine_launch"] = int(np.sum(np.isin(full[:, OP], (FO_TRSM, FO_TRSM_WIDE, FO_SCHUR64)) & (full[:, GY] >= 16)))
+    F["group_launch_level"] = n_of(full, FO_GRP_FUSED)
+    F["schur128_level"] = len(set(full[np.isin(full[:, OP], (FO_SCHUR, FO_SCHUR_P1)), LV].tolist())); F["schur64_level"] = n_of(full, FO_SCHUR64)
     # k_big_assemble / k_big_assemble2 with V.asm_pull: the fronts that gather children's blocks (not in place on a child, not assembling themselves)
     F["asm_pull_fronts"] = int(np.sum(big & (alias < 0) & (nchild > 0))) if inp["asm_pull"] else 0
     F["asm_gather_fronts"] = int(np.sum(big & (alias < 0) & (nchild > 0)))
-    # side stream (numeric.hip enqueue_factor `side`): look-ahead on, a bucket of <= 16 small fronts beside one eight times as large
-    side = 0
-    skipped = np.zeros(nl, dtype=bool)                     # levels the optimistic schedule hands to k_leaf_chain / k_front_df as a whole
-    if inp["fastpiv"]:
-        skipped[:lc_levels] = True
-        for lv0, lv1, *_ in A["df_runs"].reshape(-1, 5):
-            skipped[lv0:lv1 + 1] = True
-    for lv in range(nl):
-        if skipped[lv]:
-            continue
-        nbs = [int(lp[lv * FC_COUNT + fc + 1] - lp[lv * FC_COUNT + fc]) for fc in range(FC_COUNT)]
-        for fc in range(FC_BIG):
-            if la_any and 0 < nbs[fc] <= 16 and max(nbs) >= 8 * nbs[fc] and sum(nbs) > nbs[fc]:
-                side += 1
-    F["side_small_bucket"] = side
-    # the optimistic schedule drops strict launches where the static-order kernels take a whole bucket, and runs the leaf chains / data-flow runs
-    # k_front_reg<64, 2> (launch_bucket `nt > 0`): the strict launch over >= 2 048 fronts of order <= 16; the optimistic schedule leaves it out where the
-    # static-order kernel has taken the whole bucket (`optimistic && n16 == nb`) and on the levels of the leaf chains and the data-flow runs
-    wave_nb = np.array([lp[lv * FC_COUNT + 1] - lp[lv * FC_COUNT] for lv in range(nl)])
-    F["reg2_level_strict"] = int(np.sum(A["tiny_split"] > 0))
-    F["reg2_level_optimistic"] = int(np.sum((A["tiny_split"] > 0) & ~skipped & ~((A["tiny16"] == wave_nb) & bool(inp["fastpiv"]))))
-    F["optimistic_only"] = (lc_levels if inp["fastpiv"] else 0) + F["df_run"]
+    # side stream: the (level, class) buckets whose launches the schedule a factorisation first tries puts there
+    side = opt[(opt[:, STREAM] == FS_SIDE) & (opt[:, KIND] >= 0)]
+    F["side_small_bucket"] = len(set(zip(side[:, LV].tolist(), side[:, KIND].tolist())))      # (the profiling kind of a small-front launch is its class)
+    # the optimistic schedule drops strict launches where the static-order kernels take a whole bucket, and runs the leaf chains / data-flow runs:
+    # k_front_reg<64, 2> is the strict launch over >= 2 048 fronts of order <= 16
+    F["reg2_level_strict"] = n_of(full, FO_REG_64_2)
+    F["reg2_level_optimistic"] = n_of(opt, FO_REG_64_2)
+    F["optimistic_only"] = int(np.sum(opt[opt[:, OP] == FO_LEAF_CHAIN, A1] + 1)) + n_of(opt, FO_FRONT_DF)      # (levels of the leaf chains + data-flow runs)
     # fronts of order exactly 1024 and 1025 in ONE launch (the two sides of the big_split edge)
     level = s.symbolic(5, nsn)
     F["edge_1024_1025_level"] = len(set(level[big & (order == 1024)].tolist()) & set(level[big & (order == 1025)].tolist()))

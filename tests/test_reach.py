@@ -1,6 +1,6 @@
 """Host only (no device): which kernel paths the fixtures of the GPU suite REACH (tests/support/reach.py over get_symbolic / get_launch_plan), and that
-every MI355X_KKT_DISABLE switch of tests/test_gpu_fast_paths.py changes the launch plan -- or, where it acts in the launch code or in a kernel, the
-restated launch condition -- on the fixture it is tested on.  A fixture on which a knob changes nothing is no test of it: a later change of the
+every MI355X_KKT_DISABLE switch of tests/test_gpu_fast_paths.py changes the launch plan -- its tables, or the exported factor schedule that the
+device walks record by record -- on the fixture it is tested on; where a switch acts inside a kernel, the structural precondition of its path.  A fixture on which a knob changes nothing is no test of it: a later change of the
 ordering or of a threshold fails here instead of silently emptying a GPU test."""
 import functools
 
@@ -61,15 +61,18 @@ KNOBS = {
     "front_df": (["df_runs"], "df_run"),
     "pair_solve": (["path_scalars"], "pair_levels"),
     "fastpiv": (["df_runs", "lc_ptr", "lc_fronts", "scalars"], "leaf_chain"),
-    # these act in the launch code (numeric.hip) or in a kernel through a flag: the plan's exported `inputs` carry the switch, the condition is restated in reach()
-    "fuse_dt": (["inputs"], "fused_diag_trsm_level"),
+    # these select launches: the factor schedules differ, and the fact counts their records
+    "fuse_dt": (["inputs", "factor.single.full", "factor.single.opt"], "fused_diag_trsm_level"),
+    "p1_small": (["inputs", "factor.single.full", "factor.single.opt"], "p1_small_level"),
+    "side_small": (["inputs", "factor.single.full", "factor.single.opt"], "side_small_bucket"),
+    # this one acts in a kernel through a flag: the plan's exported `inputs` carry the switch
     "asm_pull": (["inputs"], "asm_pull_fronts"),
-    "p1_small": (["inputs"], "p1_small_level"),
 }
 # (on a system without small fronts `fastpiv` is the kernel flag DevView::fastpiv alone: the pivot blocks of the big fronts)
 OVERRIDE = {("fastpiv", "grid24"): (["inputs"], "fastpiv_big_blocks")}
-# knobs numeric.hip reads itself: nothing in the plan can show them; the structural precondition of the path they switch (reach is INFERRED)
-PRECONDITION = {"xcd_affine": "xcd_affine_launch", "side_small": "side_small_bucket", "norestore": "group_launch_level"}
+# knobs numeric.hip reads itself (DevView flags: they select nothing on the host): nothing in the plan can show them; the structural precondition of
+# the path they switch (reach is INFERRED)
+PRECONDITION = {"xcd_affine": "xcd_affine_launch", "norestore": "group_launch_level"}
 
 
 @pytest.mark.parametrize("fixture", sorted(REACH))

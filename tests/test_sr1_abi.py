@@ -151,19 +151,26 @@ def test_the_zero_matrix_is_singular_and_m_33_is_fatal():
     assert C.CDLL(ipopt_amd.library_path()).mi355x_kkt_lbfgs_sr1_coefficients(33, None, None, None, C.c_double(1.0), None, None, None) == kkt.FATAL
 
 
-def _run_host_program_under_sanitizers(tmp_path, name):
-    """tests/support/<name>.cpp, a stand-alone program with its own main, on the CPU: nothing is loaded into python under a sanitizer"""
+def _run_host_program_under_sanitizers(tmp_path, name, sources=()):
+    """tests/support/<name>.cpp, a stand-alone program with its own main, on the CPU: nothing is loaded into python under a sanitizer.  sources: host-only
+    files of ipopt_amd/csrc it is linked with, compiled with the same flags (side by side: the analysis alone takes most of a minute)"""
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     if cxx is None:
         pytest.skip("no C++ compiler")
-    flags = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+    flags = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-pthread"]
     probe = tmp_path / "probe.cpp"; probe.write_text("int main() { return 0; }\n")
     if subprocess.run([cxx, *flags, str(probe), "-o", str(tmp_path / "probe")], capture_output=True).returncode != 0 or \
             subprocess.run([str(tmp_path / "probe")], capture_output=True).returncode != 0:
         pytest.skip("the compiler has no sanitizer runtime")
+    csrc = os.path.join(ROOT, "ipopt_amd", "csrc")
+    units = [os.path.join(ROOT, "tests", "support", name + ".cpp")] + [os.path.join(csrc, f) for f in sources]
+    objs = [str(tmp_path / (os.path.basename(u) + ".o")) for u in units]
+    jobs = [subprocess.Popen([cxx, *flags, "-I", csrc, "-c", u, "-o", o], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for u, o in zip(units, objs)]
+    for j in jobs:
+        out, _ = j.communicate()
+        assert j.returncode == 0, out
     exe = tmp_path / name
-    build = subprocess.run([cxx, *flags, "-I", os.path.join(ROOT, "ipopt_amd", "csrc"), os.path.join(ROOT, "tests", "support", name + ".cpp"), "-o", str(exe)],
-                           capture_output=True, text=True)
+    build = subprocess.run([cxx, *flags, *objs, "-o", str(exe)], capture_output=True, text=True)
     assert build.returncode == 0, build.stderr
     run = subprocess.run([str(exe)], capture_output=True, text=True)
     print(run.stdout, run.stderr)
