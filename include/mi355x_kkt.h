@@ -306,6 +306,40 @@ int  mi355x_kkt_lbfgs_undo(mi355x_kkt_handle h, int* undone);
 int  mi355x_kkt_lbfgs_sr1_info(mi355x_kkt_handle h, int* type, int* nneg, int* can_undo, double* E, int capacity);
 int  mi355x_kkt_lbfgs_sr1_coefficients(int m, const double* sts, const double* L, const double* D, double sigma, double* E_out, double* Qs_out, int* nneg_out);
 
+/* ---- the restoration phase: Ypart in the history, eta per push, B0 = sigma I or eta D_R -----------------------------------------------------------
+ * The `update_for_resto_` half of the same updater (IpLimMemQuasiNewtonUpdater.cpp UpdateHessian :141-343, :359-700, UpdateInternalData :820-868,
+ * SetW, RecalcY/D/L :1338-1433), `limited_memory_special_for_resto` included.  Once per history: DR (`rows` positive entries, the restoration NLP's
+ * DR_x), type (0 BFGS, 1 SR1) and special (0/1).  Per push: s, ypart (y WITHOUT the objective part) and eta = Eta(mu) > 0.  With o the element-wise
+ * product, and restating the reference as it is:
+ *   y_new   = ypart + eta DR o s (:337-341): the BFGS skip test, sigma, s^T y_new and y_new^T y_new use it.
+ *   stored Y  = Ypart + eta S, WITHOUT DR (RecalcY is handed S in the place of DR o S, :864), with the CURRENT eta in every column; D_j = S_j^T Y_j and
+ *           L_ij = S_i^T Y_j (i > j) are those of this Y and change with every eta.  Nothing is recomputed over the vectors: G = S^T Ypart, S^T S
+ *           and, when special, R = S^T (DR o S) grow by one row and column per push, and D = diag(G) + eta diag(S^T S), L = G + eta S^T S below
+ *           the diagonal.
+ *   BFGS    the skip test of _lbfgs_push on (s, y_new); then D, L at the new eta, and when min D is not > 0 the push is SKIPPED (outcome 1, nothing
+ *           but skipped_in_a_row changes, :387-399).  sigma as for _lbfgs_push from (s^T s, s^T y_new, y_new^T y_new); special: sigma stays -1 and is
+ *           never used.  V takes only a NEW LAST COLUMN y_new / sqrt(s^T y_new) (:440-451): older columns stay what they were when pushed, although
+ *           eta may have changed since (per pair the eta and the scale of its push are kept, and the column is formed from the ring).  d = D^(-1/2),
+ *           Lt = L diag(d), M = Lt Lt^T + sigma S^T S, or + eta R when special; C, Lbar as for _lbfgs_push; U = sigma S C + V Lbar, or
+ *           eta (DR o S) C + V Lbar.  M not positive definite: outcome 2, the pair and its V column are stored, the installed columns stay.
+ *   SR1     no curvature test; sigma by the SR1 rule from (s^T s, s^T y_new, y_new^T y_new), not when special; Z = D + L + L^T - sigma S^T S, or
+ *           - eta R; the split rule of _lbfgs_define_sr1 (a skip changes nothing but the counter); W = Y - sigma S, or Y - eta DR o S, Y the stored
+ *           one above; U, V = W Qs split as there.  _lbfgs_undo works as for a plain SR1 history (eta and the Gram matrices come back too).
+ *   B0      sigma I, or the vector eta DR when special (SetW :1343-1355): the caller puts it on the x diagonal before factoring, as it puts sigma.
+ * The reference's |s|_max < 100 eps skip (:350-357) and its limited_memory_max_skipping reset stay with the caller, as the reset policy does.
+ * A history defined by _lbfgs_define_resto is pushed by _lbfgs_push_resto / _push_resto_device ONLY (_lbfgs_push / _push_device on it: FATAL, and
+ * the other way round); _reset (sigma = -1 when special, else init_val), _clear, _undo, _info, _sr1_info and _get serve it unchanged.  _lbfgs_get:
+ * what 1 is Ypart, 4 and 5 are D, L at the eta of the last stored push; 10 G (memory x memory: diagonal and strictly lower part), 11 R (memory x
+ * memory; zero unless special), 12 eta_col, 13 dv (memory; dv is 0 for SR1), 14 DR (rows); 10..14 on a plain history: FATAL.
+ *   _lbfgs_resto_info  outputs may be NULL; resto 1 for such a history, special, eta of the last stored push (-1 before the first)
+ * Arguments are checked before the device is touched (dr null or with an entry that is not positive and finite, eta not positive and finite, type
+ * outside {0, 1}, special outside {0, 1}); single-GPU handles only.  A push costs what a plain push costs plus one more streamed vector per kernel. */
+int  mi355x_kkt_lbfgs_define_resto(mi355x_kkt_handle h, int rows, int max_history, int type, int special, int init, double init_val, double sigma_min,
+                                   double sigma_max, const double* dr);
+int  mi355x_kkt_lbfgs_push_resto(mi355x_kkt_handle h, const double* s, const double* ypart, double eta, int* outcome);
+int  mi355x_kkt_lbfgs_push_resto_device(mi355x_kkt_handle h, const double* d_s, const double* d_ypart, double eta, int* outcome);
+int  mi355x_kkt_lbfgs_resto_info(mi355x_kkt_handle h, int* resto, int* special, double* eta);
+
 int  mi355x_kkt_set_pivtol(mi355x_kkt_handle h, double u);
 int  mi355x_kkt_set_pivtolmax(mi355x_kkt_handle h, double umax);
 /* IncreaseQuality (IpSparseSymLinearSolverInterface.hpp:220): raises u <- min(pivtolmax, u^0.75) (the rule of

@@ -504,7 +504,7 @@ int mi355x_kkt_lbfgs_get(mi355x_kkt_handle h, int what, double* out, int64_t cap
     if (!h) return MI355X_KKT_FATAL;
     const char* name = "lbfgs_get";
     if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
-    if (what < 0 || what > 6) LR_FAIL("what must be in [0, 6]");
+    if (what < 0 || (what > 6 && what < 10) || what > 14) LR_FAIL("what must be in [0, 6], or in [10, 14] (a restoration-phase history)");
     if (capacity < 0) LR_FAIL("capacity must be >= 0");
     if (capacity > 0 && !out) LR_FAIL("out is null with capacity > 0");
     return lowrank_call(h, name, false, [&] { return h->num->lbfgs_get(what, out, (long long)capacity); });
@@ -555,6 +555,42 @@ int mi355x_kkt_lbfgs_sr1_coefficients(int m, const double* sts, const double* L,
     const int r = mi355x::lb_sr1_coefficients(m, sts, L, m, D, sigma, E_out, Qs_out, m, &nneg);
     if (nneg_out) *nneg_out = nneg;
     return r == mi355x::LB_SR1_OK ? MI355X_KKT_SUCCESS : r == mi355x::LB_SR1_SKIP ? MI355X_KKT_SINGULAR : MI355X_KKT_FATAL;
+}
+// ---- the restoration phase: Ypart in the ring, eta per push, the fixed scaling DR; B0 = sigma I, or eta DR when special ----
+int mi355x_kkt_lbfgs_define_resto(mi355x_kkt_handle h, int rows, int max_history, int type, int special, int init, double init_val, double sigma_min, double sigma_max, const double* dr)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "lbfgs_define_resto";
+    if (lbfgs_define_args(h, name, rows, max_history, init, init_val) != 0) return MI355X_KKT_FATAL;
+    if (type != MI355X_KKT_LBFGS_BFGS && type != MI355X_KKT_LBFGS_SR1) LR_FAIL("type must be 0 (BFGS) or 1 (SR1)");
+    if (special != 0 && special != 1) LR_FAIL("special must be 0 or 1");
+    if (!(sigma_min > 0.0) || !std::isfinite(sigma_min)) LR_FAIL("sigma_min must be positive and finite");
+    if (!(sigma_max >= sigma_min) || !std::isfinite(sigma_max)) LR_FAIL("sigma_max must be finite and >= sigma_min");
+    if (!dr) LR_FAIL("dr is null");
+    for (int i = 0; i < rows; ++i)
+        if (!(dr[i] > 0.0) || !std::isfinite(dr[i])) LR_FAIL("dr must be positive and finite (entry " + std::to_string(i) + " is not)");
+    return lowrank_call(h, name, false, [&] { return h->num->lbfgs_define_resto(rows, max_history, type, special, init, init_val, sigma_min, sigma_max, dr); });
+}
+static int lbfgs_push_resto_any(mi355x_kkt_handle h, const char* name, const double* s, const double* ypart, double eta, bool device, int* outcome)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    if (outcome) *outcome = 1;
+    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
+    if (!s) LR_FAIL(device ? "d_s is null" : "s is null");
+    if (!ypart) LR_FAIL(device ? "d_ypart is null" : "ypart is null");
+    if (!(eta > 0.0) || !std::isfinite(eta)) LR_FAIL("eta must be positive and finite");
+    int oc = 1;
+    const int st = lowrank_call(h, name, false, [&] { return h->num->lbfgs_push_resto(s, ypart, eta, device, &oc); });
+    if (st == MI355X_KKT_SUCCESS && outcome) *outcome = oc;
+    return st;
+}
+int mi355x_kkt_lbfgs_push_resto(mi355x_kkt_handle h, const double* s, const double* ypart, double eta, int* outcome) { return lbfgs_push_resto_any(h, "lbfgs_push_resto", s, ypart, eta, false, outcome); }
+int mi355x_kkt_lbfgs_push_resto_device(mi355x_kkt_handle h, const double* d_s, const double* d_ypart, double eta, int* outcome) { return lbfgs_push_resto_any(h, "lbfgs_push_resto_device", d_s, d_ypart, eta, true, outcome); }
+int mi355x_kkt_lbfgs_resto_info(mi355x_kkt_handle h, int* resto, int* special, double* eta)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    if (resto) *resto = 0; if (special) *special = 0; if (eta) *eta = 0.0;
+    return lowrank_call(h, "lbfgs_resto_info", false, [&] { h->num->lbfgs_resto_info(resto, special, eta); return true; });
 }
 #undef LR_FAIL
 

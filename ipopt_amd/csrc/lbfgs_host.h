@@ -18,6 +18,8 @@
 //   lb_undo               1: st = backup with skipped = backup.skipped + 1, the backup is invalidated (one level).  0: no valid backup, nothing
 //                         changes.  It does not look at the type: a BFGS history never has a valid backup, so it answers 0 there; refusing an
 //                         undo on a BFGS history as an error is the caller's business (lbfgs_undo in numeric.hip does).
+// Last, the restoration phase (LbParams::resto): LbResto, the value that travels with LbState there, and lb_push_bfgs_resto, lb_push_sr1_resto,
+// lb_undo_resto, which take 3 m + 6 dots and eta.  A plain history never sees that part.
 #pragma once
 #include <cmath>
 #include <limits>
@@ -211,6 +213,7 @@ inline int lb_sr1_coefficients(int m, const double* sts, const double* L, int ld
 struct LbParams {                       // the constants of a history, set by define and never by a push.  type: 0 BFGS, 1 SR1
     int type = 0, max_history = 0, slots = 0, init = 0;      // slots = max_history (BFGS) or max_history + 1 (SR1: the pair a push evicts survives that push)
     double init_val = 1.0, smin = 1e-8, smax = 1e8;
+    int resto = 0, special = 0;         // resto: a restoration-phase history (lb_push_*_resto below); special: its B0 is eta D_R, not sigma I
 };
 struct LbState {                        // everything a push can change; a plain value: copied, assigned and compared as a whole
     int m = 0, head = 0, nneg = 0, skipped = 0;
@@ -256,6 +259,108 @@ inline int lb_undo(LbState& st, const LbState& backup, bool& backup_valid)
 {
     if (!backup_valid) return 0;
     st = backup; st.skipped = backup.skipped + 1; backup_valid = false;
+    return 1;
+}
+
+// ---- the restoration phase (reference update_for_resto_: UpdateHessian :331-343, :372-400, UpdateInternalData :820-868, RecalcY/D/L :1382-1433) ----
+// Per push the caller gives s, ypart (y without the objective part) and eta; DR (rows positive entries) is fixed per history.  With o the element-wise
+// product:  y_new = ypart + eta DR o s  serves the BFGS skip test, sigma and the new column of V;  the STORED Y is  Ypart + eta S  -- WITHOUT DR: the
+// reference hands S to RecalcY in the place of DR o S (:864) -- with the CURRENT eta in every column, and D, L are those of (S, that Y).  Nothing is
+// recomputed over the vectors here: with G = S^T Ypart (diagonal GD, strictly lower part GL), S^T S and, when special, R = S^T (DR o S), which grow by
+// one row and column per push like D, L, S^T S of a plain history,
+//   D_j = fma(eta, (S^T S)_jj, G_jj)      L_ij = fma(eta, (S^T S)_ij, G_ij)  (i > j)
+// for any eta.  LbState keeps its layout (D, L are the recomputed ones, so lbfgs_get serves them unchanged); what the restoration phase adds is a second
+// plain value, LbResto, that travels with it: copied, assigned and compared as a whole, backed up with it.
+//   BFGS   V takes only a new last column  v = y_new / sqrt(s^T y_new)  (:440-451): older columns keep the eta and the scale of THEIR push, so per stored
+//          pair eta_col[j] and dv[j] = 1 / sqrt(s^T y_new) are kept and V_j = (Ypart_j + eta_col[j] DR o S_j) dv[j] is formed from the ring.
+//          d = D^(-1/2) of the recomputed D, M = Lt Lt^T + sigma S^T S, or + eta R when special; U = sigma S C + V Lbar, or eta (DR o S) C + V Lbar.
+//          The push is SKIPPED, nothing but the counter changes, when the recomputed min D is not > 0 (:387-399; a NaN counts).  special: sigma stays -1.
+//   SR1    no curvature test; sigma by lb_sr1_sigma on (s^T s, s^T y_new, y_new^T y_new) unless special; Z = D + L + L^T - sigma S^T S, or - eta R;
+//          W = Y - sigma S, or Y - eta DR o S, Y the stored one above.  dv is not used (0).
+// The reference's |s|_max < 100 eps skip (:350-357) and its limited_memory_max_skipping reset stay with the caller.
+struct LbResto {
+    double eta = -1.0;                  // of the last stored push (the reference's last_eta_ starts at -1)
+    double GD[LBH_MAX] = {}, GL[LBH_MAX * LBH_MAX] = {}, R[LBH_MAX * LBH_MAX] = {}, eta_col[LBH_MAX] = {}, dv[LBH_MAX] = {};
+};
+// the downloaded dots of a resto push, over the m pairs stored before it (oldest first): sS = s^T S_j, sYp = s^T Ypart_j, sR = s^T (DR o S_j) (read
+// only when special); ss = s^T s, syp = s^T ypart, ypyp = ypart^T ypart, sDs = s^T (DR o s), ypDs = ypart^T (DR o s), DsDs = (DR o s)^T (DR o s)
+struct LbRestoDots { const double *sS, *sYp, *sR; double ss, syp, ypyp, sDs, ypDs, DsDs; };
+static constexpr int LBH_NDOT_RESTO = 3 * LBH_MAX + 6;                 // the dots in the order of LbRestoDots
+static constexpr int LBH_NCOEF_RESTO = LBH_NCOEF + LBH_MAX;            // dv, C, Lbar (the layout of LBH_NCOEF, dv in the place of d), then eta_col
+
+inline LbParams lb_params_resto(int type, int special, int max_history, int init, double init_val, double smin, double smax)
+{ LbParams P = lb_params(type, max_history, init, init_val, smin, smax); P.resto = 1; P.special = special ? 1 : 0; return P; }
+inline LbState lb_fresh_resto(const LbParams& P) { LbState st; st.sigma = P.special ? -1.0 : P.init_val; return st; }
+inline double lb_resto_sy(const LbRestoDots& d, double eta) { return std::fma(eta, d.sDs, d.syp); }                                  // s^T y_new
+inline double lb_resto_yy(const LbRestoDots& d, double eta) { return std::fma(eta, std::fma(eta, d.DsDs, 2.0 * d.ypDs), d.ypyp); }   // y_new^T y_new
+
+// the candidate of a push: G, S^T S, R, eta_col, dv take the new pair (augment / shift), then D, L are recomputed at eta.  Returns the new m.
+inline int lb_resto_store(const LbParams& P, LbState& c, LbResto& r, const LbRestoDots& d, double eta, double dv_new)
+{
+    const int ld = LBH_MAX, m0 = c.m, full = m0 == P.max_history;
+    if (full) for (int j = 0; j + 1 < m0; ++j) { r.eta_col[j] = r.eta_col[j + 1]; r.dv[j] = r.dv[j + 1]; }
+    if (P.special) {                                                  // R like S^T S in lb_store
+        int m = m0, off = 0;
+        if (full) {
+            for (int j = 0; j + 1 < m; ++j) for (int i = 0; i + 1 < m; ++i) r.R[i + j * ld] = r.R[i + 1 + (j + 1) * ld];
+            off = 1; --m;
+        }
+        for (int j = 0; j < m; ++j) r.R[m + j * ld] = r.R[j + m * ld] = d.sR[j + off];
+        r.R[m + m * ld] = d.sDs;
+    }
+    const int m = lb_store(m0, P.max_history, r.GD, r.GL, c.STS, d.sS, d.sYp, d.ss, d.syp);
+    r.eta = eta; r.eta_col[m - 1] = eta; r.dv[m - 1] = dv_new;
+    for (int j = 0; j < m; ++j) {
+        c.D[j] = std::fma(eta, c.STS[j + j * ld], r.GD[j]);
+        for (int i = 0; i < m; ++i) c.L[i + j * ld] = i > j ? std::fma(eta, c.STS[i + j * ld], r.GL[i + j * ld]) : 0.0;
+    }
+    c.m = m;
+    return m;
+}
+
+// coef: LBH_NCOEF_RESTO doubles (zeroed here; valid on LB_PUSH_STORED only).  Works on a copy: a skip -- the curvature test on (s, y_new), or a
+// recomputed D_j that is not > 0 -- leaves st, rs untouched but for st.skipped + 1.  LB_PUSH_NOT_PD: the pair, its eta and dv ARE stored.
+inline int lb_push_bfgs_resto(const LbParams& P, LbState& st, LbResto& rs, const LbRestoDots& d, double eta, double* coef)
+{
+    const double sy = lb_resto_sy(d, eta), yy = lb_resto_yy(d, eta);
+    if (lb_skip(d.ss, sy, yy)) { ++st.skipped; return LB_PUSH_SKIPPED; }
+    LbState c = st; LbResto r = rs;
+    if (st.m == P.max_history) c.head = lb_slot(P, st, 1);
+    const int m = lb_resto_store(P, c, r, d, eta, 1.0 / std::sqrt(sy));
+    for (int j = 0; j < m; ++j) if (!(c.D[j] > 0.0)) { ++st.skipped; return LB_PUSH_SKIPPED; }
+    c.skipped = 0;
+    c.sigma = P.special ? -1.0 : lb_sigma(P.init, P.init_val, P.smin, P.smax, d.ss, sy, yy);
+    st = c; rs = r;
+    for (int e = 0; e < LBH_NCOEF_RESTO; ++e) coef[e] = 0.0;
+    double dd[LBH_MAX];
+    const bool ok = lb_coefficients(m, P.special ? rs.R : st.STS, st.L, LBH_MAX, st.D, P.special ? eta : st.sigma, dd, coef + LBH_MAX, coef + LBH_MAX + LBH_MAX * LBH_MAX, LBH_MAX);
+    for (int j = 0; j < m; ++j) { coef[j] = rs.dv[j]; coef[LBH_NCOEF + j] = rs.eta_col[j]; }
+    return ok ? LB_PUSH_STORED : LB_PUSH_NOT_PD;
+}
+
+// as lb_push_sr1: LB_PUSH_SKIPPED leaves st, rs untouched but for skipped + 1 and invalidates the backup; LB_PUSH_FAILED changes nothing; LB_PUSH_STORED:
+// (backup, rs_backup) = (st, rs) as they were
+inline int lb_push_sr1_resto(const LbParams& P, LbState& st, LbResto& rs, LbState& backup, LbResto& rs_backup, bool& backup_valid, const LbRestoDots& d, double eta)
+{
+    const double sy = lb_resto_sy(d, eta), yy = lb_resto_yy(d, eta);
+    if (!std::isfinite(d.ss) || !std::isfinite(sy) || !std::isfinite(yy)) { ++st.skipped; backup_valid = false; return LB_PUSH_SKIPPED; }
+    LbState c = st; LbResto r = rs;
+    const int m = lb_resto_store(P, c, r, d, eta, 0.0);
+    c.sigma = P.special ? -1.0 : lb_sr1_sigma(P.init, P.init_val, m, d.ss, sy, yy);
+    for (int e = 0; e < LBH_MAX * LBH_MAX; ++e) { c.Qs[e] = 0.0; if (e < LBH_MAX) c.E[e] = 0.0; }
+    const int rc = lb_sr1_coefficients(m, P.special ? r.R : c.STS, c.L, LBH_MAX, c.D, P.special ? eta : c.sigma, c.E, c.Qs, LBH_MAX, &c.nneg);
+    if (rc == LB_SR1_FAILED) return LB_PUSH_FAILED;
+    if (rc == LB_SR1_SKIP) { ++st.skipped; backup_valid = false; return LB_PUSH_SKIPPED; }
+    if (st.m == P.max_history) c.head = lb_slot(P, st, 1);
+    c.skipped = 0;
+    backup = st; rs_backup = rs; backup_valid = true; st = c; rs = r;
+    return LB_PUSH_STORED;
+}
+
+inline int lb_undo_resto(LbState& st, LbResto& rs, const LbState& backup, const LbResto& rs_backup, bool& backup_valid)
+{
+    if (!lb_undo(st, backup, backup_valid)) return 0;
+    rs = rs_backup;
     return 1;
 }
 

@@ -109,6 +109,12 @@ public:
     bool   lbfgs_define_sr1(int rows, int max_history, int init, double init_val);
     bool   lbfgs_undo(int* undone);
     void   lbfgs_sr1_info(int* type, int* nneg, int* can_undo, double* E) const;
+    // a restoration-phase history (lbfgs_host.h "the restoration phase"): type 0 BFGS / 1 SR1, special: B0 = eta DR; dr: host, `rows` positive entries.
+    // It is pushed with lbfgs_push_resto only (lbfgs_push refuses it, and the other way round); every other lbfgs_* call serves it unchanged.
+    // lbfgs_get what: 1 is Ypart; 10 G, 11 R, 12 eta_col, 13 dv, 14 DR.
+    bool   lbfgs_define_resto(int rows, int max_history, int type, int special, int init, double init_val, double sigma_min, double sigma_max, const double* dr);
+    bool   lbfgs_push_resto(const double* s, const double* ypart, double eta, bool device, int* outcome);
+    void   lbfgs_resto_info(int* resto, int* special, double* eta) const;
     long long factor_count() const;                  // bumped by every factorisation (the refactorisations of a delayed-pivot loop included) and every structure edit
     // communicator of a multi-GPU handle: with one set, factor()/solve_*() run the whole distributed sequence themselves
     bool   set_comm_rccl(const void* unique_id128);                                   // RCCL (dlopen'ed), ncclCommInitRank(nranks, id, rank)

@@ -1445,27 +1445,37 @@ public:
     // passed, so a skipped push moves nothing but the counter; k_lb_form_sr1 forms V (m - nneg columns) and U (nneg).  One stored push can be taken back
     // (lbfgs_undo: the reference's RestoreInternalDataBackup): the state before it is kept in lb.backup, and the ring has max_history + 1 slots, so the
     // pair that push evicted is still in its slot.
+    // par.resto, a restoration-phase history (lbfgs_define_resto / lbfgs_push_resto; lbfgs_host.h "the restoration phase"): the ring's Y holds Ypart, DR is
+    // one more device vector of the arena, lb.rs (LbResto: G, R, eta, eta_col, dv) travels with lb.st and is backed up with it.  The same two kernels
+    // and one synchronisation per push: k_lb_dots_resto gives 3 m + 6 dots, lb_push_bfgs_resto / lb_push_sr1_resto turn them and eta into the
+    // coefficients, k_lb_form_resto / k_lb_form_sr1_resto form the columns; the tail (lb_install, lr_shape) is the plain one.
     static_assert(LB_MAX == LBH_MAX, "the kernels and lbfgs_host.h agree on the number of pairs");
+    static_assert(LB_NOUT_RESTO == LBH_NDOT_RESTO, "the kernels and lbfgs_host.h agree on the dots of a resto push");
     struct History {                           // everything of the history but its arena (own_lb): lbfgs_clear() is own_lb.clear(); lb = {};
         bool defined = false; int rows = 0; double push_ms = 0;
         LbParams par; LbState st, backup; bool backup_valid = false;      // backup: the state before the last stored SR1 push, while that can be undone
         double *S = nullptr, *Y = nullptr, *sy = nullptr, *part = nullptr, *T = nullptr, *coef = nullptr, *h = nullptr, *hc = nullptr;
+        LbResto rs, rs_backup; double* DR = nullptr;                     // a resto history only (par.resto)
         int nslab() const { return std::max(1, (rows + LR_SLAB - 1) / LR_SLAB); }
     } lb;
     LbRing lb_ring(int m) const { LbRing R; R.m = m; for (int j = 0; j < LB_MAX; ++j) R.slot[j] = (unsigned char)lb_slot(lb.par, lb.st, j); return R; }      // (a defined history: slots >= 1)
-    void lb_forget() { lb.st = lb_fresh(lb.par); lb.backup_valid = false; }
+    void lb_forget() { lb.st = lb.par.resto ? lb_fresh_resto(lb.par) : lb_fresh(lb.par); lb.rs = {}; lb.backup_valid = false; }
     void lbfgs_clear() { own_lb.clear(); lb = {}; }
-    bool lbfgs_define(int rows, int max_history, int init, double init_val, double smin, double smax, int type) {
+    // dr != nullptr: a restoration-phase history with the host vector DR of `rows` entries (its dots and coefficients are wider: buffers sized on their own)
+    bool lbfgs_define(int rows, int max_history, int init, double init_val, double smin, double smax, int type, const double* dr = nullptr, int special = 0) {
         DeviceGuard guard(dev);
-        if (!ready) { if (err_.empty()) err_ = "lbfgs_define: solver not set up"; return false; }
-        if (multi) { err_ = "lbfgs_define: not supported on a multi-GPU handle"; return false; }
+        const char* who = dr ? "lbfgs_define_resto" : "lbfgs_define";
+        if (!ready) { if (err_.empty()) err_ = std::string(who) + ": solver not set up"; return false; }
+        if (multi) { err_ = std::string(who) + ": not supported on a multi-GPU handle"; return false; }
         HIPCHK(hipStreamSynchronize(stream));
         lbfgs_clear();
-        lb.rows = rows; lb.par = lb_params(type, max_history, init, init_val, smin, smax); lb_forget();
+        lb.rows = rows; lb.par = dr ? lb_params_resto(type, special, max_history, init, init_val, smin, smax) : lb_params(type, max_history, init, init_val, smin, smax); lb_forget();
         DeviceOwner& O = own_lb;
+        const size_t nout = dr ? LB_NOUT_RESTO : LB_NOUT, ncoef = dr ? LBH_NCOEF_RESTO : LBH_NCOEF;
         if (!O.zeroed(&lb.S, (size_t)rows * lb.par.slots) || !O.zeroed(&lb.Y, (size_t)rows * lb.par.slots) || !O.raw(&lb.sy, 2 * (size_t)rows) ||
-            !O.raw(&lb.part, (size_t)lb.nslab() * LB_NOUT) || !O.raw(&lb.T, LB_NOUT) || !O.raw(&lb.coef, LBH_NCOEF) ||
-            !O.pinned(&lb.h, LB_NOUT) || !O.pinned(&lb.hc, LBH_NCOEF)) { lbfgs_clear(); return false; }
+            !O.raw(&lb.part, (size_t)lb.nslab() * nout) || !O.raw(&lb.T, nout) || !O.raw(&lb.coef, ncoef) ||
+            !O.pinned(&lb.h, nout) || !O.pinned(&lb.hc, ncoef) || (dr && !O.raw(&lb.DR, (size_t)rows))) { lbfgs_clear(); return false; }
+        if (dr) HIPCHK(hipMemcpy(lb.DR, dr, (size_t)rows * sizeof(double), hipMemcpyHostToDevice));
         HIPCHK(hipDeviceSynchronize());            // (the zero fills ran on the default stream: device_owner.h)
         lb.defined = true;
         return true;
@@ -1484,6 +1494,11 @@ public:
     }
     // ds == nullptr: no new pair, every column comes from its slot (undo).  lr.V, lr.U must have the shape (lb.rows, m - nneg, nneg).
     void lb_launch_form_sr1(const double* ds, const double* dy) {
+        if (lb.par.resto) {
+            lb_with_kp(lb.st.m, [&](auto kp) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_form_sr1_resto<decltype(kp)::value>), dim3((lb.rows + 255) / 256), dim3(256), 0, stream, lb.S, lb.Y, (long long)lb.rows,
+                                                                  (const double*)lb.DR, ds, dy, lb.rows, lb_ring(lb.st.m), (const double*)lb.coef, lb.st.sigma, lb.rs.eta, lb.par.special, lb.st.nneg, lr.V, lr.U, (long long)lb.rows); });
+            return;
+        }
         lb_with_kp(lb.st.m, [&](auto kp) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_form_sr1<decltype(kp)::value>), dim3((lb.rows + 255) / 256), dim3(256), 0, stream, lb.S, lb.Y, (long long)lb.rows,
                                                               ds, dy, lb.rows, lb_ring(lb.st.m), (const double*)lb.coef, lb.st.sigma, lb.st.nneg, lr.V, lr.U, (long long)lb.rows); });
     }
@@ -1491,7 +1506,21 @@ public:
         lb_with_kp(lb.st.m, [&](auto kp) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_dots<decltype(kp)::value>), dim3(lb.nslab()), dim3(256), 0, stream, (const double*)lb.S, (const double*)lb.Y, (long long)lb.rows,
                                                               ds, dy, lb.rows, lb_ring(lb.st.m), lb.part); });
     }
+    void lb_launch_dots_resto(const double* ds, const double* dy) {
+        lb_with_kp(lb.st.m, [&](auto kp) {
+            constexpr int KP = decltype(kp)::value;
+            if (lb.par.special) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_dots_resto<KP, true>), dim3(lb.nslab()), dim3(256), 0, stream, (const double*)lb.S, (const double*)lb.Y, (long long)lb.rows,
+                                                   (const double*)lb.DR, ds, dy, lb.rows, lb_ring(lb.st.m), lb.part);
+            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_dots_resto<KP, false>), dim3(lb.nslab()), dim3(256), 0, stream, (const double*)lb.S, (const double*)lb.Y, (long long)lb.rows,
+                                    (const double*)lb.DR, ds, dy, lb.rows, lb_ring(lb.st.m), lb.part);
+        });
+    }
     void lb_launch_form(const double* ds, const double* dy) {
+        if (lb.par.resto) {
+            lb_with_kp(lb.st.m, [&](auto kp) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_form_resto<decltype(kp)::value>), dim3((lb.rows + 255) / 256), dim3(256), 0, stream, lb.S, lb.Y, (long long)lb.rows,
+                                                                  (const double*)lb.DR, ds, dy, lb.rows, lb_ring(lb.st.m), (const double*)lb.coef, lb.st.sigma, lb.rs.eta, lb.par.special, lr.V, lr.U, (long long)lb.rows); });
+            return;
+        }
         lb_with_kp(lb.st.m, [&](auto kp) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_form<decltype(kp)::value>), dim3((lb.rows + 255) / 256), dim3(256), 0, stream, lb.S, lb.Y, (long long)lb.rows,
                                                               ds, dy, lb.rows, lb_ring(lb.st.m), (const double*)lb.coef, lb.st.sigma, lr.V, lr.U, (long long)lb.rows); });
     }
@@ -1502,7 +1531,7 @@ public:
         const LbState& st = lb.st; const bool sr1 = lb.par.type == 1;
         if (!(sr1 ? lr_shape(lb.rows, st.m - st.nneg, st.nneg, lb.par.max_history) : lr_shape(lb.rows, st.m, st.m))) return false;
         if (sr1) std::copy(st.Qs, st.Qs + LB_MAX * LB_MAX, lb.hc);
-        HIPCHK(hipMemcpyAsync(lb.coef, lb.hc, (size_t)(sr1 ? LB_MAX * LB_MAX : LBH_NCOEF) * sizeof(double), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(lb.coef, lb.hc, (size_t)(sr1 ? LB_MAX * LB_MAX : lb.par.resto ? LBH_NCOEF_RESTO : LBH_NCOEF) * sizeof(double), hipMemcpyHostToDevice, stream));
         if (sr1) lb_launch_form_sr1(ds, dy); else lb_launch_form(ds, dy);
         HIPCHK(hipGetLastError());
         return true;
@@ -1516,7 +1545,7 @@ public:
         if (lb.par.type != 1) { err_ = "lbfgs_undo: only an SR1 history (lbfgs_define_sr1) can take a push back"; return false; }
         if (!lb.backup_valid) return true;
         HIPCHK(hipStreamSynchronize(stream));      // (the form kernel of the push reads lb.coef, a correction may read the columns about to be replaced)
-        lb_undo(lb.st, lb.backup, lb.backup_valid);
+        lb_undo_resto(lb.st, lb.rs, lb.backup, lb.rs_backup, lb.backup_valid);      // (a plain history: rs and its backup are both the fresh value)
         if (lb.st.m == 0) lowrank_clear();
         else {
             if (!lb_install(nullptr, nullptr)) return false;
@@ -1531,12 +1560,16 @@ public:
         if (E && sr1) for (int j = 0; j < lb.st.m; ++j) E[j] = lb.st.E[j];
     }
     // s, y: host vectors (device = false: uploaded to the staging pair) or device vectors of lb.rows.  *outcome: 0 stored and installed, 1 skipped (only the
-    // counter moved), 2 (BFGS) stored, M not positive definite
-    bool lbfgs_push(const double* s, const double* y, bool device, int* outcome) {
+    // counter moved), 2 (BFGS) stored, M not positive definite.  resto: the push of a restoration-phase history (y is ypart, eta > 0); a history takes
+    // only the pushes of its own kind.  Either way: the dots (2 m + 3, or 3 m + 6), ONE download and synchronisation, the transition, the same tail.
+    bool lbfgs_push(const double* s, const double* y, bool device, int* outcome, bool resto = false, double eta = 0.0) {
         DeviceGuard guard(dev);
         *outcome = 1;
-        if (!ready) { if (err_.empty()) err_ = "lbfgs_push: solver not set up"; return false; }
-        if (!lb.defined) { err_ = "lbfgs_push: lbfgs_define first"; return false; }
+        const std::string who = resto ? "lbfgs_push_resto" : "lbfgs_push";
+        if (!ready) { if (err_.empty()) err_ = who + ": solver not set up"; return false; }
+        if (!lb.defined) { err_ = who + (resto ? ": lbfgs_define_resto first" : ": lbfgs_define first"); return false; }
+        if (lb.par.resto && !resto) { err_ = "lbfgs_push: this is a restoration-phase history (lbfgs_define_resto): push with lbfgs_push_resto"; return false; }
+        if (!lb.par.resto && resto) { err_ = "lbfgs_push_resto: this is a plain history (lbfgs_define / lbfgs_define_sr1): push with lbfgs_push"; return false; }
         const auto t0 = std::chrono::steady_clock::now();
         const size_t vb = (size_t)lb.rows * sizeof(double);
         const double *ds = s, *dy = y;
@@ -1545,15 +1578,23 @@ public:
             HIPCHK(hipMemcpyAsync(lb.sy + lb.rows, y, vb, hipMemcpyHostToDevice, stream));
             ds = lb.sy; dy = lb.sy + lb.rows;
         }
-        const int m0 = lb.st.m, nout = 2 * m0 + 3;
-        lb_launch_dots(ds, dy);
+        const int m0 = lb.st.m, nout = resto ? 3 * m0 + 6 : 2 * m0 + 3;
+        if (resto) lb_launch_dots_resto(ds, dy); else lb_launch_dots(ds, dy);
         hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lb.part, lb.nslab(), 0LL, (long long)nout, nout, 1, (const double*)nullptr, lb.T);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(lb.h, lb.T, (size_t)nout * sizeof(double), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));      // the one synchronisation of a push (it also ends the form kernel of the push before: lb.hc is free)
-        const double *sS = lb.h, *sY = lb.h + m0, ss = lb.h[2 * m0], sy = lb.h[2 * m0 + 1], yy = lb.h[2 * m0 + 2];
-        const int r = lb.par.type == 1 ? lb_push_sr1(lb.par, lb.st, lb.backup, lb.backup_valid, sS, sY, ss, sy, yy) : lb_push_bfgs(lb.par, lb.st, sS, sY, ss, sy, yy, lb.hc);
-        if (r == LB_PUSH_FAILED) { err_ = "lbfgs_push: the eigen-solver of the SR1 split did not converge in " + std::to_string(LBH_JACOBI_SWEEPS) + " sweeps"; return false; }
+        const bool sr1 = lb.par.type == 1;
+        int r;
+        if (resto) {
+            const double* q = lb.h + 3 * m0;
+            const LbRestoDots d{lb.h, lb.h + m0, lb.h + 2 * m0, q[0], q[1], q[2], q[3], q[4], q[5]};
+            r = sr1 ? lb_push_sr1_resto(lb.par, lb.st, lb.rs, lb.backup, lb.rs_backup, lb.backup_valid, d, eta) : lb_push_bfgs_resto(lb.par, lb.st, lb.rs, d, eta, lb.hc);
+        } else {
+            const double *sS = lb.h, *sY = lb.h + m0, ss = lb.h[2 * m0], sy = lb.h[2 * m0 + 1], yy = lb.h[2 * m0 + 2];
+            r = sr1 ? lb_push_sr1(lb.par, lb.st, lb.backup, lb.backup_valid, sS, sY, ss, sy, yy) : lb_push_bfgs(lb.par, lb.st, sS, sY, ss, sy, yy, lb.hc);
+        }
+        if (r == LB_PUSH_FAILED) { err_ = who + ": the eigen-solver of the SR1 split did not converge in " + std::to_string(LBH_JACOBI_SWEEPS) + " sweeps"; return false; }
         if (r == LB_PUSH_STORED) {                 // (nothing is in flight behind the synchronisation above)
             if (!lb_install(ds, dy)) return false;
         } else if (r == LB_PUSH_NOT_PD) {
@@ -1567,15 +1608,32 @@ public:
         lb.push_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         return true;
     }
+    void lbfgs_resto_info(int* resto, int* special, double* eta) const {
+        const bool on = lb.defined && lb.par.resto;
+        if (resto) *resto = on ? 1 : 0; if (special) *special = on ? lb.par.special : 0; if (eta) *eta = on ? lb.rs.eta : 0.0;
+    }
     void lbfgs_info(int* rows, int* max_history, int* memory, double* sigma, int* skipped, double* push_ms) const {
         if (rows) *rows = lb.defined ? lb.rows : 0; if (max_history) *max_history = lb.defined ? lb.par.max_history : 0; if (memory) *memory = lb.defined ? lb.st.m : 0;
         if (sigma) *sigma = lb.defined ? lb.st.sigma : 0.0; if (skipped) *skipped = lb.defined ? lb.st.skipped : 0; if (push_ms) *push_ms = lb.defined ? lb.push_ms : 0.0;
     }
     // what: 0 S, 1 Y (rows x memory, oldest first), 2 V, 3 U (the installed columns of the low-rank update), 4 D, 5 L, 6 S^T S (memory x memory); column-major, no padding
+    // a resto history: 1 is Ypart, 4 and 5 are D, L at the eta of the last stored push; 10 G = S^T Ypart (diagonal and strictly lower part), 11 R = S^T (DR o S)
+    // (zero unless special) (memory x memory), 12 eta_col, 13 dv (memory), 14 DR (rows)
     bool lbfgs_get(int what, double* out, long long capacity) {
         DeviceGuard guard(dev);
         if (!lb.defined) { err_ = "lbfgs_get: lbfgs_define first"; return false; }
         const int m = lb.st.m;
+        if (what >= 10) {
+            if (!lb.par.resto) { err_ = "lbfgs_get: what 10..14 are arrays of a restoration-phase history (lbfgs_define_resto)"; return false; }
+            const long long need = what <= 11 ? (long long)m * m : what <= 13 ? m : lb.rows;
+            if (capacity < need) { err_ = "lbfgs_get: capacity is below the " + std::to_string(need) + " doubles of this array"; return false; }
+            if (what == 14) { HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipMemcpy(out, lb.DR, (size_t)lb.rows * sizeof(double), hipMemcpyDeviceToHost)); return true; }
+            for (int j = 0; j < m; ++j) {
+                if (what == 12) out[j] = lb.rs.eta_col[j]; else if (what == 13) out[j] = lb.rs.dv[j];
+                else for (int i = 0; i < m; ++i) out[i + (size_t)j * m] = what == 11 ? lb.rs.R[i + j * LB_MAX] : i == j ? lb.rs.GD[j] : i > j ? lb.rs.GL[i + j * LB_MAX] : 0.0;
+            }
+            return true;
+        }
         const long long need = what <= 1 ? (long long)lb.rows * m : what == 2 ? (lr.set ? (long long)lr.rows * lr.nv : 0) : what == 3 ? (lr.set ? (long long)lr.rows * lr.nu : 0)
                              : what == 4 ? m : (long long)m * m;
         if (capacity < need) { err_ = "lbfgs_get: capacity is below the " + std::to_string(need) + " doubles of this array"; return false; }
@@ -1897,6 +1955,9 @@ void Numeric::lowrank_info(int* rows, int* nv, int* nu, int* current, double* up
 long long Numeric::factor_count() const { return p_->factor_count; }
 bool Numeric::lbfgs_define(int rows, int max_history, int init, double init_val, double sigma_min, double sigma_max) { return p_->lbfgs_define(rows, max_history, init, init_val, sigma_min, sigma_max, 0); }
 bool Numeric::lbfgs_define_sr1(int rows, int max_history, int init, double init_val) { return p_->lbfgs_define(rows, max_history, init, init_val, 1e-8, 1e8, 1); }
+bool Numeric::lbfgs_define_resto(int rows, int max_history, int type, int special, int init, double init_val, double sigma_min, double sigma_max, const double* dr) { return p_->lbfgs_define(rows, max_history, init, init_val, sigma_min, sigma_max, type, dr, special); }
+bool Numeric::lbfgs_push_resto(const double* s, const double* ypart, double eta, bool device, int* outcome) { return p_->lbfgs_push(s, ypart, device, outcome, true, eta); }
+void Numeric::lbfgs_resto_info(int* resto, int* special, double* eta) const { p_->lbfgs_resto_info(resto, special, eta); }
 bool Numeric::lbfgs_undo(int* undone) { return p_->lbfgs_undo(undone); }
 void Numeric::lbfgs_sr1_info(int* type, int* nneg, int* can_undo, double* E) const { p_->lbfgs_sr1_info(type, nneg, can_undo, E); }
 bool Numeric::lbfgs_push(const double* s, const double* y, bool device, int* outcome) { return p_->lbfgs_push(s, y, device, outcome); }

@@ -76,6 +76,7 @@ ABI_SYMBOLS = [
     "mi355x_kkt_lowrank_set", "mi355x_kkt_lowrank_update", "mi355x_kkt_lowrank_solve", "mi355x_kkt_lowrank_solve_device2", "mi355x_kkt_lowrank_clear", "mi355x_kkt_lowrank_info",
     "mi355x_kkt_lbfgs_define", "mi355x_kkt_lbfgs_push", "mi355x_kkt_lbfgs_push_device", "mi355x_kkt_lbfgs_reset", "mi355x_kkt_lbfgs_clear", "mi355x_kkt_lbfgs_info", "mi355x_kkt_lbfgs_get", "mi355x_kkt_lbfgs_coefficients",
     "mi355x_kkt_lbfgs_define_sr1", "mi355x_kkt_lbfgs_undo", "mi355x_kkt_lbfgs_sr1_info", "mi355x_kkt_lbfgs_sr1_coefficients",
+    "mi355x_kkt_lbfgs_define_resto", "mi355x_kkt_lbfgs_push_resto", "mi355x_kkt_lbfgs_push_resto_device", "mi355x_kkt_lbfgs_resto_info",
 ]
 LOWRANK_MAX = 32
 LBFGS_MAX = 32
@@ -164,6 +165,10 @@ def load_library():
     lib.mi355x_kkt_lbfgs_undo.argtypes = [vp, ip]
     lib.mi355x_kkt_lbfgs_sr1_info.argtypes = [vp, ip, ip, ip, vp, C.c_int]
     lib.mi355x_kkt_lbfgs_sr1_coefficients.argtypes = [C.c_int, vp, vp, vp, C.c_double, vp, vp, ip]
+    lib.mi355x_kkt_lbfgs_define_resto.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp]
+    lib.mi355x_kkt_lbfgs_push_resto.argtypes = [vp, vp, vp, C.c_double, ip]
+    lib.mi355x_kkt_lbfgs_push_resto_device.argtypes = [vp, vp, vp, C.c_double, ip]
+    lib.mi355x_kkt_lbfgs_resto_info.argtypes = [vp, ip, ip, dp]
     lib.mi355x_kkt_set_comm_rccl.argtypes = [vp, vp]
     lib.mi355x_kkt_comm_shm_id.argtypes = [vp, C.c_int]
     lib.mi355x_kkt_set_comm_shm.argtypes = [vp, vp]
@@ -461,14 +466,15 @@ class KKTSolver:
         return {"rows": r.value, "max_history": mh.value, "memory": m.value, "sigma": sg.value, "skipped_in_a_row": sk.value, "push_ms": ms.value}
 
     def lbfgs_get(self, what) -> np.ndarray:
-        """what: "S" | "Y" (rows x memory, oldest first), "V" | "U" (the installed columns), "D" (memory), "L" | "STS" (memory x memory), or 0..6"""
-        w = {"S": 0, "Y": 1, "V": 2, "U": 3, "D": 4, "L": 5, "STS": 6}.get(what, what)
+        """what: "S" | "Y" (rows x memory, oldest first), "V" | "U" (the installed columns), "D" (memory), "L" | "STS" (memory x memory), or 0..6;
+        a restoration-phase history: "Y" | "Ypart" is Ypart, and "G" | "R" (memory x memory), "eta_col" | "dv" (memory), "DR" (rows), or 10..14"""
+        w = {"S": 0, "Y": 1, "Ypart": 1, "V": 2, "U": 3, "D": 4, "L": 5, "STS": 6, "G": 10, "R": 11, "eta_col": 12, "dv": 13, "DR": 14}.get(what, what)
         I = self.lbfgs_info(); m = I["memory"]
         if w in (2, 3):
             lr = self.lowrank_info()
             shape = (lr["rows"], lr["nv"] if w == 2 else lr["nu"])
         else:
-            shape = (I["rows"], m) if w in (0, 1) else (m,) if w == 4 else (m, m)
+            shape = (I["rows"], m) if w in (0, 1) else (m,) if w in (4, 12, 13) else (I["rows"],) if w == 14 else (m, m)
         out = np.zeros(shape, dtype=np.float64, order="F")
         if self.lib.mi355x_kkt_lbfgs_get(self._h, int(w), out.ctypes.data if out.size else None, out.size) != 0:
             raise KKTError("lbfgs_get: " + self.last_error())
@@ -496,6 +502,43 @@ class KKTSolver:
             raise KKTError("lbfgs_sr1_info: " + self.last_error())
         m = self.lbfgs_info()["memory"] if t.value == LBFGS_SR1 else 0
         return {"type": t.value, "nneg": nn.value, "can_undo": bool(cu.value), "E": E[:m].copy()}
+
+    # --- the restoration phase: Ypart in the history, eta per push, the fixed scaling DR; B0 = sigma I, or eta DR when special ---
+    def lbfgs_define_resto(self, rows, dr, max_history=6, type=LBFGS_BFGS, special=False, init="scalar1", init_val=1.0, sigma_min=1e-8, sigma_max=1e8):
+        """dr: host vector of `rows` positive entries; type LBFGS_BFGS | LBFGS_SR1; special: B0 = eta dr (sigma stays -1)"""
+        rows = int(rows)
+        dr = None if dr is None else np.ascontiguousarray(dr, dtype=np.float64)
+        if dr is not None and dr.shape != (rows,):
+            raise KKTError("lbfgs_define_resto: dr must be a vector of `rows`")
+        st = self.lib.mi355x_kkt_lbfgs_define_resto(self._h, rows, int(max_history), int(type), int(special), LBFGS_INIT.get(init, init), init_val, sigma_min, sigma_max,
+                                                    None if dr is None else dr.ctypes.data)
+        if st != 0:
+            raise KKTError("lbfgs_define_resto: " + self.last_error())
+
+    def lbfgs_push_resto(self, s: np.ndarray, ypart: np.ndarray, eta: float) -> int:
+        """host vectors of `rows`, eta > 0; -> outcome as lbfgs_push"""
+        rows = self.lbfgs_info()["rows"]
+        s = np.ascontiguousarray(s, dtype=np.float64); ypart = np.ascontiguousarray(ypart, dtype=np.float64)
+        if rows and (s.shape != (rows,) or ypart.shape != (rows,)):
+            raise KKTError("lbfgs_push_resto: s and ypart must be vectors of `rows`")
+        oc = C.c_int(0)
+        if self.lib.mi355x_kkt_lbfgs_push_resto(self._h, s.ctypes.data, ypart.ctypes.data, float(eta), C.byref(oc)) != 0:
+            raise KKTError("lbfgs_push_resto: " + self.last_error())
+        return oc.value
+
+    def lbfgs_push_resto_device(self, ds_ptr: int, dypart_ptr: int, eta: float) -> int:
+        """device vectors of `rows`, complete before the call"""
+        oc = C.c_int(0)
+        if self.lib.mi355x_kkt_lbfgs_push_resto_device(self._h, C.c_void_p(ds_ptr), C.c_void_p(dypart_ptr), float(eta), C.byref(oc)) != 0:
+            raise KKTError("lbfgs_push_resto_device: " + self.last_error())
+        return oc.value
+
+    def lbfgs_resto_info(self) -> dict:
+        """resto: a restoration-phase history is defined; special; eta of its last stored push (-1 before the first)"""
+        r, sp, eta = C.c_int(0), C.c_int(0), C.c_double(0.0)
+        if self.lib.mi355x_kkt_lbfgs_resto_info(self._h, C.byref(r), C.byref(sp), C.byref(eta)) != 0:
+            raise KKTError("lbfgs_resto_info: " + self.last_error())
+        return {"resto": bool(r.value), "special": bool(sp.value), "eta": eta.value}
 
     # --- multi-GPU communicator (include/mi355x_kkt.h): after one of these, multi_solve / factor_device / solve_device* of a
     #     handle created with nranks > 1 run the distributed sequence inside the library ---
