@@ -254,7 +254,9 @@ int  mi355x_kkt_lowrank_info(mi355x_kkt_handle h, int* rows, int* nv, int* nu, i
  *   0  pair stored, V and U formed and INSTALLED as the handle's low-rank update, exactly as _lowrank_set(rows, memory, V, rows, memory, U, rows)
  *      would: the update is not current; the caller factors with sigma on the x diagonal and calls _lowrank_update
  *   1  skipped, nothing changed (an update that was current stays current)
- *   2  pair stored and sigma updated; M was not positive definite, the installed columns are unchanged
+ *   2  pair stored and sigma updated; M was not positive definite, the installed columns are unchanged.  The reference marks such a call "Ws",
+ *      counts it as a skip (:489-495, :687-691) and keeps the W it had: the OLD sigma with the old columns.  skipped_in_a_row is 0 after it and
+ *      _lbfgs_info reports the new sigma: a caller that follows the reference counts the skip itself and keeps the diagonal of its last outcome 0.
  * A push allocates no device memory while the installed shape (rows, nv, nu) stays the same (a full history).  The history survives
  * refactorisations and delayed-pivot structure edits; _lowrank_set / _lowrank_clear replace / remove the installed columns and leave it alone.
  *   _lbfgs_reset  forgets the pairs, sigma = init_val, removes the installed update;   _lbfgs_clear  undefines: frees the history
@@ -294,6 +296,10 @@ int  mi355x_kkt_lbfgs_coefficients(int m, const double* sts, const double* L, co
  *                 them (bitwise what that earlier push installed; memory 0: the update is removed) and are not current; skipped_in_a_row is its
  *                 value before the undone push plus one; *undone (may be NULL) = 1.  One level: after a skipped push, an undo, _reset, _define*,
  *                 _clear there is nothing to undo and the call succeeds with *undone = 0, nothing changed.
+ *                 The reference's own counter (lm_skipped_iter_, read by its limited_memory_max_skipping reset) is NOT part of what it restores: a
+ *                 call that undoes (info_regu_x > 0, mark "Wb") adds one to it whether the push that follows is stored or skipped (:674-691), so
+ *                 two such calls in a row reset the history (recorded: tests/golden/qn_sr1_517.qnrec, records 8-10).  skipped_in_a_row does not
+ *                 follow that rule -- a stored push zeroes it --: the reset policy of an SR1 caller counts on its own (tests/test_qn_oracle.py Caller).
  *   _lbfgs_sr1_info  outputs may be NULL; type 0 BFGS / 1 SR1; nneg, E (the `memory` eigenvalues of the installed split, ascending; FATAL when
  *                 `capacity` is below memory) and can_undo are 0 / untouched for a BFGS history
  *   _lbfgs_sr1_coefficients  stand-alone, HOST, no handle, no GPU: E (m), Qs (m x m, column-major) and nneg from S^T S, L, D and sigma; SUCCESS,

@@ -16,7 +16,12 @@
 // (--set linear_solver ma97 --set hsllib .../libmi355x_kkt.so = route B2; --set linear_solver mi355x with the patched
 // library oracle/_ref/libipopt_ref_mi355x.so = route B1').
 //
+// --record-qn FILE (with --set hessian_approximation limited-memory) wraps the reference's HessianUpdater and its low-rank AugSystemSolver
+// in decorators that store every quasi-Newton update (the pair, W afterwards) and every solve; --max-records K caps the updates,
+// --max-aug-records K the solves.  Fixtures tests/golden/*.qnrec, reader oracle/qn_oracle.py.
+//
 // usage: ref_driver <problem> <N> [--solver pardisomkl|mi355x|mi355x-aug|mi355x-pd|stock] [--record file] [--max-records K] [--skip-records K]
+//                   [--record-pd file] [--record-qn file] [--max-aug-records K]
 //                   [--set name value]... [--optfile ipopt.opt] [--reoptimize] [--quiet]
 //   --reoptimize: after the first solve, set warm_start_same_structure=yes and call ReOptimizeNLP (second DRIVER_SUMMARY line)
 //   --then-bounds lo hi: (LukVl problems) after the first solve, optimise a SECOND instance of the problem with constraint bounds [lo, hi]
@@ -58,6 +63,10 @@
 #include "IpIpoptCalculatedQuantities.hpp"
 #include "IpIpoptData.hpp"
 #include "IpIpoptNLP.hpp"
+#include "IpHessianUpdater.hpp"
+#include "IpAugSystemSolver.hpp"
+#include "IpLowRankUpdateSymMatrix.hpp"
+#include "IpMultiVectorMatrix.hpp"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -265,11 +274,202 @@ private:
    int nrec_, max_records_;
 };
 
+// ------------------------------------------------------------------------------------------
+// recording decorators of the quasi-Newton path (`hessian_approximation limited-memory`): what the reference's HessianUpdater is given and
+// what it leaves in IpData().W(), and what its low-rank AugSystemSolver is given and returns.  Golden fixtures for oracle/qn_oracle.py.
+//   file: "QNREC1\n", int hdr[8] = {update_type (0 bfgs, 1 sr1), max_history, initialization (0 scalar1 .. 4 constant), max_skipping, nx,
+//         P_LowRank is null, 0, 0}, double {init_val, init_val_min, init_val_max}; then records, each led by its tag:
+//   update: int hdr[8] = {1, nx, has_pair, nv, nu, W was replaced, length of the info string, iter_count}, double {Amax(s), info_regu_x};
+//         double s[nx], y[nx] when has_pair; double diag[nx], V[nv][nx], U[nu][nx]; the characters the call appended to info_string
+//   solve:  int hdr[20] = {2, nx, ns, nc, nd, nv, nu, |D_x|, |D_s|, |D_c|, |D_d|, nnz J_c, nnz J_d, check_NegEVals, numberOfNegEVals, status,
+//         NumberOfNegEVals() after the call (-1: no inertia), iter_count, 0, 0}, double {W_factor, delta_x, delta_s, delta_c, delta_d};
+//         double diag[nx], V, U of W; D_x, D_s, D_c, D_d (absent: length 0); int (irow, jcol) 1-based + double values of J_c, J_d;
+//         double rhs (4 blocks), sol (4 blocks)
+// The header is written by the first UpdateHessian call; a solve before it is not recorded.
+// ------------------------------------------------------------------------------------------
+class QnFile: public ReferencedObject
+{
+public:
+   QnFile(const std::string& file, int max_upd, int max_aug)
+      : f(fopen(file.c_str(), "wb")), header(false), nupd(0), naug(0), max_upd(max_upd), max_aug(max_aug)
+   {
+      if( f ) fwrite("QNREC1\n", 1, 7, f);
+   }
+   ~QnFile() { if( f ) fclose(f); }
+   void Vec(const Vector* v)
+   {
+      if( !v || v->Dim() <= 0 ) return;
+      std::vector<Number> a(v->Dim());
+      TripletHelper::FillValuesFromVector(v->Dim(), *v, a.data());
+      fwrite(a.data(), sizeof(Number), a.size(), f);
+   }
+   void Cols(const MultiVectorMatrix* M) { if( M ) for( Index j = 0; j < M->NCols(); ++j ) Vec(GetRawPtr(M->GetVector(j))); }
+   void Trip(Index n, const Matrix& M)
+   {
+      if( n <= 0 ) return;
+      std::vector<Index> r(n), c(n); std::vector<Number> v(n);
+      TripletHelper::FillRowCol(n, M, r.data(), c.data());
+      TripletHelper::FillValues(n, M, v.data());
+      fwrite(r.data(), sizeof(Index), n, f); fwrite(c.data(), sizeof(Index), n, f); fwrite(v.data(), sizeof(Number), n, f);
+   }
+   static int Dim(const Vector* v) { return v ? (int) v->Dim() : 0; }
+   static int NCols(const MultiVectorMatrix* M) { return M ? (int) M->NCols() : 0; }
+   FILE* f;
+   bool header;
+   int nupd, naug, max_upd, max_aug;
+};
+
+class RecordingHessianUpdater: public HessianUpdater
+{
+public:
+   RecordingHessianUpdater(SmartPtr<HessianUpdater> inner, SmartPtr<QnFile> out)
+      : inner_(inner), out_(out) { }
+   bool InitializeImpl(const OptionsList& options, const std::string& prefix)
+   {
+      Index e;
+      options.GetEnumValue("limited_memory_update_type", e, prefix); opt_[0] = e;
+      options.GetIntegerValue("limited_memory_max_history", e, prefix); opt_[1] = e;
+      options.GetEnumValue("limited_memory_initialization", e, prefix); opt_[2] = e;
+      options.GetIntegerValue("limited_memory_max_skipping", e, prefix); opt_[3] = e;
+      options.GetNumericValue("limited_memory_init_val", val_[0], prefix);
+      options.GetNumericValue("limited_memory_init_val_min", val_[1], prefix);
+      options.GetNumericValue("limited_memory_init_val_max", val_[2], prefix);
+      last_x_ = NULL; last_grad_f_ = NULL; last_jac_c_ = NULL; last_jac_d_ = NULL;
+      return inner_->Initialize(Jnlst(), IpNLP(), IpData(), IpCq(), options, prefix);
+   }
+   void UpdateHessian()
+   {
+      const bool rec = out_->f && (out_->max_upd < 0 || out_->nupd < out_->max_upd);
+      SmartPtr<const Vector> x = IpData().curr()->x(), g = IpCq().curr_grad_f();
+      SmartPtr<const Matrix> Jc = IpCq().curr_jac_c(), Jd = IpCq().curr_jac_d();
+      SmartPtr<Vector> s, y;
+      if( rec && IsValid(last_x_) )
+      {  // the pair the updater is about to form from its own kept iterate (same operations, same order)
+         s = x->MakeNew();
+         s->AddTwoVectors(1., *x, -1., *last_x_, 0.);
+         y = x->MakeNew();
+         y->AddTwoVectors(1., *g, -1., *last_grad_f_, 0.);
+         y->AddTwoVectors(1., *IpCq().curr_jac_cT_times_curr_y_c(), 1., *IpCq().curr_jac_dT_times_curr_y_d(), 1.);
+         last_jac_c_->TransMultVector(-1., *IpData().curr()->y_c(), 1., *y);
+         last_jac_d_->TransMultVector(-1., *IpData().curr()->y_d(), 1., *y);
+      }
+      const Number regu_x = IpData().info_regu_x();
+      const std::string info_before = IpData().info_string();
+      SmartPtr<const SymMatrix> W_before = IpData().W();      // (held across the call: a replaced W cannot reuse its address)
+      inner_->UpdateHessian();
+      last_x_ = x; last_grad_f_ = g; last_jac_c_ = Jc; last_jac_d_ = Jd;
+      if( !rec ) return;
+      SmartPtr<const SymMatrix> Wsym = IpData().W();
+      const LowRankUpdateSymMatrix* W = dynamic_cast<const LowRankUpdateSymMatrix*>(GetRawPtr(Wsym));
+      if( !W ) return;
+      const int nx = x->Dim();
+      if( !out_->header )
+      {
+         int hdr[8] = {opt_[0], opt_[1], opt_[2], opt_[3], nx, IsNull(W->P_LowRank()) ? 1 : 0, 0, 0};
+         fwrite(hdr, sizeof(int), 8, out_->f);
+         fwrite(val_, sizeof(double), 3, out_->f);
+         out_->header = true;
+      }
+      std::string info = IpData().info_string();
+      info = info.size() >= info_before.size() ? info.substr(info_before.size()) : info;
+      SmartPtr<const MultiVectorMatrix> V = W->GetV(), U = W->GetU();
+      int hdr[8] = {1, nx, IsValid(s) ? 1 : 0, QnFile::NCols(GetRawPtr(V)), QnFile::NCols(GetRawPtr(U)),
+                    GetRawPtr(Wsym) != GetRawPtr(W_before) ? 1 : 0, (int) info.size(), (int) IpData().iter_count()};
+      fwrite(hdr, sizeof(int), 8, out_->f);
+      double sc[2] = {IsValid(s) ? s->Amax() : 0., regu_x};
+      fwrite(sc, sizeof(double), 2, out_->f);
+      out_->Vec(GetRawPtr(s)); out_->Vec(GetRawPtr(y));
+      out_->Vec(GetRawPtr(W->GetDiag())); out_->Cols(GetRawPtr(V)); out_->Cols(GetRawPtr(U));
+      fwrite(info.data(), 1, info.size(), out_->f);
+      ++out_->nupd;
+   }
+private:
+   SmartPtr<HessianUpdater> inner_;
+   SmartPtr<QnFile> out_;
+   int opt_[4];
+   double val_[3];
+   SmartPtr<const Vector> last_x_, last_grad_f_;
+   SmartPtr<const Matrix> last_jac_c_, last_jac_d_;
+};
+
+class RecordingAugSolver: public AugSystemSolver
+{
+public:
+   RecordingAugSolver(SmartPtr<AugSystemSolver> inner, SmartPtr<QnFile> out)
+      : inner_(inner), out_(out) { }
+   bool InitializeImpl(const OptionsList& options, const std::string& prefix)
+   {
+      return inner_->Initialize(Jnlst(), IpNLP(), IpData(), IpCq(), options, prefix);
+   }
+   ESymSolverStatus Solve(const SymMatrix* W, Number W_factor, const Vector* D_x, Number delta_x, const Vector* D_s, Number delta_s,
+                          const Matrix* J_c, const Vector* D_c, Number delta_c, const Matrix* J_d, const Vector* D_d, Number delta_d,
+                          const Vector& rhs_x, const Vector& rhs_s, const Vector& rhs_c, const Vector& rhs_d,
+                          Vector& sol_x, Vector& sol_s, Vector& sol_c, Vector& sol_d, bool check_NegEVals, Index numberOfNegEVals)
+   {
+      const ESymSolverStatus st = inner_->Solve(W, W_factor, D_x, delta_x, D_s, delta_s, J_c, D_c, delta_c, J_d, D_d, delta_d,
+                                                rhs_x, rhs_s, rhs_c, rhs_d, sol_x, sol_s, sol_c, sol_d, check_NegEVals, numberOfNegEVals);
+      const LowRankUpdateSymMatrix* LW = dynamic_cast<const LowRankUpdateSymMatrix*>(W);
+      if( !LW || !J_c || !J_d || !out_->f || !out_->header || !(out_->max_aug < 0 || out_->naug < out_->max_aug) ) return st;
+      SmartPtr<const MultiVectorMatrix> V = LW->GetV(), U = LW->GetU();
+      const Index nJc = TripletHelper::GetNumberEntries(*J_c), nJd = TripletHelper::GetNumberEntries(*J_d);
+      int hdr[20] = {2, (int) rhs_x.Dim(), (int) rhs_s.Dim(), (int) rhs_c.Dim(), (int) rhs_d.Dim(), QnFile::NCols(GetRawPtr(V)), QnFile::NCols(GetRawPtr(U)),
+                     QnFile::Dim(D_x), QnFile::Dim(D_s), QnFile::Dim(D_c), QnFile::Dim(D_d), (int) nJc, (int) nJd, check_NegEVals ? 1 : 0,
+                     (int) numberOfNegEVals, (int) st, inner_->ProvidesInertia() ? (int) inner_->NumberOfNegEVals() : -1, (int) IpData().iter_count(), 0, 0};
+      fwrite(hdr, sizeof(int), 20, out_->f);
+      double sc[5] = {W_factor, delta_x, delta_s, delta_c, delta_d};
+      fwrite(sc, sizeof(double), 5, out_->f);
+      out_->Vec(GetRawPtr(LW->GetDiag())); out_->Cols(GetRawPtr(V)); out_->Cols(GetRawPtr(U));
+      out_->Vec(D_x); out_->Vec(D_s); out_->Vec(D_c); out_->Vec(D_d);
+      out_->Trip(nJc, *J_c); out_->Trip(nJd, *J_d);
+      out_->Vec(&rhs_x); out_->Vec(&rhs_s); out_->Vec(&rhs_c); out_->Vec(&rhs_d);
+      if( st == SYMSOLVER_SUCCESS ) { out_->Vec(&sol_x); out_->Vec(&sol_s); out_->Vec(&sol_c); out_->Vec(&sol_d); }
+      else
+      {  // (nothing was returned: the solution vectors may never have been written)
+         std::vector<Number> z(hdr[1] + hdr[2] + hdr[3] + hdr[4], 0.);
+         fwrite(z.data(), sizeof(Number), z.size(), out_->f);
+      }
+      ++out_->naug;
+      return st;
+   }
+   ESymSolverStatus MultiSolve(const SymMatrix* W, Number W_factor, const Vector* D_x, Number delta_x, const Vector* D_s, Number delta_s,
+                               const Matrix* J_c, const Vector* D_c, Number delta_c, const Matrix* J_d, const Vector* D_d, Number delta_d,
+                               std::vector<SmartPtr<const Vector> >& rhs_xV, std::vector<SmartPtr<const Vector> >& rhs_sV,
+                               std::vector<SmartPtr<const Vector> >& rhs_cV, std::vector<SmartPtr<const Vector> >& rhs_dV,
+                               std::vector<SmartPtr<Vector> >& sol_xV, std::vector<SmartPtr<Vector> >& sol_sV,
+                               std::vector<SmartPtr<Vector> >& sol_cV, std::vector<SmartPtr<Vector> >& sol_dV, bool check_NegEVals, Index numberOfNegEVals)
+   {
+      return inner_->MultiSolve(W, W_factor, D_x, delta_x, D_s, delta_s, J_c, D_c, delta_c, J_d, D_d, delta_d, rhs_xV, rhs_sV, rhs_cV, rhs_dV,
+                                sol_xV, sol_sV, sol_cV, sol_dV, check_NegEVals, numberOfNegEVals);
+   }
+   Index NumberOfNegEVals() const { return inner_->NumberOfNegEVals(); }
+   bool ProvidesInertia() const { return inner_->ProvidesInertia(); }
+   bool IncreaseQuality() { return inner_->IncreaseQuality(); }
+private:
+   SmartPtr<AugSystemSolver> inner_;
+   SmartPtr<QnFile> out_;
+};
+
 class DriverAlgBuilder: public AlgorithmBuilder
 {
 public:
-   DriverAlgBuilder(const std::string& solver, const std::string& record, int max_records, const std::string& record_pd = "", int skip_records = 0)
-      : solver_(solver), record_(record), record_pd_(record_pd), max_records_(max_records), skip_records_(skip_records) { }
+   DriverAlgBuilder(const std::string& solver, const std::string& record, int max_records, const std::string& record_pd = "", int skip_records = 0,
+                    const std::string& record_qn = "", int max_aug_records = -1)
+      : solver_(solver), record_(record), record_pd_(record_pd), max_records_(max_records), skip_records_(skip_records)
+   {
+      if( !record_qn.empty() ) qn_ = new QnFile(record_qn, max_records, max_aug_records);
+   }
+   virtual SmartPtr<HessianUpdater> BuildHessianUpdater(const Journalist& jnlst, const OptionsList& options, const std::string& prefix)
+   {
+      SmartPtr<HessianUpdater> up = AlgorithmBuilder::BuildHessianUpdater(jnlst, options, prefix);
+      if( IsValid(qn_) ) up = new RecordingHessianUpdater(up, qn_);
+      return up;
+   }
+   virtual SmartPtr<AugSystemSolver> AugSystemSolverFactory(const Journalist& jnlst, const OptionsList& options, const std::string& prefix)
+   {
+      SmartPtr<AugSystemSolver> aug = AlgorithmBuilder::AugSystemSolverFactory(jnlst, options, prefix);      // the reference's LowRankAugSystemSolver
+      if( IsValid(qn_) ) aug = new RecordingAugSolver(aug, qn_);
+      return aug;
+   }
    virtual SmartPtr<PDSystemSolver> PDSystemSolverFactory(const Journalist& jnlst, const OptionsList& options, const std::string& prefix)
    {
       SmartPtr<PDSystemSolver> pd = AlgorithmBuilder::PDSystemSolverFactory(jnlst, options, prefix);      // the reference's PDFullSpaceSolver
@@ -295,17 +495,18 @@ public:
 private:
    std::string solver_, record_, record_pd_;
    int max_records_, skip_records_;
+   SmartPtr<QnFile> qn_;
 };
 
 static double wall(const TimedTask& t) { return t.TotalWallclockTime(); }
 
 int main(int argc, char** argv)
 {
-   if( argc < 3 ) { fprintf(stderr, "usage: %s <problem> <N> [--solver s] [--record f] [--max-records k] [--set k v]... [--quiet]\n", argv[0]); return 2; }
+   if( argc < 3 ) { fprintf(stderr, "usage: %s <problem> <N> [--solver s] [--record f] [--record-pd f] [--record-qn f] [--max-records k] [--max-aug-records k] [--skip-records k] [--set k v]... [--quiet]\n", argv[0]); return 2; }
    std::string problem = argv[1];
    int N = atoi(argv[2]);
-   std::string solver = "pardisomkl", record, record_pd;
-   int max_records = -1, skip_records = 0;
+   std::string solver = "pardisomkl", record, record_pd, record_qn;
+   int max_records = -1, skip_records = 0, max_aug_records = -1;
    bool quiet = false, reopt = false, then_bounds = false;
    double tb_lo = 0., tb_hi = 0.;
    std::string optfile;
@@ -316,7 +517,9 @@ int main(int argc, char** argv)
       if( a == "--solver" && i + 1 < argc ) solver = argv[++i];
       else if( a == "--record" && i + 1 < argc ) record = argv[++i];
       else if( a == "--record-pd" && i + 1 < argc ) record_pd = argv[++i];
+      else if( a == "--record-qn" && i + 1 < argc ) record_qn = argv[++i];
       else if( a == "--max-records" && i + 1 < argc ) max_records = atoi(argv[++i]);
+      else if( a == "--max-aug-records" && i + 1 < argc ) max_aug_records = atoi(argv[++i]);
       else if( a == "--skip-records" && i + 1 < argc ) skip_records = atoi(argv[++i]);
       else if( a == "--set" && i + 2 < argc ) { sets.push_back(std::make_pair(std::string(argv[i + 1]), std::string(argv[i + 2]))); i += 2; }
       else if( a == "--quiet" ) quiet = true;
@@ -403,7 +606,7 @@ int main(int argc, char** argv)
       builder = MakeMi355xPDSystemAlgorithmBuilder();
    }
 #endif
-   else builder = new DriverAlgBuilder(solver, record, max_records, record_pd, skip_records);
+   else builder = new DriverAlgBuilder(solver, record, max_records, record_pd, skip_records, record_qn, max_aug_records);
    auto t0 = std::chrono::steady_clock::now();
    ApplicationReturnStatus status = app->OptimizeNLP(nlp, builder);
    double total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

@@ -7,6 +7,8 @@
 #   *.kktrec   every call that crossed the SparseSymLinearSolverInterface boundary during the run
 #              (structure, values, rhs, returned status / inertia / solution); reader: oracle/kkt_oracle.py
 #   *.iters    the iteration table of the reference run (iter objective inf_pr inf_du lg(mu) lg(rg) ls)
+#   *.qnrec    the quasi-Newton path of runs with `hessian_approximation limited-memory`: every update of the reference's limited-memory
+#              updater and the solves of its low-rank augmented-system solver (end of this file); reader: oracle/qn_oracle.py
 #   *.summary  DRIVER_SUMMARY json (iteration count, objective, reference timers on the build container)
 set -e
 cd "$(dirname "$0")"
@@ -78,3 +80,23 @@ for k in 3 4 5 6 7 8; do run mbndry${k}_100 MBndryCntrl$k 100 norec; done
 for k in 2 3 3a 4 5 6a 4a 5a 6; do run mdist${k}_100 MDistCntrl$k 100 norec; done
 run mbndry3d27_12 MBndryCntrl_3D_27 12 norec; run mbndry3d27bt_12 MBndryCntrl_3D_27BT 12 norec; run mbndry3dsin_12 MBndryCntrl_3Dsin 12 norec
 run mpara5_2_3_40 MPara5_2_3 40 norec
+# the quasi-Newton path (`hessian_approximation limited-memory`): every UpdateHessian call of the reference's LimMemQuasiNewtonUpdater (the pair it formed, the
+# W = sigma I + V V^T - U U^T it left) and the Solve calls of its LowRankAugSystemSolver; reader: oracle/qn_oracle.py, tests/test_qn_oracle.py says what the
+# files must hold.  N = the `rows` at which the device kernels change regime (tests/test_gpu_lbfgs.py); --max-records caps the updates, --max-aug-records the
+# solves, both so that no file passes 1 MB.  One MKL thread: the recordings are reproduced byte for byte.
+export MKL_NUM_THREADS=1 OMP_NUM_THREADS=1
+qn() {  # name problem N options...
+  name=$1; p=$2; n=$3; shift 3
+  $D/ref_driver $p $n --set hessian_approximation limited-memory --record-qn $name.qnrec --quiet "$@" > /dev/null
+  echo "$name: $(wc -c < $name.qnrec) bytes"
+}
+# BFGS, defaults (scalar1, history 6): all 15 updates (shifts from the 7th stored pair on), the first 12 solves (iterations 0-5: nv = nu = 0 .. 5)
+qn qn_bfgs_180 LukVlE1 180 --max-aug-records 12
+# BFGS on inequalities (slacks: D_s, J_d), scalar2, history 12, sigma clipped from above at 1000 (mark Wp on 7 records): 11 updates, 6 solves (the 6th with nv = nu = 1)
+qn qn_bfgs_517 LukVlI1 517 --set limited_memory_initialization scalar2 --set limited_memory_max_history 12 --set limited_memory_init_val_max 1000. --max-records 11 --max-aug-records 6
+# BFGS, two 1024-row slabs, history 2: 9 updates (a curvature skip, mark Ws, with the memory full; shifts), 1 solve
+qn qn_bfgs_1728 LukVlE1 1728 --set limited_memory_max_history 2 --max-records 9 --max-aug-records 1
+# SR1: all 22 updates (undo Wb x 3, eigenvalue skips Ws x 2, reset Wr, nv and nu > 0 together), 12 solves (5 of them answered "wrong inertia": not used as fixtures of a solve)
+qn qn_sr1_180 LukVlE1 180 --set limited_memory_update_type sr1 --max-aug-records 12
+# SR1 on inequalities, scalar4: 12 updates (undo on three calls, two of them in a row -> reset), 2 solves
+qn qn_sr1_517 LukVlI1 517 --set limited_memory_update_type sr1 --set limited_memory_initialization scalar4 --max-records 12 --max-aug-records 2
