@@ -214,7 +214,8 @@ int  mi355x_kkt_solve_device2(mi355x_kkt_handle h, int nrhs, const double* d_b, 
  * W = B0 + V V^T - U U^T (IpLowRankAugSystemSolver.cpp): factor K with W = diag(B0), solve for the columns of the update and factor two small
  * dense matrices (UpdateFactorization, :299-396), correct every later solve by Sherman-Morrison (Solve, :195-228) -- with the tall-skinny
  * algebra on the device instead of host MultiVectorMatrix products (HighRankUpdateTranspose :319,:367,:383; AddRightMultMatrix :370).
- * V is rows x nv, U is rows x nu; they act on the FIRST `rows` indices of the caller's numbering (Ipopt's x block; zero rows below):
+ * V is rows x nv, U is rows x nu; they act on the first `rows` indices of the caller's numbering (Ipopt's x block; zero rows below) or, with a
+ * row map (_lowrank_rowmap below), on the `rows` indices it names: K~ = K + P (V V^T - U U^T) P^T.
  *   update:  Z1 = K^-1 V,  M1 = I + sym(V^T Z1),  W1 = K^-1 U,  C = M1^-1 (Z1^T U),  Z2 = W1 - Z1 C,  M2 = I - sym(U^T Z2),  sym(G) = (G + G^T) / 2
  *   solve:   x0 = K^-1 b,  x1 = x0 - Z1 M1^-1 (V^T x0),  x = x1 + Z2 M2^-1 (U^T x1)      (the reference's Z^T b taken from the running solution: in place)
  * M1 and M2 positive definite <=> K~ has K's inertia; a Cholesky failure is the reference's "wrong inertia" answer (ComputeCholeskyFactor :323, :387 -> SYMSOLVER_WRONG_INERTIA :330, :392).
@@ -225,7 +226,7 @@ int  mi355x_kkt_solve_device2(mi355x_kkt_handle h, int nrhs, const double* d_b, 
  *                    that _lowrank_update completed on the factorisation now in the handle (every factor / refactor / factor_assembled ends it); FATAL otherwise
  *   _lowrank_clear   removes the update;  _lowrank_info   what is set, whether it is current, host ms of the last _lowrank_update (outputs may be NULL)
  * While an update is set, _pd_solve_once applies the correction to the 4-block solution (it needs a current update) and _pd_residual adds
- * V (V^T res_x) - U (U^T res_x) to the x rows, so the W segment of the assembly carries B0 only; both need rows <= n_x.
+ * V (V^T res_x) - U (U^T res_x) to the x rows, so the W segment of the assembly carries B0 only; both need rows <= n_x (under a row map: idx[rows-1] < n_x).
  * Arguments are checked before the device is touched; single-GPU handles only (nranks > 1: FATAL). */
 #define MI355X_KKT_LOWRANK_MAX 32                       /* columns of V, and of U */
 int  mi355x_kkt_lowrank_set(mi355x_kkt_handle h, int rows, int nv, const double* V, int ldv, int nu, const double* U, int ldu);
@@ -234,12 +235,33 @@ int  mi355x_kkt_lowrank_solve(mi355x_kkt_handle h, int nrhs, double* rhs_inout, 
 int  mi355x_kkt_lowrank_solve_device2(mi355x_kkt_handle h, int nrhs, const double* d_b, int ldb, double* d_x, int ldx);
 int  mi355x_kkt_lowrank_clear(mi355x_kkt_handle h);
 int  mi355x_kkt_lowrank_info(mi355x_kkt_handle h, int* rows, int* nv, int* nu, int* current, double* update_ms);
+/* The row map: the reference's P_LowRank.  `hessian_approximation_space nonlinear-variables` (the default, IpOrigIpoptNLP.cpp:127,258) gives a TNLP that
+ * declares its nonlinear variables W = P (B0 + V V^T - U U^T) P^T with P an ExpansionMatrix onto an ascending index subset of x; the updater works in
+ * the reduced space (IpLimMemQuasiNewtonUpdater.cpp:169-193, :313-325) and LowRankAugSystemSolver expands every column through P before its solves
+ * (IpLowRankAugSystemSolver.cpp:274-290, :449-457).  Here: row i of V, U, S, Y, DR, s, y is the caller's index idx[i] -- 0-based (whatever index_base
+ * says of the matrix), STRICTLY ascending, 0 <= idx[i] < n: ExpansionMatrix::ExpandedPosIndices.  rows = 0 or idx = NULL removes the map.
+ *   _lowrank_rowmap      idx: HOST memory, `rows` entries, copied (once to the device, into an arena of its own).  Every argument is validated on the
+ *                        host before the device is touched -- that check is why no kernel can index out of range -- FATAL names `rows`, `idx`, the
+ *                        first position that is not ascending or the first value out of range.  The map is a property of the handle, stated in the
+ *                        caller's numbering: it survives factorisations, delayed-pivot structure edits, _lowrank_clear, _lbfgs_reset and _lbfgs_clear
+ *                        (a new _analyse ends it).  Setting or removing it while a low-rank update is set or a history is defined: FATAL (clear first).
+ *   while a map is set   _lowrank_set, _lbfgs_define, _lbfgs_define_sr1, _lbfgs_define_resto take `rows` equal to the map's (FATAL otherwise); V, U, s,
+ *                        y, ypart, dr and _lbfgs_get 0..3, 14 stay `rows` long, in the reduced space; _lowrank_info, _lbfgs_info, _lbfgs_get are unchanged.
+ *   _lowrank_rowmap_get  *rows (0: no map) and the indices; FATAL when `capacity` (entries) is below rows; outputs may be NULL
+ *   _lowrank_rowmap_check  stand-alone, HOST, no handle, no GPU: the validation itself for a system of n rows, and -- len >= 0 -- of a full-space
+ *                        vector length against the map (len > idx[rows-1]); SUCCESS, or FATAL with the reason in msg (capacity bytes, may be NULL)
+ * What stays with the caller, as the reference does it: B0 on the diagonal -- with ReducedDiag, sigma on the MAPPED diagonal entries and 0 elsewhere
+ * (IpLowRankAugSystemSolver.cpp:286-290); for a restoration history, DR gathered through the map once, at _lbfgs_define_resto (:190-192).
+ * With no map set every call runs exactly the code it ran before maps existed.  Single-GPU handles only. */
+int  mi355x_kkt_lowrank_rowmap(mi355x_kkt_handle h, int rows, const int32_t* idx);
+int  mi355x_kkt_lowrank_rowmap_get(mi355x_kkt_handle h, int* rows, int32_t* idx, int64_t capacity);
+int  mi355x_kkt_lowrank_rowmap_check(int64_t n, int rows, const int32_t* idx, int64_t len, char* msg, int64_t capacity);
 
 /* ---- limited-memory BFGS: the (s, y) history on the device, V and U formed there -------------------------------------------------------------
  * What the reference's LimMemQuasiNewtonUpdater does for `hessian_approximation limited-memory` with the BFGS update "with skipping" (its default),
  * IpLimMemQuasiNewtonUpdater.cpp -- with the tall products on the device instead of host MultiVectorMatrix products over the whole history: an
  * accepted step moves TWO vectors (s, y) to the device, V and U never exist in host memory.  History S = [s_1 .. s_k], Y = [y_1 .. y_k], oldest
- * first, k <= max_history, `rows` entries each (the first `rows` indices of the caller's numbering, as for _lowrank_set).
+ * first, k <= max_history, `rows` entries each (the first `rows` indices of the caller's numbering, or those of the row map, as for _lowrank_set).
  *   skip    (CheckSkippingBFGS :985-1019)  s^T y <= sqrt(eps) |s|_2 |y|_2: nothing changes.  A non-finite s^T s, s^T y or y^T y is a skip too (a
  *           stated deviation: the reference never sees one).
  *   store   (UpdateInternalData :769-818)  append the pair, or drop the oldest when the history is full; D = diag(s_i^T y_i), L (strictly lower,
@@ -345,6 +367,13 @@ int  mi355x_kkt_lbfgs_define_resto(mi355x_kkt_handle h, int rows, int max_histor
 int  mi355x_kkt_lbfgs_push_resto(mi355x_kkt_handle h, const double* s, const double* ypart, double eta, int* outcome);
 int  mi355x_kkt_lbfgs_push_resto_device(mi355x_kkt_handle h, const double* d_s, const double* d_ypart, double eta, int* outcome);
 int  mi355x_kkt_lbfgs_resto_info(mi355x_kkt_handle h, int* resto, int* special, double* eta);
+/* Pushing FULL-SPACE vectors under a row map (the reference's P_LM^T s_full, P_LM^T y_full, IpLimMemQuasiNewtonUpdater.cpp:323-324): sx, yx (ypartx) are
+ * x-block vectors of `len` entries, len > idx[rows-1]; HOST memory, or -- on_device != 0 -- device memory, complete before the call and free again when
+ * it returns.  One launch gathers s[i] = sx[idx[i]], y[i] = yx[idx[i]] into the history's staging pair; then the call IS _lbfgs_push / _lbfgs_push_resto
+ * of that pair: the same outcomes, the one download, the one synchronisation, the same bits.  No map set, len too small: FATAL, answered before the
+ * device is touched.  _lbfgs_push* themselves keep taking reduced vectors of `rows` entries, with or without a map. */
+int  mi355x_kkt_lbfgs_push_mapped(mi355x_kkt_handle h, const double* sx, const double* yx, int64_t len, int on_device, int* outcome);
+int  mi355x_kkt_lbfgs_push_resto_mapped(mi355x_kkt_handle h, const double* sx, const double* ypartx, int64_t len, int on_device, double eta, int* outcome);
 
 int  mi355x_kkt_set_pivtol(mi355x_kkt_handle h, double u);
 int  mi355x_kkt_set_pivtolmax(mi355x_kkt_handle h, double umax);

@@ -8,6 +8,7 @@
 #include "comm_shm.h"
 #include "env_knobs.h"
 #include "lbfgs_host.h"      // the small algebra of an L-BFGS push: mi355x_kkt_lbfgs_coefficients is this header alone
+#include "lowrank_host.h"    // the validation of a row map: mi355x_kkt_lowrank_rowmap_check is this header alone
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -403,12 +404,16 @@ template <class F> static int lowrank_call(mi355x_kkt_handle h, const char* name
     catch (...) { h->err = std::string(name) + ": unexpected exception"; return MI355X_KKT_FATAL; }
 }
 }
+// while a row map is set, every update and history has its rows (host state of the engine: answers without a device)
+static bool rowmap_rows_differ(mi355x_kkt_handle h, int rows) { int mr = 0; if (h->num) h->num->lowrank_rowmap_info(&mr, nullptr); return mr > 0 && rows != mr; }
+static std::string rowmap_rows_text(mi355x_kkt_handle h, int rows) { int mr = 0; if (h->num) h->num->lowrank_rowmap_info(&mr, nullptr); return "rows = " + std::to_string(rows) + " must equal the " + std::to_string(mr) + " rows of the row map while one is set (lowrank_rowmap)"; }
 int mi355x_kkt_lowrank_set(mi355x_kkt_handle h, int rows, int nv, const double* V, int ldv, int nu, const double* U, int ldu)
 {
     if (!h) return MI355X_KKT_FATAL;
     const char* name = "lowrank_set";
     if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
     if (rows < 0 || rows > h->sym.n) LR_FAIL("rows must be in [0, n]");
+    if (rowmap_rows_differ(h, rows)) LR_FAIL(rowmap_rows_text(h, rows));
     if (nv < 0 || nv > MI355X_KKT_LOWRANK_MAX) LR_FAIL("nv must be in [0, 32]");
     if (nu < 0 || nu > MI355X_KKT_LOWRANK_MAX) LR_FAIL("nu must be in [0, 32]");
     if (nv > 0 && ldv < rows) LR_FAIL("ldv must be >= rows");
@@ -457,12 +462,73 @@ int mi355x_kkt_lowrank_info(mi355x_kkt_handle h, int* rows, int* nv, int* nu, in
     if (rows) *rows = 0; if (nv) *nv = 0; if (nu) *nu = 0; if (current) *current = 0; if (update_ms) *update_ms = 0.0;
     return lowrank_call(h, "lowrank_info", false, [&] { h->num->lowrank_info(rows, nv, nu, current, update_ms); return true; });
 }
+// ---- the row map of the low-rank update (P_LowRank, ExpansionMatrix::ExpandedPosIndices): validated by lowrank_host.h before anything else happens ----
+int mi355x_kkt_lowrank_rowmap(mi355x_kkt_handle h, int rows, const int32_t* idx)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "lowrank_rowmap";
+    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
+    std::string why;
+    if (!lr_rowmap_check(h->sym.n, rows, idx, why)) LR_FAIL(why);
+    return lowrank_call(h, name, false, [&] { return h->num->lowrank_rowmap(rows, idx); });
+}
+int mi355x_kkt_lowrank_rowmap_get(mi355x_kkt_handle h, int* rows, int32_t* idx, int64_t capacity)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "lowrank_rowmap_get";
+    if (rows) *rows = 0;
+    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
+    if (capacity < 0) LR_FAIL("capacity must be >= 0");
+    if (h->opts.nranks > 1) LR_FAIL("not supported on a multi-GPU handle");
+    int mr = 0;
+    if (h->num) h->num->lowrank_rowmap_info(&mr, nullptr);
+    if (idx && capacity < mr) LR_FAIL("capacity is below the " + std::to_string(mr) + " indices of the map");
+    if (rows) *rows = mr;
+    if (idx && mr > 0) h->num->lowrank_rowmap_copy(idx);
+    return MI355X_KKT_SUCCESS;
+}
+// host only, no handle, no device: the validation itself (lowrank_host.h); len >= 0 also checks a full-space vector length against the map
+int mi355x_kkt_lowrank_rowmap_check(int64_t n, int rows, const int32_t* idx, int64_t len, char* msg, int64_t capacity)
+{
+    std::string why;
+    bool ok = n >= 0;
+    if (!ok) why = "n must be >= 0";
+    try {
+        ok = ok && lr_rowmap_check((long long)n, rows, idx, why);
+        if (ok && len >= 0) ok = lr_rowmap_len_check((long long)len, rows > 0 && idx ? (long long)idx[rows - 1] : -1, why);
+    } catch (...) { ok = false; why = "unexpected exception"; }
+    if (msg && capacity > 0) { const size_t k = std::min<size_t>(why.size(), (size_t)capacity - 1); std::memcpy(msg, why.data(), k); msg[k] = 0; }
+    return ok ? MI355X_KKT_SUCCESS : MI355X_KKT_FATAL;
+}
+// a push of full-space vectors: pointers, eta, the multi-GPU refusal, then the map and len (host state), then the device
+static int lbfgs_push_mapped_any(mi355x_kkt_handle h, const char* name, const double* sx, const double* yx, int64_t len, int on_device, bool resto, double eta, int* outcome)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    if (outcome) *outcome = 1;
+    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
+    if (!sx) LR_FAIL("sx is null");
+    if (!yx) LR_FAIL(resto ? "ypartx is null" : "yx is null");
+    if (resto && (!(eta > 0.0) || !std::isfinite(eta))) LR_FAIL("eta must be positive and finite");
+    if (h->opts.nranks > 1) LR_FAIL("not supported on a multi-GPU handle");
+    long long last = -1; std::string why;
+    if (h->num) h->num->lowrank_rowmap_info(nullptr, &last);
+    if (!lr_rowmap_len_check((long long)len, last, why)) LR_FAIL(why);
+    int oc = 1;
+    const int st = lowrank_call(h, name, false, [&] { return resto ? h->num->lbfgs_push_resto_mapped(sx, yx, (long long)len, eta, on_device != 0, &oc) : h->num->lbfgs_push_mapped(sx, yx, (long long)len, on_device != 0, &oc); });
+    if (st == MI355X_KKT_SUCCESS && outcome) *outcome = oc;
+    return st;
+}
+int mi355x_kkt_lbfgs_push_mapped(mi355x_kkt_handle h, const double* sx, const double* yx, int64_t len, int on_device, int* outcome)
+{ return lbfgs_push_mapped_any(h, "lbfgs_push_mapped", sx, yx, len, on_device, false, 0.0, outcome); }
+int mi355x_kkt_lbfgs_push_resto_mapped(mi355x_kkt_handle h, const double* sx, const double* ypartx, int64_t len, int on_device, double eta, int* outcome)
+{ return lbfgs_push_mapped_any(h, "lbfgs_push_resto_mapped", sx, ypartx, len, on_device, true, eta, outcome); }
 // ---- limited-memory BFGS on the device (IpLimMemQuasiNewtonUpdater.cpp): the (s, y) history, V and U formed there and installed as the low-rank update ----
 // The same order as above: every argument, then the multi-GPU refusal, then the device.
 static int lbfgs_define_args(mi355x_kkt_handle h, const char* name, int rows, int max_history, int init, double init_val)      // (lbfgs_define and lbfgs_define_sr1)
 {
     if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
     if (rows < 1 || rows > h->sym.n) LR_FAIL("rows must be in [1, n]");
+    if (rowmap_rows_differ(h, rows)) LR_FAIL(rowmap_rows_text(h, rows));
     if (max_history < 1 || max_history > MI355X_KKT_LBFGS_MAX) LR_FAIL("max_history must be in [1, 32]");
     if (init < 0 || init > 4) LR_FAIL("init must be in [0, 4] (scalar1..4, constant)");
     if (!(init_val > 0.0) || !std::isfinite(init_val)) LR_FAIL("init_val must be positive and finite");

@@ -1,7 +1,9 @@
 // kernels_lowrank.hip.inc -- part of numeric.hip (one translation unit; included there, inside namespace mi355x): the tall-skinny algebra of a
-// low-rank-updated solve,  K~ = K + V V^T - U U^T  with V (rows x nv), U (rows x nu) on the first `rows` indices of the caller's numbering
+// low-rank-updated solve,  K~ = K + V V^T - U U^T  with V (rows x nv), U (rows x nu) on `rows` indices of the caller's numbering (the first `rows`, or those of the row map)
 // (reference IpLowRankAugSystemSolver.cpp:299-396 UpdateFactorization, :195-228 Solve; the in-place form is restated in DESIGN.md).
 // ================================================================================================
+// Under a row map (lowrank_rowmap; P_LowRank, :274-290, :449-457) row i of V and U is the caller's index idx[i]: the n-row operands are then gathered
+// through the map (k_lr_gram<GA, GB>, k_lr_apply<true>), the columns scattered into their n-row form (k_lr_scatter), a full-space pair gathered (k_lr_gather2).
 // Three kernels, all of them streaming: at p = q = 32 a Gram does 4 flop per byte, so HBM is the ruler and fp64 MFMA buys nothing.
 //   k_lr_gram     partial p x q blocks of A^T B, one per SLAB of LR_SLAB rows (the split depends on `rows` alone)
 //   k_lr_reduce   ONE workgroup: sums the partials of all slabs in a fixed order; in solve mode applies an uploaded Cholesky factor to every column
@@ -19,10 +21,15 @@
 // row lanes per output element: the largest power of two with nout * L <= 256, at most LR_CHUNK (nout > 128: one lane, several outputs per thread)
 __host__ __device__ __forceinline__ int lr_lanes(int nout) { int L = 1; while (2 * L * nout <= 256 && 2 * L <= LR_CHUNK) L *= 2; return L; }
 
-// part[(blockIdx.y * gridDim.x + slab) * p * q + i + j * p] = sum over the slab's rows r of A[r + i lda] * B[r + (blockIdx.y q + j) ldb]
-__global__ __launch_bounds__(256) void k_lr_gram(const double* __restrict__ A, long long lda, const double* __restrict__ B, long long ldb, int rows, int p, int q, double* __restrict__ part)
+// part[(blockIdx.y * gridDim.x + slab) * p * q + i + j * p] = sum over the slab's rows r of A[ra(r) + i lda] * B[rb(r) + (blockIdx.y q + j) ldb]
+// GA / GB: that side has n rows and is read through the row map, ra(r) = idx[r] (ExpansionMatrix::ExpandedPosIndices: strictly ascending, validated on the
+// host by lr_rowmap_check, so a gathered chunk touches no more cache lines than its span); the other side has `rows` rows, ra(r) = r.  The chunk's 64
+// indices are staged in LDS once, not once per column.  Every summation order is that of the unmapped kernel; <false, false> IS the unmapped kernel.
+template <bool GA, bool GB>
+__global__ __launch_bounds__(256) void k_lr_gram(const double* __restrict__ A, long long lda, const double* __restrict__ B, long long ldb, int rows, int p, int q, double* __restrict__ part, const int* __restrict__ idx)
 {
     __shared__ double sa[LR_MAX * LR_LDC], sb[LR_MAX * LR_LDC], red[256];
+    __shared__ int si[(GA || GB) ? LR_CHUNK : 1];
     const int t = threadIdx.x, nout = p * q;
     const int L = lr_lanes(nout), l = t % L, og = t / L, ostep = 256 / L;
     const long long r0 = (long long)blockIdx.x * LR_SLAB;
@@ -31,8 +38,12 @@ __global__ __launch_bounds__(256) void k_lr_gram(const double* __restrict__ A, l
     for (int ch = 0; ch < LR_SLAB / LR_CHUNK; ++ch) {
         const long long rc = r0 + (long long)ch * LR_CHUNK;
         if (rc >= rows) break;                                        // (uniform: the whole workgroup leaves together)
-        for (int e = t; e < LR_CHUNK * p; e += 256) { const int r = e % LR_CHUNK, c = e / LR_CHUNK; sa[c * LR_LDC + r] = (rc + r < rows) ? A[rc + r + c * lda] : 0.0; }
-        for (int e = t; e < LR_CHUNK * q; e += 256) { const int r = e % LR_CHUNK, c = e / LR_CHUNK; sb[c * LR_LDC + r] = (rc + r < rows) ? B[rc + r + c * ldb] : 0.0; }
+        if constexpr (GA || GB) {
+            if (t < LR_CHUNK) si[t] = (rc + t < rows) ? idx[rc + t] : 0;
+            __syncthreads();
+        }
+        for (int e = t; e < LR_CHUNK * p; e += 256) { const int r = e % LR_CHUNK, c = e / LR_CHUNK; sa[c * LR_LDC + r] = (rc + r < rows) ? A[(GA ? (long long)si[r] : rc + r) + c * lda] : 0.0; }
+        for (int e = t; e < LR_CHUNK * q; e += 256) { const int r = e % LR_CHUNK, c = e / LR_CHUNK; sb[c * LR_LDC + r] = (rc + r < rows) ? B[(GB ? (long long)si[r] : rc + r) + c * ldb] : 0.0; }
         __syncthreads();
 #pragma unroll
         for (int ps = 0; ps < 4; ++ps) {
@@ -88,14 +99,17 @@ __global__ __launch_bounds__(256) void k_lr_reduce(const double* __restrict__ pa
     for (int e = t; e < p * ncol; e += 256) out[e] = g[e];
 }
 
-// X[i + j ldx] += sigma * sum_k Z[i + k ldz] T[k + j p], k ascending (one thread per row: Z is read once, coalesced along the rows)
-__global__ __launch_bounds__(256) void k_lr_apply(double* __restrict__ X, long long ldx, const double* __restrict__ Z, long long ldz, const double* __restrict__ T, long long n, int p, int q, double sigma)
+// X[x(i) + j ldx] += sigma * sum_k Z[i + k ldz] T[k + j p], k ascending (one thread per row: Z is read once, coalesced along the rows)
+// MX (lr_residual under a row map only): Z has n = `rows` rows and X is an x-block vector, x(i) = idx[i]; otherwise x(i) = i
+template <bool MX>
+__global__ __launch_bounds__(256) void k_lr_apply(double* __restrict__ X, long long ldx, const double* __restrict__ Z, long long ldz, const double* __restrict__ T, long long n, int p, int q, double sigma, const int* __restrict__ idx)
 {
     __shared__ double ts[LR_MAX * LR_MAX];
     for (int e = threadIdx.x; e < LR_MAX * q; e += 256) { const int k = e % LR_MAX, j = e / LR_MAX; ts[e] = k < p ? T[k + j * p] : 0.0; }
     __syncthreads();
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
+    const long long xi = MX ? (long long)idx[i] : i;
     double z[LR_MAX];
 #pragma unroll
     for (int k = 0; k < LR_MAX; ++k) z[k] = k < p ? Z[i + k * ldz] : 0.0;
@@ -103,6 +117,23 @@ __global__ __launch_bounds__(256) void k_lr_apply(double* __restrict__ X, long l
         double s = 0.0;
 #pragma unroll
         for (int k = 0; k < LR_MAX; ++k) s = fma(z[k], ts[k + LR_MAX * j], s);
-        X[i + j * ldx] += sigma * s;
+        X[xi + j * ldx] += sigma * s;
     }
+}
+
+// Z[idx[i] + k n] = A[i + k rows] for the `rows` mapped rows of column k = blockIdx.y (lr_pad under a row map, behind the zero fill of Z: P V, P U)
+__global__ __launch_bounds__(256) void k_lr_scatter(double* __restrict__ Z, long long n, const double* __restrict__ A, int rows, const int* __restrict__ idx)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows) return;
+    Z[idx[i] + (long long)blockIdx.y * n] = A[i + (long long)blockIdx.y * rows];
+}
+
+// s[i] = sx[idx[i]], y[i] = yx[idx[i]]: the reduced pair of a mapped push, P^T s_full and P^T y_full (IpLimMemQuasiNewtonUpdater.cpp:323-324), one launch
+__global__ __launch_bounds__(256) void k_lr_gather2(const double* __restrict__ sx, const double* __restrict__ yx, int rows, const int* __restrict__ idx, double* __restrict__ s, double* __restrict__ y)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows) return;
+    const long long x = idx[i];
+    s[i] = sx[x]; y[i] = yx[x];
 }

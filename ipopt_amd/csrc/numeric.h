@@ -85,7 +85,7 @@ public:
     bool   pd_solve_once(int rhs, int res, double alpha, double beta);
     bool   pd_residual(int rhs, int res, int resid, const double* deltas4, double* norms3);
     // low-rank update K + V V^T - U U^T of the factored system (IpLowRankAugSystemSolver.cpp): V (rows x nv), U (rows x nu), host, column-major, on the
-    // first `rows` indices of the caller's numbering; kept on the device across refactorisations and structure edits.  lowrank_update runs after a
+    // first `rows` indices of the caller's numbering (or, with a row map, on the indices it names); kept on the device across refactorisations and structure edits.  lowrank_update runs after a
     // factorisation (*which: 0 in force, 1 / 2 = M1 / M2 not positive definite); the solves refuse an update that is not current (factor_count).
     // While one is set, pd_solve_once corrects the 4-block solution and pd_residual adds V (V^T res_x) - U (U^T res_x) to the x rows.
     bool   lowrank_set(int rows, int nv, const double* V, int ldv, int nu, const double* U, int ldu);
@@ -94,6 +94,15 @@ public:
     bool   lowrank_solve_device2(int nrhs, const double* db, int ldb, double* dx, int ldx);
     bool   lowrank_clear();
     void   lowrank_info(int* rows, int* nv, int* nu, int* current, double* update_ms) const;
+    // the row map (P_LowRank, ExpansionMatrix::ExpandedPosIndices): row i of V, U, S, Y, DR is the caller's index idx[i] (0-based, strictly ascending, < n;
+    // lowrank_host.h lr_rowmap_check).  rows = 0 / idx = nullptr removes it.  Refused while an update is set or a history defined; while it is set every
+    // lowrank_set / lbfgs_define* takes its `rows`.  _info: rows (0: none) and the largest index (-1: none), host state, answers without a device.
+    bool   lowrank_rowmap(int rows, const int32_t* idx);
+    void   lowrank_rowmap_info(int* rows, long long* last) const;
+    void   lowrank_rowmap_copy(int32_t* idx) const;          // `rows` entries (the caller checks the capacity)
+    // a push of x-block vectors of `len` > idx[rows-1] entries: gathered through the map on the device, then the plain push (:323-324)
+    bool   lbfgs_push_mapped(const double* sx, const double* yx, long long len, bool device, int* outcome);
+    bool   lbfgs_push_resto_mapped(const double* sx, const double* ypartx, long long len, double eta, bool device, int* outcome);
     // limited-memory BFGS (IpLimMemQuasiNewtonUpdater.cpp, BFGS "with skipping"): the (s, y) history of `rows` entries per vector stays on the device;
     // a push (host or device vectors) answers *outcome = 0 stored, V and U formed on the device and installed as the low-rank update above (not current),
     // 1 skipped, 2 stored but M not positive definite: the installed columns stay.  lbfgs_get what: 0 S, 1 Y, 2 V, 3 U, 4 D, 5 L, 6 S^T S.

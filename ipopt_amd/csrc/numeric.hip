@@ -102,6 +102,7 @@ public:
     DeviceOwner own_pd{err_};          // until pd_define or release(false): the primal-dual workspace
     DeviceOwner own_lr{err_};          // until lowrank_set / lowrank_clear or release(false): the low-rank update (caller's numbering: survives a restructure, like own_pd)
     DeviceOwner own_lb{err_};          // until lbfgs_define / lbfgs_clear or release(false): the L-BFGS history (caller's numbering, like own_lr)
+    DeviceOwner own_map{err_};         // until lowrank_rowmap or release(false): the row map of the low-rank update (caller's numbering; lowrank_clear / lbfgs_clear leave it alone)
     DevView V{};
     int* d_stats = nullptr;
     double* d_rhs = nullptr; size_t d_rhs_cap = 0;
@@ -464,6 +465,7 @@ public:
             own_pd.clear(); pd_ready = false;
             lowrank_clear();
             lbfgs_clear();
+            own_map.clear(); rmap = {};
             own_handle.clear(); h_vals = nullptr; h_stats = nullptr; ev0 = ev1 = nullptr; V.tvals = nullptr; d_user_scale = nullptr; prof_ev.clear(); prof_used = 0; prof_kind.clear();
             if (stream3) { (void)hipStreamDestroy(stream3); stream3 = nullptr; }
             if (stream2) { (void)hipStreamDestroy(stream2); stream2 = nullptr; }
@@ -1251,7 +1253,7 @@ public:
     }
 
     // ---------------- low-rank update of the factored system: K~ = K + V V^T - U U^T (IpLowRankAugSystemSolver.cpp) ----------------
-    // V (rows x nv) and U (rows x nu) act on the first `rows` indices of the CALLER's numbering and stay on the device until lowrank_set /
+    // V (rows x nv) and U (rows x nu) act on `rows` indices of the CALLER's numbering (the first `rows`, or those of the row map rmap) and stay on the device until lowrank_set /
     // lowrank_clear; lowrank_update forms, through the CURRENT factorisation,
     //   Z1 = K^-1 V,  M1 = I + sym(V^T Z1),  W1 = K^-1 U,  C = M1^-1 (Z1^T U),  Z2 = W1 - Z1 C,  M2 = I - sym(U^T Z2)          (:299-396)
     // and a solve corrects x0 = K^-1 b in place:  x1 = x0 - Z1 M1^-1 (V^T x0),  x = x1 + Z2 M2^-1 (U^T x1)                       (:195-228, from the
@@ -1272,15 +1274,47 @@ public:
         return false;
     }
     bool lr_fits_x(const char* who) {
+        if (rmap.rows > 0) {
+            if (rmap.h.back() < pd_.nx) return true;
+            err_ = std::string(who) + ": the row map of the low-rank update reaches beyond the x block (idx[rows-1] = " + std::to_string(rmap.h.back()) + " must be < n_x = " + std::to_string(pd_.nx) + ")"; return false;
+        }
         if (lr.rows <= pd_.nx) return true;
         err_ = std::string(who) + ": the low-rank update acts on more rows than the x block has (rows <= n_x)"; return false;
     }
+    // ---------------- the row map: row i of V, U, S, Y, DR is the caller's index idx[i] (P_LowRank; IpLowRankAugSystemSolver.cpp:274-290, :449-457) ----------------
+    // A property of the handle, in the caller's numbering: one device copy in its own arena, untouched by factorisations, structure edits, lowrank_clear,
+    // lbfgs_reset and lbfgs_clear.  It can change only while neither an update is set nor a history defined, and while it is set every update and history has
+    // rmap.rows rows (lr_rows_ok) -- with lr_rowmap_check (lowrank_host.h: strictly ascending, < n) that is why no kernel below indexes out of range.
+    struct RowMap { int rows = 0; const int* d = nullptr; std::vector<int32_t> h; } rmap;
+    bool lr_rows_ok(const std::string& who, int rows) {
+        if (rmap.rows == 0 || rows == rmap.rows) return true;
+        err_ = who + ": rows = " + std::to_string(rows) + " must equal the " + std::to_string(rmap.rows) + " rows of the row map while one is set (lowrank_rowmap)"; return false;
+    }
+    bool lowrank_rowmap(int rows, const int32_t* idx) {
+        DeviceGuard guard(dev);
+        if (!ready) { if (err_.empty()) err_ = "lowrank_rowmap: solver not set up"; return false; }
+        if (multi) { err_ = "lowrank_rowmap: not supported on a multi-GPU handle"; return false; }
+        if (lr.set) { err_ = "lowrank_rowmap: a low-rank update is set: the map cannot change under it (lowrank_clear first)"; return false; }
+        if (lb.defined) { err_ = "lowrank_rowmap: a history is defined: the map cannot change under it (lbfgs_clear first)"; return false; }
+        std::string why;
+        if (!lr_rowmap_check(S->n, rows, idx, why)) { err_ = "lowrank_rowmap: " + why; return false; }
+        HIPCHK(hipStreamSynchronize(stream));
+        own_map.clear(); rmap = {};
+        if (rows == 0 || !idx) return true;
+        std::vector<int32_t> hcopy(idx, idx + rows);
+        if (!own_map.upload(hcopy, &rmap.d)) { own_map.clear(); rmap = {}; return false; }
+        rmap.h = std::move(hcopy); rmap.rows = rows;
+        return true;
+    }
+    void lowrank_rowmap_info(int* rows, long long* last) const { if (rows) *rows = rmap.rows; if (last) *last = rmap.rows > 0 ? (long long)rmap.h.back() : -1; }
+    void lowrank_rowmap_copy(int32_t* idx) const { std::copy(rmap.h.begin(), rmap.h.end(), idx); }
     void lowrank_clear() { own_lr.clear(); lr = {}; }
     // the buffers of an update of the shape (rows, nv, nu), set and not current: those in place when that is the installed shape (nothing is
     // allocated: an L-BFGS push with a full history installs its columns into them), fresh ones otherwise.  Nothing may be in flight on them.
     // cap > 0 (an SR1 push, whose split nv + nu = m moves from push to push): fresh buffers get room for max(nv, cap) and max(nu, cap) columns, and
     // buffers in place are kept whenever they have room for nv and nu columns -- then a push allocates nothing although the shape changes.
     bool lr_shape(int rows, int nv, int nu, int cap = 0) {
+        if (!lr_rows_ok("lowrank_set", rows)) return false;
         const bool fits = cap > 0 ? nv <= lr.capv && nu <= lr.capu : nv == lr.nv && nu == lr.nu;
         if (lr.set && rows == lr.rows && fits) { lr.nv = nv; lr.nu = nu; lr.ok = false; lr.at = -1; lr.update_ms = 0; return true; }
         lowrank_clear();
@@ -1306,22 +1340,31 @@ public:
         return true;
     }
     // G = A^T B over the first lr.rows rows: gy = 1: one p x q block; gy > 1 (q = 1): gy separate columns of B.  Partials into lr.part.
-    void lr_gram(const double* A, long long lda, const double* B, long long ldb, int p, int q, int gy) {
-        hipLaunchKernelGGL(k_lr_gram, dim3(lr.nslab(), gy), dim3(256), 0, stream, A, lda, B, ldb, lr.rows, p, q, lr.part);
+    // nside: which operand has n rows (0 neither, 1 A, 2 B): under a row map that one is read through the map; without a map all are the one unmapped kernel
+    void lr_gram(const double* A, long long lda, const double* B, long long ldb, int p, int q, int gy, int nside) {
+        const dim3 g(lr.nslab(), gy);
+        if (rmap.rows == 0 || nside == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lr_gram<false, false>), g, dim3(256), 0, stream, A, lda, B, ldb, lr.rows, p, q, lr.part, (const int*)nullptr);
+        else if (nside == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lr_gram<true, false>), g, dim3(256), 0, stream, A, lda, B, ldb, lr.rows, p, q, lr.part, rmap.d);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lr_gram<false, true>), g, dim3(256), 0, stream, A, lda, B, ldb, lr.rows, p, q, lr.part, rmap.d);
     }
     // the p x q Gram A^T B, summed on the device, into the pinned lr.h (synchronises)
-    bool lr_gram_host(const double* A, long long lda, const double* B, long long ldb, int p, int q) {
-        lr_gram(A, lda, B, ldb, p, q, 1);
+    bool lr_gram_host(const double* A, long long lda, const double* B, long long ldb, int p, int q, int nside) {
+        lr_gram(A, lda, B, ldb, p, q, 1, nside);
         hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lr.part, lr.nslab(), (long long)p, (long long)p * q, p, q, (const double*)nullptr, lr.T);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(lr.h, lr.T, (size_t)p * q * sizeof(double), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
         return true;
     }
-    // Z (n x p) <- the columns of A (lr.rows x p) padded with zero rows, on the solver's stream
+    // Z (n x p) <- the columns of A (lr.rows x p) padded with zero rows (under a row map: row i goes to row idx[i]), on the solver's stream
     bool lr_pad(double* Z, const double* A, int p) {
         const size_t n = S->n;
         HIPCHK(hipMemsetAsync(Z, 0, n * (size_t)p * sizeof(double), stream));
+        if (rmap.rows > 0) {
+            hipLaunchKernelGGL(k_lr_scatter, dim3((lr.rows + 255) / 256, p), dim3(256), 0, stream, Z, (long long)n, A, lr.rows, rmap.d);
+            HIPCHK(hipGetLastError());
+            return true;
+        }
         if (lr.rows > 0) HIPCHK(hipMemcpy2DAsync(Z, n * sizeof(double), A, (size_t)lr.rows * sizeof(double), (size_t)lr.rows * sizeof(double), p, hipMemcpyDeviceToDevice, stream));
         return true;
     }
@@ -1340,7 +1383,7 @@ public:
         // (Gram, apply) is ordered behind all columns.
         if (n > 0 && nv > 0) {
             if (!lr_pad(lr.Z1, lr.V, nv) || !solve_device(nv, lr.Z1, n, lr.Z1, n, true)) return false;
-            if (!lr_gram_host(lr.V, lr.rows, lr.Z1, n, nv, nv)) return false;
+            if (!lr_gram_host(lr.V, lr.rows, lr.Z1, n, nv, nv, 2)) return false;
             lr_shifted_sym(lr.h, nv, 1.0, M);
             if (!lr_cholesky(M, nv)) { *which = 1; return true; }
             HIPCHK(hipMemcpyAsync(lr.L1, M, (size_t)nv * nv * sizeof(double), hipMemcpyHostToDevice, stream));
@@ -1349,15 +1392,15 @@ public:
         if (n > 0 && nu > 0) {
             if (!lr_pad(lr.Z2, lr.U, nu) || !solve_device(nu, lr.Z2, n, lr.Z2, n, true)) return false;      // W1
             if (nv > 0) {
-                if (!lr_gram_host(lr.Z1, n, lr.U, lr.rows, nv, nu)) return false;                          // Z1^T U
+                if (!lr_gram_host(lr.Z1, n, lr.U, lr.rows, nv, nu, 1)) return false;                          // Z1^T U
                 for (int e = 0; e < nv * nu; ++e) Cm[e] = lr.h[e];
                 lr_cholesky_solve(M, nv, Cm, nu);                                                           // C = M1^-1 (Z1^T U)
                 HIPCHK(hipMemcpyAsync(lr.T, Cm, (size_t)nv * nu * sizeof(double), hipMemcpyHostToDevice, stream));
-                hipLaunchKernelGGL(k_lr_apply, dim3((n + 255) / 256), dim3(256), 0, stream, lr.Z2, (long long)n, (const double*)lr.Z1, (long long)n, (const double*)lr.T, (long long)n, nv, nu, -1.0);      // Z2 = W1 - Z1 C
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lr_apply<false>), dim3((n + 255) / 256), dim3(256), 0, stream, lr.Z2, (long long)n, (const double*)lr.Z1, (long long)n, (const double*)lr.T, (long long)n, nv, nu, -1.0, (const int*)nullptr);      // Z2 = W1 - Z1 C
                 HIPCHK(hipGetLastError());
                 HIPCHK(hipStreamSynchronize(stream));  // (Cm is pageable; lr.T is written again by the next Gram)
             }
-            if (!lr_gram_host(lr.U, lr.rows, lr.Z2, n, nu, nu)) return false;
+            if (!lr_gram_host(lr.U, lr.rows, lr.Z2, n, nu, nu, 2)) return false;
             lr_shifted_sym(lr.h, nu, -1.0, M);
             if (!lr_cholesky(M, nu)) { *which = 2; return true; }
             HIPCHK(hipMemcpyAsync(lr.L2, M, (size_t)nu * nu * sizeof(double), hipMemcpyHostToDevice, stream));
@@ -1376,29 +1419,30 @@ public:
             const int nc = std::min(LR_MAX, nrhs - c0);
             double* Xc = X + (long long)c0 * ldx;
             if (lr.nv > 0) {
-                lr_gram(lr.V, lr.rows, Xc, ldx, lr.nv, 1, nc);
+                lr_gram(lr.V, lr.rows, Xc, ldx, lr.nv, 1, nc, 2);
                 hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lr.part, nslab, (long long)nslab * lr.nv, (long long)lr.nv, lr.nv, nc, (const double*)lr.L1, lr.T);
-                hipLaunchKernelGGL(k_lr_apply, dim3(ga), dim3(256), 0, stream, Xc, ldx, (const double*)lr.Z1, n, (const double*)lr.T, n, lr.nv, nc, -1.0);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lr_apply<false>), dim3(ga), dim3(256), 0, stream, Xc, ldx, (const double*)lr.Z1, n, (const double*)lr.T, n, lr.nv, nc, -1.0, (const int*)nullptr);
             }
             if (lr.nu > 0) {
-                lr_gram(lr.U, lr.rows, Xc, ldx, lr.nu, 1, nc);
+                lr_gram(lr.U, lr.rows, Xc, ldx, lr.nu, 1, nc, 2);
                 hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lr.part, nslab, (long long)nslab * lr.nu, (long long)lr.nu, lr.nu, nc, (const double*)lr.L2, lr.T);
-                hipLaunchKernelGGL(k_lr_apply, dim3(ga), dim3(256), 0, stream, Xc, ldx, (const double*)lr.Z2, n, (const double*)lr.T, n, lr.nu, nc, 1.0);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lr_apply<false>), dim3(ga), dim3(256), 0, stream, Xc, ldx, (const double*)lr.Z2, n, (const double*)lr.T, n, lr.nu, nc, 1.0, (const int*)nullptr);
             }
         }
         HIPCHK(hipGetLastError());
         return true;
     }
-    // resid[0:rows] += V (V^T res[0:rows]) - U (U^T res[0:rows])   (the x rows of the unreduced residual; W holds B0 only)
+    // resid[0:rows] += V (V^T res[0:rows]) - U (U^T res[0:rows])   (the x rows of the unreduced residual; W holds B0 only); under a row map: resid[idx] += V (V^T res[idx]) - ...
     bool lr_residual(const double* res, double* resid) {
         if (lr.rows == 0) return true;
         const int ga = (lr.rows + 255) / 256;
         for (int half = 0; half < 2; ++half) {
             const int p = half == 0 ? lr.nv : lr.nu; const double* A = half == 0 ? lr.V : lr.U;
             if (p == 0) continue;
-            lr_gram(A, lr.rows, res, lr.rows, p, 1, 1);
+            lr_gram(A, lr.rows, res, lr.rows, p, 1, 1, 2);
             hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lr.part, lr.nslab(), (long long)lr.nslab() * p, (long long)p, p, 1, (const double*)nullptr, lr.T);
-            hipLaunchKernelGGL(k_lr_apply, dim3(ga), dim3(256), 0, stream, resid, (long long)lr.rows, A, (long long)lr.rows, (const double*)lr.T, (long long)lr.rows, p, 1, half == 0 ? 1.0 : -1.0);
+            if (rmap.rows > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lr_apply<true>), dim3(ga), dim3(256), 0, stream, resid, (long long)lr.rows, A, (long long)lr.rows, (const double*)lr.T, (long long)lr.rows, p, 1, half == 0 ? 1.0 : -1.0, rmap.d);
+            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lr_apply<false>), dim3(ga), dim3(256), 0, stream, resid, (long long)lr.rows, A, (long long)lr.rows, (const double*)lr.T, (long long)lr.rows, p, 1, half == 0 ? 1.0 : -1.0, (const int*)nullptr);
         }
         HIPCHK(hipGetLastError());
         return true;
@@ -1456,6 +1500,7 @@ public:
         LbParams par; LbState st, backup; bool backup_valid = false;      // backup: the state before the last stored SR1 push, while that can be undone
         double *S = nullptr, *Y = nullptr, *sy = nullptr, *part = nullptr, *T = nullptr, *coef = nullptr, *h = nullptr, *hc = nullptr;
         LbResto rs, rs_backup; double* DR = nullptr;                     // a resto history only (par.resto)
+        double* xs = nullptr; size_t xs_cap = 0;                          // a mapped push of host vectors: the staging of the two full-space vectors (2 * xs_cap doubles, made on first use)
         int nslab() const { return std::max(1, (rows + LR_SLAB - 1) / LR_SLAB); }
     } lb;
     LbRing lb_ring(int m) const { LbRing R; R.m = m; for (int j = 0; j < LB_MAX; ++j) R.slot[j] = (unsigned char)lb_slot(lb.par, lb.st, j); return R; }      // (a defined history: slots >= 1)
@@ -1467,6 +1512,7 @@ public:
         const char* who = dr ? "lbfgs_define_resto" : "lbfgs_define";
         if (!ready) { if (err_.empty()) err_ = std::string(who) + ": solver not set up"; return false; }
         if (multi) { err_ = std::string(who) + ": not supported on a multi-GPU handle"; return false; }
+        if (!lr_rows_ok(who, rows)) return false;
         HIPCHK(hipStreamSynchronize(stream));
         lbfgs_clear();
         lb.rows = rows; lb.par = dr ? lb_params_resto(type, special, max_history, init, init_val, smin, smax) : lb_params(type, max_history, init, init_val, smin, smax); lb_forget();
@@ -1562,10 +1608,11 @@ public:
     // s, y: host vectors (device = false: uploaded to the staging pair) or device vectors of lb.rows.  *outcome: 0 stored and installed, 1 skipped (only the
     // counter moved), 2 (BFGS) stored, M not positive definite.  resto: the push of a restoration-phase history (y is ypart, eta > 0); a history takes
     // only the pushes of its own kind.  Either way: the dots (2 m + 3, or 3 m + 6), ONE download and synchronisation, the transition, the same tail.
-    bool lbfgs_push(const double* s, const double* y, bool device, int* outcome, bool resto = false, double eta = 0.0) {
+    // staged (lbfgs_push_mapped): the reduced pair is already in the staging pair lb.sy, on the stream; `device` then says whose vectors the gather read.
+    bool lbfgs_push(const double* s, const double* y, bool device, int* outcome, bool resto = false, double eta = 0.0, bool staged = false) {
         DeviceGuard guard(dev);
         *outcome = 1;
-        const std::string who = resto ? "lbfgs_push_resto" : "lbfgs_push";
+        const std::string who = std::string(resto ? "lbfgs_push_resto" : "lbfgs_push") + (staged ? "_mapped" : "");
         if (!ready) { if (err_.empty()) err_ = who + ": solver not set up"; return false; }
         if (!lb.defined) { err_ = who + (resto ? ": lbfgs_define_resto first" : ": lbfgs_define first"); return false; }
         if (lb.par.resto && !resto) { err_ = "lbfgs_push: this is a restoration-phase history (lbfgs_define_resto): push with lbfgs_push_resto"; return false; }
@@ -1573,7 +1620,8 @@ public:
         const auto t0 = std::chrono::steady_clock::now();
         const size_t vb = (size_t)lb.rows * sizeof(double);
         const double *ds = s, *dy = y;
-        if (!device) {
+        if (staged) { ds = lb.sy; dy = lb.sy + lb.rows; }
+        else if (!device) {
             HIPCHK(hipMemcpyAsync(lb.sy, s, vb, hipMemcpyHostToDevice, stream));
             HIPCHK(hipMemcpyAsync(lb.sy + lb.rows, y, vb, hipMemcpyHostToDevice, stream));
             ds = lb.sy; dy = lb.sy + lb.rows;
@@ -1603,10 +1651,39 @@ public:
             HIPCHK(hipMemcpyAsync(lb.S + slot, ds, vb, hipMemcpyDeviceToDevice, stream));
             HIPCHK(hipMemcpyAsync(lb.Y + slot, dy, vb, hipMemcpyDeviceToDevice, stream));
         }
-        if (r != LB_PUSH_SKIPPED && device) HIPCHK(hipStreamSynchronize(stream));      // (the caller's vectors are free again when the call returns)
+        if (r != LB_PUSH_SKIPPED && device && !staged) HIPCHK(hipStreamSynchronize(stream));      // (the caller's vectors are free again when the call returns; staged: the gather that read them ended before the synchronisation above)
         *outcome = r;
         lb.push_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         return true;
+    }
+    // sx, yx: x-block vectors of `len` entries (host, or device): gathered through the row map into the staging pair by ONE launch (P^T s_full, P^T y_full,
+    // IpLimMemQuasiNewtonUpdater.cpp:323-324), then lbfgs_push itself on that pair -- the same dots, download, synchronisation, transition and tail.
+    bool lbfgs_push_mapped(const double* sx, const double* yx, long long len, bool device, int* outcome, bool resto, double eta) {
+        *outcome = 1;
+        const std::string who = resto ? "lbfgs_push_resto_mapped" : "lbfgs_push_mapped";
+        {
+            DeviceGuard guard(dev);
+            if (!ready) { if (err_.empty()) err_ = who + ": solver not set up"; return false; }
+            if (!lb.defined) { err_ = who + (resto ? ": lbfgs_define_resto first" : ": lbfgs_define first"); return false; }
+            std::string why;
+            if (!lr_rowmap_len_check(len, rmap.rows > 0 ? (long long)rmap.h.back() : -1, why)) { err_ = who + ": " + why; return false; }
+            if (lb.rows != rmap.rows) { err_ = who + ": the history has not the rows of the row map"; return false; }      // (lr_rows_ok at define: cannot happen)
+            const double *dsx = sx, *dyx = yx;
+            if (!device) {
+                if (lb.xs_cap < (size_t)len) {
+                    HIPCHK(hipStreamSynchronize(stream));
+                    own_lb.free_device(lb.xs); lb.xs = nullptr; lb.xs_cap = 0;
+                    if (!own_lb.raw(&lb.xs, 2 * (size_t)len)) return false;
+                    lb.xs_cap = (size_t)len;
+                }
+                HIPCHK(hipMemcpyAsync(lb.xs, sx, (size_t)len * sizeof(double), hipMemcpyHostToDevice, stream));
+                HIPCHK(hipMemcpyAsync(lb.xs + lb.xs_cap, yx, (size_t)len * sizeof(double), hipMemcpyHostToDevice, stream));
+                dsx = lb.xs; dyx = lb.xs + lb.xs_cap;
+            }
+            hipLaunchKernelGGL(k_lr_gather2, dim3((lb.rows + 255) / 256), dim3(256), 0, stream, dsx, dyx, lb.rows, rmap.d, lb.sy, lb.sy + lb.rows);
+            HIPCHK(hipGetLastError());
+        }
+        return lbfgs_push(nullptr, nullptr, device, outcome, resto, eta, true);
     }
     void lbfgs_resto_info(int* resto, int* special, double* eta) const {
         const bool on = lb.defined && lb.par.resto;
@@ -1950,6 +2027,11 @@ bool Numeric::lowrank_set(int rows, int nv, const double* V, int ldv, int nu, co
 bool Numeric::lowrank_update(int* which) { return p_->lowrank_update(which); }
 bool Numeric::lowrank_solve_host(int nrhs, double* rhs, int ld) { return p_->lowrank_solve_host(nrhs, rhs, ld); }
 bool Numeric::lowrank_solve_device2(int nrhs, const double* db, int ldb, double* dx, int ldx) { return p_->lowrank_solve_device2(nrhs, db, ldb, dx, ldx); }
+bool Numeric::lowrank_rowmap(int rows, const int32_t* idx) { return p_->lowrank_rowmap(rows, idx); }
+void Numeric::lowrank_rowmap_info(int* rows, long long* last) const { p_->lowrank_rowmap_info(rows, last); }
+void Numeric::lowrank_rowmap_copy(int32_t* idx) const { p_->lowrank_rowmap_copy(idx); }
+bool Numeric::lbfgs_push_mapped(const double* sx, const double* yx, long long len, bool device, int* outcome) { return p_->lbfgs_push_mapped(sx, yx, len, device, outcome, false, 0.0); }
+bool Numeric::lbfgs_push_resto_mapped(const double* sx, const double* ypartx, long long len, double eta, bool device, int* outcome) { return p_->lbfgs_push_mapped(sx, ypartx, len, device, outcome, true, eta); }
 bool Numeric::lowrank_clear() { DeviceGuard guard(p_->dev); if (p_->stream) (void)hipStreamSynchronize(p_->stream); p_->lowrank_clear(); return true; }
 void Numeric::lowrank_info(int* rows, int* nv, int* nu, int* current, double* update_ms) const { p_->lowrank_info(rows, nv, nu, current, update_ms); }
 long long Numeric::factor_count() const { return p_->factor_count; }

@@ -77,6 +77,7 @@ ABI_SYMBOLS = [
     "mi355x_kkt_lbfgs_define", "mi355x_kkt_lbfgs_push", "mi355x_kkt_lbfgs_push_device", "mi355x_kkt_lbfgs_reset", "mi355x_kkt_lbfgs_clear", "mi355x_kkt_lbfgs_info", "mi355x_kkt_lbfgs_get", "mi355x_kkt_lbfgs_coefficients",
     "mi355x_kkt_lbfgs_define_sr1", "mi355x_kkt_lbfgs_undo", "mi355x_kkt_lbfgs_sr1_info", "mi355x_kkt_lbfgs_sr1_coefficients",
     "mi355x_kkt_lbfgs_define_resto", "mi355x_kkt_lbfgs_push_resto", "mi355x_kkt_lbfgs_push_resto_device", "mi355x_kkt_lbfgs_resto_info",
+    "mi355x_kkt_lowrank_rowmap", "mi355x_kkt_lowrank_rowmap_get", "mi355x_kkt_lowrank_rowmap_check", "mi355x_kkt_lbfgs_push_mapped", "mi355x_kkt_lbfgs_push_resto_mapped",
 ]
 LOWRANK_MAX = 32
 LBFGS_MAX = 32
@@ -169,6 +170,11 @@ def load_library():
     lib.mi355x_kkt_lbfgs_push_resto.argtypes = [vp, vp, vp, C.c_double, ip]
     lib.mi355x_kkt_lbfgs_push_resto_device.argtypes = [vp, vp, vp, C.c_double, ip]
     lib.mi355x_kkt_lbfgs_resto_info.argtypes = [vp, ip, ip, dp]
+    lib.mi355x_kkt_lowrank_rowmap.argtypes = [vp, C.c_int, vp]
+    lib.mi355x_kkt_lowrank_rowmap_get.argtypes = [vp, ip, vp, C.c_int64]
+    lib.mi355x_kkt_lowrank_rowmap_check.argtypes = [C.c_int64, C.c_int, vp, C.c_int64, C.c_char_p, C.c_int64]
+    lib.mi355x_kkt_lbfgs_push_mapped.argtypes = [vp, vp, vp, C.c_int64, C.c_int, ip]
+    lib.mi355x_kkt_lbfgs_push_resto_mapped.argtypes = [vp, vp, vp, C.c_int64, C.c_int, C.c_double, ip]
     lib.mi355x_kkt_set_comm_rccl.argtypes = [vp, vp]
     lib.mi355x_kkt_comm_shm_id.argtypes = [vp, C.c_int]
     lib.mi355x_kkt_set_comm_shm.argtypes = [vp, vp]
@@ -206,6 +212,15 @@ def lbfgs_sr1_coefficients(sts, L, D, sigma):
     if st == FATAL:
         raise KKTError("lbfgs_sr1_coefficients: m must be in [0, 32]" if not 0 <= m <= LBFGS_MAX else "lbfgs_sr1_coefficients: the eigen-solver did not converge")
     return st, E, Qs, nneg.value
+
+
+def lowrank_rowmap_check(n, idx, length=-1):
+    """host only, no handle, no GPU: (ok, reason) of include/mi355x_kkt.h's mi355x_kkt_lowrank_rowmap_check -- the validation every row map passes before the
+    device is touched (0-based, strictly ascending, < n) and, with length >= 0, that a full-space vector of `length` entries covers the map"""
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    msg = C.create_string_buffer(512)
+    st = load_library().mi355x_kkt_lowrank_rowmap_check(int(n), idx.size, idx.ctypes.data if idx.size else None, int(length), msg, 512)
+    return st == 0, msg.value.decode()
 
 
 class KKTSolver:
@@ -377,7 +392,7 @@ class KKTSolver:
 
     # --- low-rank update of the factored system, K + V V^T - U U^T (include/mi355x_kkt.h; reference IpLowRankAugSystemSolver.cpp) ---
     def lowrank_set(self, V, U, rows=None):
-        """V (rows x nv) and U (rows x nu), numpy, acting on the first `rows` indices; None or zero columns = that half is absent"""
+        """V (rows x nv) and U (rows x nu), numpy, acting on the first `rows` indices, or on those of the row map (lowrank_rowmap); None or zero columns = that half is absent"""
         def prep(A):
             if A is None:
                 return None
@@ -425,6 +440,33 @@ class KKTSolver:
         if self.lib.mi355x_kkt_lowrank_info(self._h, C.byref(r), C.byref(v), C.byref(u), C.byref(c), C.byref(ms)) != 0:
             raise KKTError("lowrank_info: " + self.last_error())
         return {"rows": r.value, "nv": v.value, "nu": u.value, "current": bool(c.value), "update_ms": ms.value}
+
+    # --- the row map (the reference's P_LowRank): row i of V, U, S, Y, DR is the caller's index idx[i] ---
+    def lowrank_rowmap(self, idx):
+        """idx: 0-based, strictly ascending indices below n (ExpansionMatrix::ExpandedPosIndices), or None / empty to remove the map; refused while an update
+        is set or a history defined.  While it is set, lowrank_set and the lbfgs_define* calls take len(idx) rows."""
+        if idx is None:
+            st = self.lib.mi355x_kkt_lowrank_rowmap(self._h, 0, None)
+        else:
+            a = np.asarray(idx)
+            if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)) or (a.size and (a.min() < -2**31 or a.max() >= 2**31)):
+                raise KKTError("lowrank_rowmap: idx must be a vector of int32 indices")
+            a = np.ascontiguousarray(a, dtype=np.int32)
+            st = self.lib.mi355x_kkt_lowrank_rowmap(self._h, a.size, a.ctypes.data if a.size else None)
+        if st != 0:
+            raise KKTError("lowrank_rowmap: " + self.last_error())
+
+    def lowrank_rowmap_info(self):
+        """None when no map is set, else the indices (int32)"""
+        r = C.c_int(0)
+        if self.lib.mi355x_kkt_lowrank_rowmap_get(self._h, C.byref(r), None, 0) != 0:
+            raise KKTError("lowrank_rowmap_info: " + self.last_error())
+        if r.value == 0:
+            return None
+        out = np.zeros(r.value, dtype=np.int32)
+        if self.lib.mi355x_kkt_lowrank_rowmap_get(self._h, C.byref(r), out.ctypes.data, out.size) != 0:
+            raise KKTError("lowrank_rowmap_info: " + self.last_error())
+        return out
 
     # --- limited-memory BFGS: the (s, y) history on the device, V and U formed there (include/mi355x_kkt.h; reference IpLimMemQuasiNewtonUpdater.cpp) ---
     def lbfgs_define(self, rows, max_history=6, init="scalar1", init_val=1.0, sigma_min=1e-8, sigma_max=1e8):
@@ -531,6 +573,39 @@ class KKTSolver:
         oc = C.c_int(0)
         if self.lib.mi355x_kkt_lbfgs_push_resto_device(self._h, C.c_void_p(ds_ptr), C.c_void_p(dypart_ptr), float(eta), C.byref(oc)) != 0:
             raise KKTError("lbfgs_push_resto_device: " + self.last_error())
+        return oc.value
+
+    # --- pushes of full-space (x-block) vectors under a row map: gathered on the device, then the plain push (IpLimMemQuasiNewtonUpdater.cpp:323-324) ---
+    def lbfgs_push_mapped(self, sx: np.ndarray, yx: np.ndarray) -> int:
+        """host x-block vectors of equal length > idx[rows-1]; -> outcome as lbfgs_push of (sx[idx], yx[idx]), bit for bit"""
+        sx = np.ascontiguousarray(sx, dtype=np.float64); yx = np.ascontiguousarray(yx, dtype=np.float64)
+        if sx.ndim != 1 or sx.shape != yx.shape:
+            raise KKTError("lbfgs_push_mapped: sx and yx must be vectors of one length")
+        return self._push_mapped("lbfgs_push_mapped", sx.ctypes.data, yx.ctypes.data, sx.size, 0, None)
+
+    def lbfgs_push_resto_mapped(self, sx: np.ndarray, ypartx: np.ndarray, eta: float) -> int:
+        """host x-block vectors of equal length > idx[rows-1], eta > 0; -> outcome as lbfgs_push_resto of the gathered vectors"""
+        sx = np.ascontiguousarray(sx, dtype=np.float64); ypartx = np.ascontiguousarray(ypartx, dtype=np.float64)
+        if sx.ndim != 1 or sx.shape != ypartx.shape:
+            raise KKTError("lbfgs_push_resto_mapped: sx and ypartx must be vectors of one length")
+        return self._push_mapped("lbfgs_push_resto_mapped", sx.ctypes.data, ypartx.ctypes.data, sx.size, 0, eta)
+
+    def lbfgs_push_mapped_device(self, dsx_ptr: int, dyx_ptr: int, length: int) -> int:
+        """device x-block vectors of `length` entries, complete before the call"""
+        return self._push_mapped("lbfgs_push_mapped", C.c_void_p(dsx_ptr), C.c_void_p(dyx_ptr), length, 1, None)
+
+    def lbfgs_push_resto_mapped_device(self, dsx_ptr: int, dypartx_ptr: int, length: int, eta: float) -> int:
+        """device x-block vectors of `length` entries, complete before the call"""
+        return self._push_mapped("lbfgs_push_resto_mapped", C.c_void_p(dsx_ptr), C.c_void_p(dypartx_ptr), length, 1, eta)
+
+    def _push_mapped(self, name, ps, py, length, on_device, eta):
+        oc = C.c_int(0)
+        if eta is None:
+            st = self.lib.mi355x_kkt_lbfgs_push_mapped(self._h, ps, py, int(length), on_device, C.byref(oc))
+        else:
+            st = self.lib.mi355x_kkt_lbfgs_push_resto_mapped(self._h, ps, py, int(length), on_device, float(eta), C.byref(oc))
+        if st != 0:
+            raise KKTError(name + ": " + self.last_error())
         return oc.value
 
     def lbfgs_resto_info(self) -> dict:
