@@ -500,28 +500,31 @@ int mi355x_kkt_lowrank_rowmap_check(int64_t n, int rows, const int32_t* idx, int
     if (msg && capacity > 0) { const size_t k = std::min<size_t>(why.size(), (size_t)capacity - 1); std::memcpy(msg, why.data(), k); msg[k] = 0; }
     return ok ? MI355X_KKT_SUCCESS : MI355X_KKT_FATAL;
 }
-// a push of full-space vectors: pointers, eta, the multi-GPU refusal, then the map and len (host state), then the device
-static int lbfgs_push_mapped_any(mi355x_kkt_handle h, const char* name, const double* sx, const double* yx, int64_t len, int on_device, bool resto, double eta, int* outcome)
+// every push of a history: pointers, eta (a resto push); x-block vectors (mapped): the multi-GPU refusal, then the map and len (host state); then the device
+static int lbfgs_push_checked(mi355x_kkt_handle h, const char* name, mi355x::LbPush p, bool mapped, int* outcome)
 {
     if (!h) return MI355X_KKT_FATAL;
     if (outcome) *outcome = 1;
     if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
-    if (!sx) LR_FAIL("sx is null");
-    if (!yx) LR_FAIL(resto ? "ypartx is null" : "yx is null");
-    if (resto && (!(eta > 0.0) || !std::isfinite(eta))) LR_FAIL("eta must be positive and finite");
-    if (h->opts.nranks > 1) LR_FAIL("not supported on a multi-GPU handle");
-    long long last = -1; std::string why;
-    if (h->num) h->num->lowrank_rowmap_info(nullptr, &last);
-    if (!lr_rowmap_len_check((long long)len, last, why)) LR_FAIL(why);
+    const std::string pre = p.device && !mapped ? "d_" : "", post = mapped ? "x is null" : " is null";
+    if (!p.s) LR_FAIL(pre + "s" + post);
+    if (!p.y) LR_FAIL(pre + (p.resto ? "ypart" : "y") + post);
+    if (p.resto && (!(p.eta > 0.0) || !std::isfinite(p.eta))) LR_FAIL("eta must be positive and finite");
+    if (mapped) {
+        if (h->opts.nranks > 1) LR_FAIL("not supported on a multi-GPU handle");
+        long long last = -1; std::string why;
+        if (h->num) h->num->lowrank_rowmap_info(nullptr, &last);
+        if (!lr_rowmap_len_check(p.len, last, why)) LR_FAIL(why);
+    }
     int oc = 1;
-    const int st = lowrank_call(h, name, false, [&] { return resto ? h->num->lbfgs_push_resto_mapped(sx, yx, (long long)len, eta, on_device != 0, &oc) : h->num->lbfgs_push_mapped(sx, yx, (long long)len, on_device != 0, &oc); });
+    const int st = lowrank_call(h, name, false, [&] { return h->num->lbfgs_push(p, &oc); });
     if (st == MI355X_KKT_SUCCESS && outcome) *outcome = oc;
     return st;
 }
 int mi355x_kkt_lbfgs_push_mapped(mi355x_kkt_handle h, const double* sx, const double* yx, int64_t len, int on_device, int* outcome)
-{ return lbfgs_push_mapped_any(h, "lbfgs_push_mapped", sx, yx, len, on_device, false, 0.0, outcome); }
+{ return lbfgs_push_checked(h, "lbfgs_push_mapped", {sx, yx, (long long)len, on_device != 0, false, 0.0}, true, outcome); }
 int mi355x_kkt_lbfgs_push_resto_mapped(mi355x_kkt_handle h, const double* sx, const double* ypartx, int64_t len, int on_device, double eta, int* outcome)
-{ return lbfgs_push_mapped_any(h, "lbfgs_push_resto_mapped", sx, ypartx, len, on_device, true, eta, outcome); }
+{ return lbfgs_push_checked(h, "lbfgs_push_resto_mapped", {sx, ypartx, (long long)len, on_device != 0, true, eta}, true, outcome); }
 // ---- limited-memory BFGS on the device (IpLimMemQuasiNewtonUpdater.cpp): the (s, y) history, V and U formed there and installed as the low-rank update ----
 // The same order as above: every argument, then the multi-GPU refusal, then the device.
 static int lbfgs_define_args(mi355x_kkt_handle h, const char* name, int rows, int max_history, int init, double init_val)      // (lbfgs_define and lbfgs_define_sr1)
@@ -534,29 +537,21 @@ static int lbfgs_define_args(mi355x_kkt_handle h, const char* name, int rows, in
     if (!(init_val > 0.0) || !std::isfinite(init_val)) LR_FAIL("init_val must be positive and finite");
     return MI355X_KKT_SUCCESS;
 }
+static int lbfgs_sigma_args(mi355x_kkt_handle h, const char* name, double sigma_min, double sigma_max)      // (lbfgs_define and lbfgs_define_resto)
+{
+    if (!(sigma_min > 0.0) || !std::isfinite(sigma_min)) LR_FAIL("sigma_min must be positive and finite");
+    if (!(sigma_max >= sigma_min) || !std::isfinite(sigma_max)) LR_FAIL("sigma_max must be finite and >= sigma_min");
+    return MI355X_KKT_SUCCESS;
+}
 int mi355x_kkt_lbfgs_define(mi355x_kkt_handle h, int rows, int max_history, int init, double init_val, double sigma_min, double sigma_max)
 {
     if (!h) return MI355X_KKT_FATAL;
     const char* name = "lbfgs_define";
-    if (lbfgs_define_args(h, name, rows, max_history, init, init_val) != 0) return MI355X_KKT_FATAL;
-    if (!(sigma_min > 0.0) || !std::isfinite(sigma_min)) LR_FAIL("sigma_min must be positive and finite");
-    if (!(sigma_max >= sigma_min) || !std::isfinite(sigma_max)) LR_FAIL("sigma_max must be finite and >= sigma_min");
-    return lowrank_call(h, name, false, [&] { return h->num->lbfgs_define(rows, max_history, init, init_val, sigma_min, sigma_max); });
+    if (lbfgs_define_args(h, name, rows, max_history, init, init_val) != 0 || lbfgs_sigma_args(h, name, sigma_min, sigma_max) != 0) return MI355X_KKT_FATAL;
+    return lowrank_call(h, name, false, [&] { return h->num->lbfgs_define({rows, max_history, MI355X_KKT_LBFGS_BFGS, init, init_val, sigma_min, sigma_max}); });
 }
-static int lbfgs_push_any(mi355x_kkt_handle h, const char* name, const double* s, const double* y, bool device, int* outcome)
-{
-    if (!h) return MI355X_KKT_FATAL;
-    if (outcome) *outcome = 1;
-    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
-    if (!s) LR_FAIL(device ? "d_s is null" : "s is null");
-    if (!y) LR_FAIL(device ? "d_y is null" : "y is null");
-    int oc = 1;
-    const int st = lowrank_call(h, name, false, [&] { return h->num->lbfgs_push(s, y, device, &oc); });
-    if (st == MI355X_KKT_SUCCESS && outcome) *outcome = oc;
-    return st;
-}
-int mi355x_kkt_lbfgs_push(mi355x_kkt_handle h, const double* s, const double* y, int* outcome) { return lbfgs_push_any(h, "lbfgs_push", s, y, false, outcome); }
-int mi355x_kkt_lbfgs_push_device(mi355x_kkt_handle h, const double* d_s, const double* d_y, int* outcome) { return lbfgs_push_any(h, "lbfgs_push_device", d_s, d_y, true, outcome); }
+int mi355x_kkt_lbfgs_push(mi355x_kkt_handle h, const double* s, const double* y, int* outcome) { return lbfgs_push_checked(h, "lbfgs_push", {s, y}, false, outcome); }
+int mi355x_kkt_lbfgs_push_device(mi355x_kkt_handle h, const double* d_s, const double* d_y, int* outcome) { return lbfgs_push_checked(h, "lbfgs_push_device", {d_s, d_y, 0, true}, false, outcome); }
 int mi355x_kkt_lbfgs_reset(mi355x_kkt_handle h) { return lowrank_call(h, "lbfgs_reset", false, [&] { return h->num->lbfgs_reset(); }); }
 int mi355x_kkt_lbfgs_clear(mi355x_kkt_handle h) { return lowrank_call(h, "lbfgs_clear", false, [&] { return h->num->lbfgs_clear(); }); }
 int mi355x_kkt_lbfgs_info(mi355x_kkt_handle h, int* rows, int* max_history, int* memory, double* sigma, int* skipped_in_a_row, double* push_ms)
@@ -587,7 +582,7 @@ int mi355x_kkt_lbfgs_define_sr1(mi355x_kkt_handle h, int rows, int max_history, 
     if (!h) return MI355X_KKT_FATAL;
     const char* name = "lbfgs_define_sr1";
     if (lbfgs_define_args(h, name, rows, max_history, init, init_val) != 0) return MI355X_KKT_FATAL;
-    return lowrank_call(h, name, false, [&] { return h->num->lbfgs_define_sr1(rows, max_history, init, init_val); });
+    return lowrank_call(h, name, false, [&] { return h->num->lbfgs_define({rows, max_history, MI355X_KKT_LBFGS_SR1, init, init_val, mi355x::LB_SR1_SIGMA_MIN, mi355x::LB_SR1_SIGMA_MAX}); });
 }
 int mi355x_kkt_lbfgs_undo(mi355x_kkt_handle h, int* undone)
 {
@@ -630,28 +625,14 @@ int mi355x_kkt_lbfgs_define_resto(mi355x_kkt_handle h, int rows, int max_history
     if (lbfgs_define_args(h, name, rows, max_history, init, init_val) != 0) return MI355X_KKT_FATAL;
     if (type != MI355X_KKT_LBFGS_BFGS && type != MI355X_KKT_LBFGS_SR1) LR_FAIL("type must be 0 (BFGS) or 1 (SR1)");
     if (special != 0 && special != 1) LR_FAIL("special must be 0 or 1");
-    if (!(sigma_min > 0.0) || !std::isfinite(sigma_min)) LR_FAIL("sigma_min must be positive and finite");
-    if (!(sigma_max >= sigma_min) || !std::isfinite(sigma_max)) LR_FAIL("sigma_max must be finite and >= sigma_min");
+    if (lbfgs_sigma_args(h, name, sigma_min, sigma_max) != 0) return MI355X_KKT_FATAL;
     if (!dr) LR_FAIL("dr is null");
     for (int i = 0; i < rows; ++i)
         if (!(dr[i] > 0.0) || !std::isfinite(dr[i])) LR_FAIL("dr must be positive and finite (entry " + std::to_string(i) + " is not)");
-    return lowrank_call(h, name, false, [&] { return h->num->lbfgs_define_resto(rows, max_history, type, special, init, init_val, sigma_min, sigma_max, dr); });
+    return lowrank_call(h, name, false, [&] { return h->num->lbfgs_define({rows, max_history, type, init, init_val, sigma_min, sigma_max, dr, special}); });
 }
-static int lbfgs_push_resto_any(mi355x_kkt_handle h, const char* name, const double* s, const double* ypart, double eta, bool device, int* outcome)
-{
-    if (!h) return MI355X_KKT_FATAL;
-    if (outcome) *outcome = 1;
-    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
-    if (!s) LR_FAIL(device ? "d_s is null" : "s is null");
-    if (!ypart) LR_FAIL(device ? "d_ypart is null" : "ypart is null");
-    if (!(eta > 0.0) || !std::isfinite(eta)) LR_FAIL("eta must be positive and finite");
-    int oc = 1;
-    const int st = lowrank_call(h, name, false, [&] { return h->num->lbfgs_push_resto(s, ypart, eta, device, &oc); });
-    if (st == MI355X_KKT_SUCCESS && outcome) *outcome = oc;
-    return st;
-}
-int mi355x_kkt_lbfgs_push_resto(mi355x_kkt_handle h, const double* s, const double* ypart, double eta, int* outcome) { return lbfgs_push_resto_any(h, "lbfgs_push_resto", s, ypart, eta, false, outcome); }
-int mi355x_kkt_lbfgs_push_resto_device(mi355x_kkt_handle h, const double* d_s, const double* d_ypart, double eta, int* outcome) { return lbfgs_push_resto_any(h, "lbfgs_push_resto_device", d_s, d_ypart, eta, true, outcome); }
+int mi355x_kkt_lbfgs_push_resto(mi355x_kkt_handle h, const double* s, const double* ypart, double eta, int* outcome) { return lbfgs_push_checked(h, "lbfgs_push_resto", {s, ypart, 0, false, true, eta}, false, outcome); }
+int mi355x_kkt_lbfgs_push_resto_device(mi355x_kkt_handle h, const double* d_s, const double* d_ypart, double eta, int* outcome) { return lbfgs_push_checked(h, "lbfgs_push_resto_device", {d_s, d_ypart, 0, true, true, eta}, false, outcome); }
 int mi355x_kkt_lbfgs_resto_info(mi355x_kkt_handle h, int* resto, int* special, double* eta)
 {
     if (!h) return MI355X_KKT_FATAL;

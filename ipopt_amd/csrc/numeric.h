@@ -27,6 +27,21 @@ struct NumericOptions {
 // num_fast = pivot blocks of big fronts accepted on the blocked a-posteriori path (the others took the strict loop)
 struct FactorStats { int num_neg = 0, num_zero = 0, num_two = 0, num_small = 0, u_sensitive = 1, num_fast = 0; };
 
+// the two requests of a limited-memory quasi-Newton history (Numeric::lbfgs_define, lbfgs_push)
+struct LbDefine {
+    int rows, max_history, type;                      // type 0 BFGS / 1 SR1
+    int init; double init_val, smin, smax;            // the rule of the first sigma and its bounds
+    const double* dr = nullptr;                       // host, `rows` positive entries: a restoration-phase history (B0 = sigma I, or eta DR when special)
+    int special = 0;
+};
+constexpr double LB_SR1_SIGMA_MIN = 1e-8, LB_SR1_SIGMA_MAX = 1e8;      // smin, smax of a plain SR1 history (its C entry point takes none)
+struct LbPush {
+    const double *s, *y;                              // host or device vectors; y is ypart when resto
+    long long len = 0;                                // 0: vectors of the history's `rows`; > idx[rows-1]: x-block vectors of len entries, gathered through the row map (:323-324)
+    bool device = false, resto = false;
+    double eta = 0.0;                                 // a resto push only (> 0)
+};
+
 class NumericImpl;
 
 class Numeric {
@@ -100,14 +115,11 @@ public:
     bool   lowrank_rowmap(int rows, const int32_t* idx);
     void   lowrank_rowmap_info(int* rows, long long* last) const;
     void   lowrank_rowmap_copy(int32_t* idx) const;          // `rows` entries (the caller checks the capacity)
-    // a push of x-block vectors of `len` > idx[rows-1] entries: gathered through the map on the device, then the plain push (:323-324)
-    bool   lbfgs_push_mapped(const double* sx, const double* yx, long long len, bool device, int* outcome);
-    bool   lbfgs_push_resto_mapped(const double* sx, const double* ypartx, long long len, double eta, bool device, int* outcome);
     // limited-memory BFGS (IpLimMemQuasiNewtonUpdater.cpp, BFGS "with skipping"): the (s, y) history of `rows` entries per vector stays on the device;
     // a push (host or device vectors) answers *outcome = 0 stored, V and U formed on the device and installed as the low-rank update above (not current),
     // 1 skipped, 2 stored but M not positive definite: the installed columns stay.  lbfgs_get what: 0 S, 1 Y, 2 V, 3 U, 4 D, 5 L, 6 S^T S.
-    bool   lbfgs_define(int rows, int max_history, int init, double init_val, double sigma_min, double sigma_max);
-    bool   lbfgs_push(const double* s, const double* y, bool device, int* outcome);
+    bool   lbfgs_define(const LbDefine& d);
+    bool   lbfgs_push(const LbPush& p, int* outcome);
     bool   lbfgs_reset();
     bool   lbfgs_clear();
     void   lbfgs_info(int* rows, int* max_history, int* memory, double* sigma, int* skipped_in_a_row, double* push_ms) const;
@@ -115,14 +127,10 @@ public:
     // limited-memory SR1 (the same file, case SR1): a history defined here answers a push with 0 or 1 only (V: memory - nneg columns, U: nneg, from
     // the eigen-split of Z = D + L + L^T - sigma S^T S) and can take its last stored push back once (lbfgs_undo; a BFGS history refuses).
     // lbfgs_sr1_info: E receives the `memory` eigenvalues of the installed split, ascending (the caller checks the capacity).
-    bool   lbfgs_define_sr1(int rows, int max_history, int init, double init_val);
     bool   lbfgs_undo(int* undone);
     void   lbfgs_sr1_info(int* type, int* nneg, int* can_undo, double* E) const;
-    // a restoration-phase history (lbfgs_host.h "the restoration phase"): type 0 BFGS / 1 SR1, special: B0 = eta DR; dr: host, `rows` positive entries.
-    // It is pushed with lbfgs_push_resto only (lbfgs_push refuses it, and the other way round); every other lbfgs_* call serves it unchanged.
-    // lbfgs_get what: 1 is Ypart; 10 G, 11 R, 12 eta_col, 13 dv, 14 DR.
-    bool   lbfgs_define_resto(int rows, int max_history, int type, int special, int init, double init_val, double sigma_min, double sigma_max, const double* dr);
-    bool   lbfgs_push_resto(const double* s, const double* ypart, double eta, bool device, int* outcome);
+    // a restoration-phase history (LbDefine::dr; lbfgs_host.h "the restoration phase") takes resto pushes only (LbPush::resto; a plain push is refused,
+    // and the other way round); every other lbfgs_* call serves it unchanged.  lbfgs_get what: 1 is Ypart; 10 G, 11 R, 12 eta_col, 13 dv, 14 DR.
     void   lbfgs_resto_info(int* resto, int* special, double* eta) const;
     long long factor_count() const;                  // bumped by every factorisation (the refactorisations of a delayed-pivot loop included) and every structure edit
     // communicator of a multi-GPU handle: with one set, factor()/solve_*() run the whole distributed sequence themselves

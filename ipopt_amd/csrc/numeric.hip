@@ -1489,12 +1489,12 @@ public:
     // passed, so a skipped push moves nothing but the counter; k_lb_form_sr1 forms V (m - nneg columns) and U (nneg).  One stored push can be taken back
     // (lbfgs_undo: the reference's RestoreInternalDataBackup): the state before it is kept in lb.backup, and the ring has max_history + 1 slots, so the
     // pair that push evicted is still in its slot.
-    // par.resto, a restoration-phase history (lbfgs_define_resto / lbfgs_push_resto; lbfgs_host.h "the restoration phase"): the ring's Y holds Ypart, DR is
-    // one more device vector of the arena, lb.rs (LbResto: G, R, eta, eta_col, dv) travels with lb.st and is backed up with it.  The same two kernels
-    // and one synchronisation per push: k_lb_dots_resto gives 3 m + 6 dots, lb_push_bfgs_resto / lb_push_sr1_resto turn them and eta into the
-    // coefficients, k_lb_form_resto / k_lb_form_sr1_resto form the columns; the tail (lb_install, lr_shape) is the plain one.
+    // par.resto, a restoration-phase history (LbDefine::dr / LbPush::resto; lbfgs_host.h "the restoration phase"): the ring's Y holds Ypart, DR is
+    // one more device vector of the arena, lb.rs (LbResto: G, R, eta, eta_col, dv) travels with lb.st and is backed up with it.  The same kernels in
+    // their resto instantiations (lb_with_kp_mode) and one synchronisation per push: k_lb_dots gives 3 m + 6 dots, lb_push_bfgs_resto /
+    // lb_push_sr1_resto turn them and eta into the coefficients, k_lb_form / k_lb_form_sr1 form the columns; the tail (lb_install, lr_shape) is the same.
     static_assert(LB_MAX == LBH_MAX, "the kernels and lbfgs_host.h agree on the number of pairs");
-    static_assert(LB_NOUT_RESTO == LBH_NDOT_RESTO, "the kernels and lbfgs_host.h agree on the dots of a resto push");
+    static_assert(lb_nout(LB_RESTO) == LBH_NDOT_RESTO, "the kernels and lbfgs_host.h agree on the dots of a resto push");
     struct History {                           // everything of the history but its arena (own_lb): lbfgs_clear() is own_lb.clear(); lb = {};
         bool defined = false; int rows = 0; double push_ms = 0;
         LbParams par; LbState st, backup; bool backup_valid = false;      // backup: the state before the last stored SR1 push, while that can be undone
@@ -1506,18 +1506,19 @@ public:
     LbRing lb_ring(int m) const { LbRing R; R.m = m; for (int j = 0; j < LB_MAX; ++j) R.slot[j] = (unsigned char)lb_slot(lb.par, lb.st, j); return R; }      // (a defined history: slots >= 1)
     void lb_forget() { lb.st = lb.par.resto ? lb_fresh_resto(lb.par) : lb_fresh(lb.par); lb.rs = {}; lb.backup_valid = false; }
     void lbfgs_clear() { own_lb.clear(); lb = {}; }
-    // dr != nullptr: a restoration-phase history with the host vector DR of `rows` entries (its dots and coefficients are wider: buffers sized on their own)
-    bool lbfgs_define(int rows, int max_history, int init, double init_val, double smin, double smax, int type, const double* dr = nullptr, int special = 0) {
+    // d.dr != nullptr: a restoration-phase history with the host vector DR of `rows` entries (its dots and coefficients are wider: buffers sized on their own)
+    bool lbfgs_define(const LbDefine& d) {
         DeviceGuard guard(dev);
+        const int rows = d.rows; const double* dr = d.dr;
         const char* who = dr ? "lbfgs_define_resto" : "lbfgs_define";
         if (!ready) { if (err_.empty()) err_ = std::string(who) + ": solver not set up"; return false; }
         if (multi) { err_ = std::string(who) + ": not supported on a multi-GPU handle"; return false; }
         if (!lr_rows_ok(who, rows)) return false;
         HIPCHK(hipStreamSynchronize(stream));
         lbfgs_clear();
-        lb.rows = rows; lb.par = dr ? lb_params_resto(type, special, max_history, init, init_val, smin, smax) : lb_params(type, max_history, init, init_val, smin, smax); lb_forget();
+        lb.rows = rows; lb.par = dr ? lb_params_resto(d.type, d.special, d.max_history, d.init, d.init_val, d.smin, d.smax) : lb_params(d.type, d.max_history, d.init, d.init_val, d.smin, d.smax); lb_forget();
         DeviceOwner& O = own_lb;
-        const size_t nout = dr ? LB_NOUT_RESTO : LB_NOUT, ncoef = dr ? LBH_NCOEF_RESTO : LBH_NCOEF;
+        const size_t nout = lb_nout(dr ? LB_RESTO : LB_PLAIN), ncoef = dr ? LBH_NCOEF_RESTO : LBH_NCOEF;
         if (!O.zeroed(&lb.S, (size_t)rows * lb.par.slots) || !O.zeroed(&lb.Y, (size_t)rows * lb.par.slots) || !O.raw(&lb.sy, 2 * (size_t)rows) ||
             !O.raw(&lb.part, (size_t)lb.nslab() * nout) || !O.raw(&lb.T, nout) || !O.raw(&lb.coef, ncoef) ||
             !O.pinned(&lb.h, nout) || !O.pinned(&lb.hc, ncoef) || (dr && !O.raw(&lb.DR, (size_t)rows))) { lbfgs_clear(); return false; }
@@ -1538,37 +1539,25 @@ public:
     template <class F> static void lb_with_kp(int m, F&& f) {
         if (m <= 8) f(std::integral_constant<int, 8>{}); else if (m <= 16) f(std::integral_constant<int, 16>{}); else f(std::integral_constant<int, 32>{});
     }
-    // ds == nullptr: no new pair, every column comes from its slot (undo).  lr.V, lr.U must have the shape (lb.rows, m - nneg, nneg).
-    void lb_launch_form_sr1(const double* ds, const double* dy) {
-        if (lb.par.resto) {
-            lb_with_kp(lb.st.m, [&](auto kp) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_form_sr1_resto<decltype(kp)::value>), dim3((lb.rows + 255) / 256), dim3(256), 0, stream, lb.S, lb.Y, (long long)lb.rows,
-                                                                  (const double*)lb.DR, ds, dy, lb.rows, lb_ring(lb.st.m), (const double*)lb.coef, lb.st.sigma, lb.rs.eta, lb.par.special, lb.st.nneg, lr.V, lr.U, (long long)lb.rows); });
-            return;
-        }
-        lb_with_kp(lb.st.m, [&](auto kp) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_form_sr1<decltype(kp)::value>), dim3((lb.rows + 255) / 256), dim3(256), 0, stream, lb.S, lb.Y, (long long)lb.rows,
-                                                              ds, dy, lb.rows, lb_ring(lb.st.m), (const double*)lb.coef, lb.st.sigma, lb.st.nneg, lr.V, lr.U, (long long)lb.rows); });
-    }
-    void lb_launch_dots(const double* ds, const double* dy) {
-        lb_with_kp(lb.st.m, [&](auto kp) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_dots<decltype(kp)::value>), dim3(lb.nslab()), dim3(256), 0, stream, (const double*)lb.S, (const double*)lb.Y, (long long)lb.rows,
-                                                              ds, dy, lb.rows, lb_ring(lb.st.m), lb.part); });
-    }
-    void lb_launch_dots_resto(const double* ds, const double* dy) {
+    // ... and on the kind of the history (LB_PLAIN / LB_RESTO / LB_RESTO_SPECIAL): f(KP, MODE) for the current state.  Every launch passes DR, eta and
+    // special; a plain instantiation does not read them.
+    template <class F> void lb_with_kp_mode(F&& f) {
         lb_with_kp(lb.st.m, [&](auto kp) {
-            constexpr int KP = decltype(kp)::value;
-            if (lb.par.special) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_dots_resto<KP, true>), dim3(lb.nslab()), dim3(256), 0, stream, (const double*)lb.S, (const double*)lb.Y, (long long)lb.rows,
-                                                   (const double*)lb.DR, ds, dy, lb.rows, lb_ring(lb.st.m), lb.part);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_dots_resto<KP, false>), dim3(lb.nslab()), dim3(256), 0, stream, (const double*)lb.S, (const double*)lb.Y, (long long)lb.rows,
-                                    (const double*)lb.DR, ds, dy, lb.rows, lb_ring(lb.st.m), lb.part);
+            if (!lb.par.resto) f(kp, std::integral_constant<int, LB_PLAIN>{}); else if (!lb.par.special) f(kp, std::integral_constant<int, LB_RESTO>{}); else f(kp, std::integral_constant<int, LB_RESTO_SPECIAL>{});
         });
     }
+    void lb_launch_dots(const double* ds, const double* dy) {
+        lb_with_kp_mode([&](auto kp, auto mode) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_dots<decltype(kp)::value, decltype(mode)::value>), dim3(lb.nslab()), dim3(256), 0, stream, (const double*)lb.S, (const double*)lb.Y,
+                                                                     (long long)lb.rows, (const double*)lb.DR, ds, dy, lb.rows, lb_ring(lb.st.m), lb.part); });
+    }
     void lb_launch_form(const double* ds, const double* dy) {
-        if (lb.par.resto) {
-            lb_with_kp(lb.st.m, [&](auto kp) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_form_resto<decltype(kp)::value>), dim3((lb.rows + 255) / 256), dim3(256), 0, stream, lb.S, lb.Y, (long long)lb.rows,
-                                                                  (const double*)lb.DR, ds, dy, lb.rows, lb_ring(lb.st.m), (const double*)lb.coef, lb.st.sigma, lb.rs.eta, lb.par.special, lr.V, lr.U, (long long)lb.rows); });
-            return;
-        }
-        lb_with_kp(lb.st.m, [&](auto kp) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_form<decltype(kp)::value>), dim3((lb.rows + 255) / 256), dim3(256), 0, stream, lb.S, lb.Y, (long long)lb.rows,
-                                                              ds, dy, lb.rows, lb_ring(lb.st.m), (const double*)lb.coef, lb.st.sigma, lr.V, lr.U, (long long)lb.rows); });
+        lb_with_kp_mode([&](auto kp, auto mode) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_form<decltype(kp)::value, decltype(mode)::value != LB_PLAIN>), dim3((lb.rows + 255) / 256), dim3(256), 0, stream, lb.S, lb.Y, (long long)lb.rows,
+                                                                     ds, dy, lb.rows, lb_ring(lb.st.m), (const double*)lb.coef, lb.st.sigma, lr.V, lr.U, (long long)lb.rows, (const double*)lb.DR, lb.rs.eta, lb.par.special); });
+    }
+    // ds == nullptr: no new pair, every column comes from its slot (undo).  lr.V, lr.U must have the shape (lb.rows, m - nneg, nneg).
+    void lb_launch_form_sr1(const double* ds, const double* dy) {
+        lb_with_kp_mode([&](auto kp, auto mode) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lb_form_sr1<decltype(kp)::value, decltype(mode)::value != LB_PLAIN>), dim3((lb.rows + 255) / 256), dim3(256), 0, stream, lb.S, lb.Y, (long long)lb.rows,
+                                                                     ds, dy, lb.rows, lb_ring(lb.st.m), (const double*)lb.coef, lb.st.sigma, lb.st.nneg, lr.V, lr.U, (long long)lb.rows, (const double*)lb.DR, lb.rs.eta, lb.par.special); });
     }
     // installs the columns of the current state (st.m >= 1) as the low-rank update: its shape, the coefficients (BFGS: d, C, Lbar, which the transition
     // wrote to lb.hc; SR1: st.Qs, and as the split nv + nu = m moves from push to push the buffers get room for max_history columns each), the form kernel.
@@ -1605,29 +1594,52 @@ public:
         if (type) *type = lb.defined ? lb.par.type : 0; if (nneg) *nneg = sr1 ? lb.st.nneg : 0; if (can_undo) *can_undo = sr1 && lb.backup_valid ? 1 : 0;
         if (E && sr1) for (int j = 0; j < lb.st.m; ++j) E[j] = lb.st.E[j];
     }
-    // s, y: host vectors (device = false: uploaded to the staging pair) or device vectors of lb.rows.  *outcome: 0 stored and installed, 1 skipped (only the
-    // counter moved), 2 (BFGS) stored, M not positive definite.  resto: the push of a restoration-phase history (y is ypart, eta > 0); a history takes
+    // p.s, p.y: host vectors (device = false: uploaded to the staging pair) or device vectors of lb.rows.  *outcome: 0 stored and installed, 1 skipped (only
+    // the counter moved), 2 (BFGS) stored, M not positive definite.  p.resto: the push of a restoration-phase history (y is ypart, eta > 0); a history takes
     // only the pushes of its own kind.  Either way: the dots (2 m + 3, or 3 m + 6), ONE download and synchronisation, the transition, the same tail.
-    // staged (lbfgs_push_mapped): the reduced pair is already in the staging pair lb.sy, on the stream; `device` then says whose vectors the gather read.
-    bool lbfgs_push(const double* s, const double* y, bool device, int* outcome, bool resto = false, double eta = 0.0, bool staged = false) {
+    // p.len > 0: s, y are x-block vectors of len entries (host, or device), gathered through the row map into the staging pair by ONE launch in front of
+    // the dots (P^T s_full, P^T y_full, IpLimMemQuasiNewtonUpdater.cpp:323-324); the rest of the push does not know.
+    bool lbfgs_push(const LbPush& p, int* outcome) {
         DeviceGuard guard(dev);
         *outcome = 1;
-        const std::string who = std::string(resto ? "lbfgs_push_resto" : "lbfgs_push") + (staged ? "_mapped" : "");
+        const bool resto = p.resto, device = p.device, mapped = p.len > 0;
+        const std::string who = std::string(resto ? "lbfgs_push_resto" : "lbfgs_push") + (mapped ? "_mapped" : "");
         if (!ready) { if (err_.empty()) err_ = who + ": solver not set up"; return false; }
         if (!lb.defined) { err_ = who + (resto ? ": lbfgs_define_resto first" : ": lbfgs_define first"); return false; }
+        if (mapped) {
+            std::string why;
+            if (!lr_rowmap_len_check(p.len, rmap.rows > 0 ? (long long)rmap.h.back() : -1, why)) { err_ = who + ": " + why; return false; }
+            if (lb.rows != rmap.rows) { err_ = who + ": the history has not the rows of the row map"; return false; }      // (lr_rows_ok at define: cannot happen)
+        }
         if (lb.par.resto && !resto) { err_ = "lbfgs_push: this is a restoration-phase history (lbfgs_define_resto): push with lbfgs_push_resto"; return false; }
         if (!lb.par.resto && resto) { err_ = "lbfgs_push_resto: this is a plain history (lbfgs_define / lbfgs_define_sr1): push with lbfgs_push"; return false; }
-        const auto t0 = std::chrono::steady_clock::now();
         const size_t vb = (size_t)lb.rows * sizeof(double);
-        const double *ds = s, *dy = y;
-        if (staged) { ds = lb.sy; dy = lb.sy + lb.rows; }
-        else if (!device) {
-            HIPCHK(hipMemcpyAsync(lb.sy, s, vb, hipMemcpyHostToDevice, stream));
-            HIPCHK(hipMemcpyAsync(lb.sy + lb.rows, y, vb, hipMemcpyHostToDevice, stream));
+        const double *ds = p.s, *dy = p.y;
+        if (mapped) {
+            if (!device) {
+                const size_t len = (size_t)p.len;
+                if (lb.xs_cap < len) {
+                    HIPCHK(hipStreamSynchronize(stream));
+                    own_lb.free_device(lb.xs); lb.xs = nullptr; lb.xs_cap = 0;
+                    if (!own_lb.raw(&lb.xs, 2 * len)) return false;
+                    lb.xs_cap = len;
+                }
+                HIPCHK(hipMemcpyAsync(lb.xs, p.s, len * sizeof(double), hipMemcpyHostToDevice, stream));
+                HIPCHK(hipMemcpyAsync(lb.xs + lb.xs_cap, p.y, len * sizeof(double), hipMemcpyHostToDevice, stream));
+                ds = lb.xs; dy = lb.xs + lb.xs_cap;
+            }
+            hipLaunchKernelGGL(k_lr_gather2, dim3((lb.rows + 255) / 256), dim3(256), 0, stream, ds, dy, lb.rows, rmap.d, lb.sy, lb.sy + lb.rows);
+            HIPCHK(hipGetLastError());
             ds = lb.sy; dy = lb.sy + lb.rows;
         }
-        const int m0 = lb.st.m, nout = resto ? 3 * m0 + 6 : 2 * m0 + 3;
-        if (resto) lb_launch_dots_resto(ds, dy); else lb_launch_dots(ds, dy);
+        const auto t0 = std::chrono::steady_clock::now();      // (push_ms: the push behind the gather)
+        if (!mapped && !device) {
+            HIPCHK(hipMemcpyAsync(lb.sy, p.s, vb, hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemcpyAsync(lb.sy + lb.rows, p.y, vb, hipMemcpyHostToDevice, stream));
+            ds = lb.sy; dy = lb.sy + lb.rows;
+        }
+        const int m0 = lb.st.m, nout = lb_nout(resto ? LB_RESTO : LB_PLAIN, m0);
+        lb_launch_dots(ds, dy);
         hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, stream, (const double*)lb.part, lb.nslab(), 0LL, (long long)nout, nout, 1, (const double*)nullptr, lb.T);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(lb.h, lb.T, (size_t)nout * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -1637,7 +1649,7 @@ public:
         if (resto) {
             const double* q = lb.h + 3 * m0;
             const LbRestoDots d{lb.h, lb.h + m0, lb.h + 2 * m0, q[0], q[1], q[2], q[3], q[4], q[5]};
-            r = sr1 ? lb_push_sr1_resto(lb.par, lb.st, lb.rs, lb.backup, lb.rs_backup, lb.backup_valid, d, eta) : lb_push_bfgs_resto(lb.par, lb.st, lb.rs, d, eta, lb.hc);
+            r = sr1 ? lb_push_sr1_resto(lb.par, lb.st, lb.rs, lb.backup, lb.rs_backup, lb.backup_valid, d, p.eta) : lb_push_bfgs_resto(lb.par, lb.st, lb.rs, d, p.eta, lb.hc);
         } else {
             const double *sS = lb.h, *sY = lb.h + m0, ss = lb.h[2 * m0], sy = lb.h[2 * m0 + 1], yy = lb.h[2 * m0 + 2];
             r = sr1 ? lb_push_sr1(lb.par, lb.st, lb.backup, lb.backup_valid, sS, sY, ss, sy, yy) : lb_push_bfgs(lb.par, lb.st, sS, sY, ss, sy, yy, lb.hc);
@@ -1651,39 +1663,10 @@ public:
             HIPCHK(hipMemcpyAsync(lb.S + slot, ds, vb, hipMemcpyDeviceToDevice, stream));
             HIPCHK(hipMemcpyAsync(lb.Y + slot, dy, vb, hipMemcpyDeviceToDevice, stream));
         }
-        if (r != LB_PUSH_SKIPPED && device && !staged) HIPCHK(hipStreamSynchronize(stream));      // (the caller's vectors are free again when the call returns; staged: the gather that read them ended before the synchronisation above)
+        if (r != LB_PUSH_SKIPPED && device && !mapped) HIPCHK(hipStreamSynchronize(stream));      // (the caller's vectors are free again when the call returns; mapped: the gather that read them ended before the synchronisation above)
         *outcome = r;
         lb.push_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         return true;
-    }
-    // sx, yx: x-block vectors of `len` entries (host, or device): gathered through the row map into the staging pair by ONE launch (P^T s_full, P^T y_full,
-    // IpLimMemQuasiNewtonUpdater.cpp:323-324), then lbfgs_push itself on that pair -- the same dots, download, synchronisation, transition and tail.
-    bool lbfgs_push_mapped(const double* sx, const double* yx, long long len, bool device, int* outcome, bool resto, double eta) {
-        *outcome = 1;
-        const std::string who = resto ? "lbfgs_push_resto_mapped" : "lbfgs_push_mapped";
-        {
-            DeviceGuard guard(dev);
-            if (!ready) { if (err_.empty()) err_ = who + ": solver not set up"; return false; }
-            if (!lb.defined) { err_ = who + (resto ? ": lbfgs_define_resto first" : ": lbfgs_define first"); return false; }
-            std::string why;
-            if (!lr_rowmap_len_check(len, rmap.rows > 0 ? (long long)rmap.h.back() : -1, why)) { err_ = who + ": " + why; return false; }
-            if (lb.rows != rmap.rows) { err_ = who + ": the history has not the rows of the row map"; return false; }      // (lr_rows_ok at define: cannot happen)
-            const double *dsx = sx, *dyx = yx;
-            if (!device) {
-                if (lb.xs_cap < (size_t)len) {
-                    HIPCHK(hipStreamSynchronize(stream));
-                    own_lb.free_device(lb.xs); lb.xs = nullptr; lb.xs_cap = 0;
-                    if (!own_lb.raw(&lb.xs, 2 * (size_t)len)) return false;
-                    lb.xs_cap = (size_t)len;
-                }
-                HIPCHK(hipMemcpyAsync(lb.xs, sx, (size_t)len * sizeof(double), hipMemcpyHostToDevice, stream));
-                HIPCHK(hipMemcpyAsync(lb.xs + lb.xs_cap, yx, (size_t)len * sizeof(double), hipMemcpyHostToDevice, stream));
-                dsx = lb.xs; dyx = lb.xs + lb.xs_cap;
-            }
-            hipLaunchKernelGGL(k_lr_gather2, dim3((lb.rows + 255) / 256), dim3(256), 0, stream, dsx, dyx, lb.rows, rmap.d, lb.sy, lb.sy + lb.rows);
-            HIPCHK(hipGetLastError());
-        }
-        return lbfgs_push(nullptr, nullptr, device, outcome, resto, eta, true);
     }
     void lbfgs_resto_info(int* resto, int* special, double* eta) const {
         const bool on = lb.defined && lb.par.resto;
@@ -2030,19 +2013,14 @@ bool Numeric::lowrank_solve_device2(int nrhs, const double* db, int ldb, double*
 bool Numeric::lowrank_rowmap(int rows, const int32_t* idx) { return p_->lowrank_rowmap(rows, idx); }
 void Numeric::lowrank_rowmap_info(int* rows, long long* last) const { p_->lowrank_rowmap_info(rows, last); }
 void Numeric::lowrank_rowmap_copy(int32_t* idx) const { p_->lowrank_rowmap_copy(idx); }
-bool Numeric::lbfgs_push_mapped(const double* sx, const double* yx, long long len, bool device, int* outcome) { return p_->lbfgs_push_mapped(sx, yx, len, device, outcome, false, 0.0); }
-bool Numeric::lbfgs_push_resto_mapped(const double* sx, const double* ypartx, long long len, double eta, bool device, int* outcome) { return p_->lbfgs_push_mapped(sx, ypartx, len, device, outcome, true, eta); }
 bool Numeric::lowrank_clear() { DeviceGuard guard(p_->dev); if (p_->stream) (void)hipStreamSynchronize(p_->stream); p_->lowrank_clear(); return true; }
 void Numeric::lowrank_info(int* rows, int* nv, int* nu, int* current, double* update_ms) const { p_->lowrank_info(rows, nv, nu, current, update_ms); }
 long long Numeric::factor_count() const { return p_->factor_count; }
-bool Numeric::lbfgs_define(int rows, int max_history, int init, double init_val, double sigma_min, double sigma_max) { return p_->lbfgs_define(rows, max_history, init, init_val, sigma_min, sigma_max, 0); }
-bool Numeric::lbfgs_define_sr1(int rows, int max_history, int init, double init_val) { return p_->lbfgs_define(rows, max_history, init, init_val, 1e-8, 1e8, 1); }
-bool Numeric::lbfgs_define_resto(int rows, int max_history, int type, int special, int init, double init_val, double sigma_min, double sigma_max, const double* dr) { return p_->lbfgs_define(rows, max_history, init, init_val, sigma_min, sigma_max, type, dr, special); }
-bool Numeric::lbfgs_push_resto(const double* s, const double* ypart, double eta, bool device, int* outcome) { return p_->lbfgs_push(s, ypart, device, outcome, true, eta); }
+bool Numeric::lbfgs_define(const LbDefine& d) { return p_->lbfgs_define(d); }
 void Numeric::lbfgs_resto_info(int* resto, int* special, double* eta) const { p_->lbfgs_resto_info(resto, special, eta); }
 bool Numeric::lbfgs_undo(int* undone) { return p_->lbfgs_undo(undone); }
 void Numeric::lbfgs_sr1_info(int* type, int* nneg, int* can_undo, double* E) const { p_->lbfgs_sr1_info(type, nneg, can_undo, E); }
-bool Numeric::lbfgs_push(const double* s, const double* y, bool device, int* outcome) { return p_->lbfgs_push(s, y, device, outcome); }
+bool Numeric::lbfgs_push(const LbPush& p, int* outcome) { return p_->lbfgs_push(p, outcome); }
 bool Numeric::lbfgs_reset() { return p_->lbfgs_reset(); }
 bool Numeric::lbfgs_clear() { DeviceGuard guard(p_->dev); if (p_->stream) (void)hipStreamSynchronize(p_->stream); p_->lbfgs_clear(); return true; }
 void Numeric::lbfgs_info(int* rows, int* max_history, int* memory, double* sigma, int* skipped_in_a_row, double* push_ms) const { p_->lbfgs_info(rows, max_history, memory, sigma, skipped_in_a_row, push_ms); }
