@@ -158,6 +158,35 @@ def clique_kkt(sizes, sep, m_con, seed=0, delta_c=0.0):
     return kkt_from_blocks((hi, hj, hv), Sigma, (ji, jj, jv.ravel()), np.full(m_con, delta_c), nx, m_con) + (m_con,)
 
 
+def star_kkt(leaves, own, sep, hub, seed=0):
+    """A star of dense cliques: a hub clique of `hub` variables, and `leaves` leaf cliques of `own` variables of their own each plus the SAME first `sep`
+    variables of the hub.  Every leaf is a subtree of its own under the hub's front, so that front has `leaves` children: one it may take over in
+    place, the others gathered -- more children than a nested-dissection separator has.  The recipe of clique_kkt: H strictly diagonally dominant (SPD),
+    Sigma = 10^U(-3, 3); no constraint rows => inertia (n, 0, 0) exactly.  The leaves' variables come first, the hub's last."""
+    rng = np.random.default_rng(seed)
+    leaves, own, sep, hub = int(leaves), int(own), int(sep), int(hub)
+    assert leaves >= 1 and own >= 1 and 0 < sep <= hub
+    nx = leaves * own + hub
+    h0 = leaves * own                                   # first hub variable
+    hi, hj = [], []
+    for l in range(leaves):
+        idx = np.concatenate([l * own + np.arange(own), h0 + np.arange(sep)])
+        a, b = np.tril_indices(own + sep, -1)
+        keep = b < own                                  # (the pairs inside the shared variables belong to the hub clique)
+        hi.append(idx[b[keep]]); hj.append(idx[a[keep]])
+    a, b = np.tril_indices(hub, -1)
+    hi.append(h0 + b); hj.append(h0 + a)
+    hi, hj = np.concatenate(hi), np.concatenate(hj)      # upper: row < col
+    hv = rng.uniform(-1, 1, hi.shape[0])
+    diag = np.zeros(nx)
+    np.add.at(diag, hi, np.abs(hv)); np.add.at(diag, hj, np.abs(hv))
+    diag += rng.uniform(0.1, 1.0, nx)
+    hi = np.concatenate([np.arange(nx), hi]); hj = np.concatenate([np.arange(nx), hj]); hv = np.concatenate([diag, hv])
+    Sigma = 10.0 ** rng.uniform(-3, 3, nx)
+    none = np.zeros(0, dtype=np.int64)
+    return kkt_from_blocks((hi, hj, hv), Sigma, (none, none, np.zeros(0)), np.zeros(0), nx, 0) + (0,)
+
+
 def block_diag(*systems):
     """the direct sum of systems (n, row, col, val, neg): independent components in one matrix -- one elimination forest, so the fronts of all of
     them share the tree levels and the launches."""

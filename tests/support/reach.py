@@ -4,8 +4,8 @@ of the ordering or of a threshold then fails a CPU test instead of silently empt
 
 What the FACTORISATION launches is counted, not restated: the exported factor schedules ("factor.single.full" / "factor.single.opt", one record per
 launch and stream operation, built by launch_plan.cpp build_factor_schedule and walked as they are by numeric.hip) hold every launch decision once.  The
-solve-side facts -- pair_levels, pair16_levels, leafchain_solve -- still restate numeric.hip solve_sweep / solve_level: the solve walkers are the
-follow-up of the same shape.
+solve-side facts -- pair_levels, pair16_levels, leafchain_solve, and solve_reach(solver) for the fronts above 128 rows and the chain segments -- still
+restate numeric.hip solve_sweep / solve_level: the solve walkers are the follow-up of the same shape.
 
 reach(solver) is evaluated under the MI355X_KKT_DISABLE / MI355X_KKT_TUNE settings of the moment (the plan is rebuilt from the environment at every
 query), so one analysed handle gives the facts of both legs of an A/B test.  Every fact is a count (0 = not reached)."""
@@ -35,6 +35,68 @@ def plan_arrays(s):
 def plan_diff(a, b):
     """names of the arrays in which two plans differ"""
     return sorted(w for w in PLAN_ARRAYS if not np.array_equal(a[w], b[w]))
+
+
+def solve_reach(s):
+    """What the solve sweeps launch for the BIG fronts (order > 128) and the chain segments, under the MI355X_KKT_DISABLE / MI355X_KKT_TUNE of the moment:
+    numeric.hip solve_sweep / solve_level restated for the single-GPU schedule (the per-class choice of the levels outside the chain segments; the
+    segments go to k_fwd_chain / k_bwd_chain whole), with the shapes those kernels branch on.  Sets are returned as sorted lists."""
+    I = s.info()
+    nl, nsn = I.num_levels, I.num_sn
+    order = np.diff(s.symbolic(2, nsn + 1)); cols = np.diff(s.symbolic(1, nsn + 1))
+    parent, cls, level = s.symbolic(4, nsn), s.symbolic(23, nsn), s.symbolic(5, nsn)
+    grp_pos, grp_rem, alias = s.symbolic(15, nsn), s.symbolic(16, nsn), s.symbolic(17, nsn)
+    nchild = np.bincount(parent[parent >= 0], minlength=nsn)
+    gathered = nchild - (alias >= 0)                      # children whose rows are added in (the in-place child shares the vector)
+    A = {w: s.launch_plan(w).copy() for w in ("chain_segs", "chain_descs", "chain_links", "single.ptr", "single.maxm", "single.maxk", "single.last0",
+                                              "single.last1", "single.allsolo", "scalars", "path_scalars")}
+    ptr, maxk, allsolo = A["single.ptr"], A["single.maxk"], A["single.allsolo"]
+    ng = A["single.last1"] - A["single.last0"]
+    pair_solve, solve_group, lc_levels = int(A["path_scalars"][0]), int(A["path_scalars"][4]), int(A["scalars"][2])
+    segs, descs, links = A["chain_segs"].reshape(-1, 9), A["chain_descs"].reshape(-1, 6), A["chain_links"].reshape(-1, 4)
+    seg_of = np.full(nl, -1)
+    for q, (lv0, lv1, *_) in enumerate(segs):
+        seg_of[lv0:lv1 + 1] = q
+    lcs = lc_levels if (pair_solve and lc_levels > 0 and not (seg_of[:lc_levels] >= 0).any()) else 0
+    big = cls == FC_BIG
+    F = dict(fwd_solo64_levels=0, fwd_solo_levels=0, fwd_grp_levels=0, bwd_dot64_levels=0, bwd_grp_levels=0)
+    on_level = np.zeros(nsn, dtype=bool)                  # big fronts on level launches
+    for lv in range(lcs, nl):
+        if seg_of[lv] >= 0 or ptr[lv * FC_COUNT + FC_BIG + 1] == ptr[lv * FC_COUNT + FC_BIG] or ng[lv] <= 0:
+            continue
+        on_level |= big & (level == lv)
+        F["fwd_solo64_levels" if allsolo[lv] and maxk[lv] <= 64 else "fwd_solo_levels" if allsolo[lv] else "fwd_grp_levels"] += 1
+        F["bwd_dot64_levels" if not solve_group and maxk[lv] <= 64 else "bwd_grp_levels"] += 1
+    F["solve_group"] = solve_group
+    F["segments"], F["chains"], F["chain_levels"] = len(segs), len(descs), int((seg_of >= 0).sum())
+    F["chain_fronts"] = len(links); F["chain_big_fronts"] = int(big[links[:, 0]].sum()) if len(links) else 0
+    F["link_widths"] = sorted({int(x) for x in links[:, 1]})
+    F["max_nlinks"] = int(descs[:, 1].max()) if len(descs) else 0
+    F["chain_shapes"] = sorted({(int(d[1]), int(d[2])) for d in descs if big[d[4]]})      # (links, tail) of the chains that start at a big front
+    F["tails"] = sorted({int(x) for x in descs[:, 2]})
+    F["inits"] = sorted({int(x) for x in descs[:, 5]})
+    F["max_gathered_chain_head"] = int(gathered[descs[:, 4]].max()) if len(descs) else 0
+    F["max_gathered_level"] = int(gathered[on_level].max()) if on_level.any() else 0
+    F["level_widths"] = sorted({int(x) for x in cols[on_level]})
+    F["level_tails"] = sorted({int(x) for x in (order - cols)[on_level]})
+    # solve units: per link, or (solve_group) per chain group, handled at the group's last link
+    unit = big & ((grp_rem == 0) | (solve_group == 0))
+    ulinks = np.where(solve_group != 0, grp_pos + 1, 1)
+    ucols = cols.copy()
+    if solve_group:
+        for f in np.nonzero(unit)[0]:
+            cur, tot = f, 0
+            for _ in range(int(grp_pos[f]) + 1):
+                tot += int(cols[cur]); cur = alias[cur]
+            ucols[f] = tot
+    F["unit_max_links"] = int(ulinks[unit].max()) if unit.any() else 0
+    F["unit_max_cols"] = int(ucols[unit].max()) if unit.any() else 0
+    F["unit_shapes"] = sorted({(int(ulinks[f]), int(ucols[f])) for f in np.nonzero(unit)[0]})
+    F["upd_mod256"] = sorted({int(x) % 256 for x in (order - cols)[big]})
+    F["big_fronts"] = int(big.sum())
+    F["big_orders"] = (int(order[big].min()), int(order[big].max())) if big.any() else (0, 0)
+    F["maxsupernode"] = int(I.maxsupernode)
+    return F
 
 
 def reach(s):

@@ -49,3 +49,24 @@ def test_clique_generator_has_the_structure_and_the_inertia_it_was_built_for():
     K = kktgen.to_scipy(n, r, c, v).toarray()
     assert n == a[0] + b[0] and neg == a[4] + b[4] == int((np.linalg.eigvalsh(K) < 0).sum())
     assert not K[:a[0], a[0]:].any() and np.array_equal(K[:a[0], :a[0]], kktgen.to_scipy(*a[:4]).toarray())
+
+
+def test_star_generator_has_the_structure_and_the_inertia_it_was_built_for():
+    """leaf cliques that share the same variables of a hub clique: symmetric pattern, every clique dense, the leaves coupled through the hub only,
+    inertia (n, 0, 0) by LAPACK's eigenvalues"""
+    leaves, own, sep, hub = 4, 9, 5, 8
+    n, r, c, v, neg = kktgen.star_kkt(leaves, own, sep, hub, seed=3)
+    assert n == leaves * own + hub and neg == 0 and np.array_equal(v, kktgen.star_kkt(leaves, own, sep, hub, seed=3)[3])
+    K = kktgen.to_scipy(n, r, c, v).toarray()
+    w = np.linalg.eigvalsh(K)
+    assert np.array_equal(K, K.T) and int((w < 0).sum()) == 0 and w.min() > 1e-8
+    P = K != 0
+    h0 = leaves * own
+    assert P[h0:, h0:].all()
+    for l in range(leaves):
+        mine = np.r_[l * own:(l + 1) * own]
+        assert P[np.ix_(mine, mine)].all() and P[np.ix_(mine, np.r_[h0:h0 + sep])].all()
+        assert not P[np.ix_(mine, np.r_[h0 + sep:n])].any()
+        others = np.setdiff1d(np.r_[0:h0], mine)
+        assert not P[np.ix_(mine, others)].any()
+    assert int(np.tril(P, -1).sum()) == leaves * (own * (own - 1) // 2 + own * sep) + hub * (hub - 1) // 2
