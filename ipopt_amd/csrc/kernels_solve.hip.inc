@@ -33,6 +33,112 @@ __global__ void k_refine_spmv(DevView V)
 __global__ void k_save_rhs(DevView V) { for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < V.n; i += gridDim.x * blockDim.x) V.bw[i] = V.xw[i]; }
 __global__ void k_refine_finish(DevView V) { for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < V.n; i += gridDim.x * blockDim.x) V.xw[i] += V.xacc[i]; }
 
+// ------------------------------------------------------------------------------------------------
+// Steps of a front that several sweep kernels take: ONE definition each.  The kernels that share a step agree bit for bit because they call the same
+// expression -- same operand order inside each product and sum, same number and pairing of partial accumulators, same guards.
+// ------------------------------------------------------------------------------------------------
+// z = D^{-1} y over 1x1 and 2x2 pivots is NOT among them: every kernel spells it out.  Moved into a shared function, with the same expressions, the step
+// gave other bits on tests/support/midfix.py hostile16, the one fixture with 2x2 pivots (which product of a * b + c * d goes into the fma is the compiler's
+// choice, and it chose differently there).  Shared is the load of what the step needs, for the kernels that request everything
+// the front record gives before they wait for anything: pivot type, the row's diagonal entry of D^{-1}, the off-diagonal entries towards the next and
+// the previous row.
+struct PivD { int pt; double dq, oq, oq1; };
+__device__ __forceinline__ PivD ld_pivd(const DevView& V, const int c0, const int j, const bool on)
+{
+    PivD D = {1, 0.0, 0.0, 0.0};
+    if (on) { D.pt = V.ptype[c0 + j]; D.dq = V.dinv[c0 + j]; D.oq = V.doff[c0 + j]; D.oq1 = j > 0 ? V.doff[c0 + j - 1] : 0.0; }
+    return D;
+}
+// ys = L11^{-1} bp with the stored k x k inverse (column-major, lower triangle), a workgroup of 256: 4 threads per row (columns part, part + 4, ...),
+// combined by two quad shuffles
+__device__ __forceinline__ void minv_rows_quad(const double* Mg, const int k, const double* bp, double* ys, const int tid)
+{
+    const int part = tid & 3;
+    for (int q = tid >> 2; q < k; q += 64) {
+        double a = 0.0;
+        int p = part;
+        for (; p + 12 <= q; p += 16) {
+            const double m0 = Mg[q + (size_t)p * k], m1 = Mg[q + (size_t)(p + 4) * k], m2 = Mg[q + (size_t)(p + 8) * k], m3 = Mg[q + (size_t)(p + 12) * k];
+            a += m0 * bp[p] + m1 * bp[p + 4] + m2 * bp[p + 8] + m3 * bp[p + 12];
+        }
+        for (; p <= q; p += 4) a += Mg[q + (size_t)p * k] * bp[p];
+        a += __shfl_xor(a, 1); a += __shfl_xor(a, 2);
+        if (part == 0) ys[q] = a;
+    }
+}
+// x = P^T L11^{-T} ws, written un-permuted to xw: x_p = sum_{q >= p} Minv(q,p) w_q, 4 threads per column (contiguous quarter-interleaved walk), combined by shuffles
+__device__ __forceinline__ void minv_cols_quad(const DevView& V, const double* Mg, const int c0, const int k, const double* ws, const int tid)
+{
+    const int part = tid & 3;
+    for (int p = tid >> 2; p < k; p += 64) {
+        double a = 0.0;
+        int q = p + part;
+        for (; q + 12 < k; q += 16) {
+            const double m0 = Mg[q + (size_t)p * k], m1 = Mg[q + 4 + (size_t)p * k], m2 = Mg[q + 8 + (size_t)p * k], m3 = Mg[q + 12 + (size_t)p * k];
+            a += m0 * ws[q] + m1 * ws[q + 4] + m2 * ws[q + 8] + m3 * ws[q + 12];
+        }
+        for (; q < k; q += 4) a += Mg[q + (size_t)p * k] * ws[q];
+        a += __shfl_xor(a, 1); a += __shfl_xor(a, 2);
+        if (part == 0) V.xw[c0 + V.lperm[c0 + p]] = a;
+    }
+}
+// The 16-entry register forms of the two (k <= 64): thread (row, part) holds entries part, part + 4, ... of row `row` of the inverse (columns <= row),
+// thread (col, part) the entries col + part, col + part + 4, ... of column `col` (rows < k); zeros elsewhere.
+__device__ __forceinline__ void ld_minv_row16(double (&mreg)[16], const double* Mg, const int k, const int tid)
+{
+    const int row = (tid >> 2) & 63, part = tid & 3;
+#pragma unroll
+    for (int u = 0; u < 16; ++u) { const int p = part + 4 * u; mreg[u] = (row < k && p <= row) ? Mg[row + (size_t)p * k] : 0.0; }      // Minv(row, p)
+}
+__device__ __forceinline__ void ld_minv_col16(double (&mreg)[16], const double* Mg, const int k, const int col, const int part)
+{
+#pragma unroll
+    for (int u = 0; u < 16; ++u) { const int q = col + part + 4 * u; mreg[u] = (col < k && q < k) ? Mg[q + (size_t)col * k] : 0.0; }      // Minv(q, col), q >= col
+}
+// Their product with the 64-entry LDS vector x, entry u against x[(o + 4 u) mod 64] (every entry of x must be a number: zeros of v meet it).  TWO shapes,
+// different bits, and each kernel keeps its own: the level kernels (k_fwd_solo64, k_bwd_fin64) sum in one accumulator and combine the quad by shuffles;
+// the chain sweeps (k_fwd_chain, k_bwd_chain: the steps along the chain and the final solve) sum the even and the odd entries apart, and combine by DPP
+// where they use the sum (quad_sum_dpp).
+__device__ __forceinline__ double quad_dot16(const double (&v)[16], const double* x, const int o)
+{
+    double a = 0.0;
+#pragma unroll
+    for (int u = 0; u < 16; ++u) a += v[u] * x[(o + 4 * u) & 63];
+    a += __shfl_xor(a, 1); a += __shfl_xor(a, 2);
+    return a;
+}
+__device__ __forceinline__ void quad_dot16_eo(const double (&v)[16], const double* x, const int o, double& a0, double& a1)
+{
+    a0 = 0.0; a1 = 0.0;
+#pragma unroll
+    for (int u = 0; u < 16; u += 2) { a0 += v[u] * x[(o + 4 * u) & 63]; a1 += v[u + 1] * x[(o + 4 * u + 4) & 63]; }
+}
+__device__ __forceinline__ double quad_sum_dpp(double t) { t += dpp_f64<0xB1>(t); t += dpp_f64<0x4E>(t); return t; }      // the 4 lanes of a row / column are a DPP quad
+// the sum over the nch row blocks of the partial sums of column col (rows of gcols entries), in four accumulators
+__device__ __forceinline__ double part_sum4(const double* part, const int nch, const int gcols, const int col)
+{
+    double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
+    int c = 0;
+    for (; c + 3 < nch; c += 4) { t0 += part[(size_t)c * gcols + col]; t1 += part[(size_t)(c + 1) * gcols + col];
+                                  t2 += part[(size_t)(c + 2) * gcols + col]; t3 += part[(size_t)(c + 3) * gcols + col]; }
+    for (; c < nch; ++c) t0 += part[(size_t)c * gcols + col];
+    return (t0 + t1) + (t2 + t3);
+}
+// 64 update rows per workgroup of 256 (one per lane, Lg: the lane's row of the panel), the k columns dealt to the 4 wavefronts in blocks of 8 (8 coalesced
+// loads in flight per lane): t0 += over the even, t1 += over the odd columns of this wavefront's blocks.  The 4 wavefronts' t0 + t1 go to red[wave][lane]
+// and are combined in fixed order (red4).
+__device__ __forceinline__ void upd_row_acc(const double* Lg, const int ldp, const int k, const double* y, const int wave, double& t0, double& t1)
+{
+    for (int p = wave * 8; p < k; p += 32) {
+        double l[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) l[u] = (p + u < k) ? Lg[(size_t)(p + u) * ldp] : 0.0;
+#pragma unroll
+        for (int u = 0; u < 8; u += 2) { t0 += l[u] * ((p + u < k) ? y[p + u] : 0.0); t1 += l[u + 1] * ((p + u + 1 < k) ? y[p + u + 1] : 0.0); }
+    }
+}
+__device__ __forceinline__ double red4(const double (&red)[4][64], const int lane) { return (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]); }
+
 // forward: y = L11^{-1} P b for the pivot rows (a k x k mat-vec with the stored inverse: no substitution chain),
 // z = D^{-1} y, and the contribution  c = (children) - L21 y  for the ancestors is left in cvec (the parent
 // gathers it: no atomics, deterministic).  One workgroup per front of order <= 128 (BIG fronts: k_fwd_grp).
@@ -42,7 +148,7 @@ __global__ __launch_bounds__(NT) void k_fwd(DevView V, int list_off, int top_mod
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int tid = threadIdx.x;
     const FrontMeta M = V.fmeta[list_off + blockIdx.x];
-    const int s = M.s, c0 = M.c0, k = M.k, r0 = M.r0, m = M.m; (void)s; (void)c0; (void)r0; (void)k;
+    const int c0 = M.c0, k = M.k, m = M.m;
     double* xp = reinterpret_cast<double*>(smem_raw);   // k   pivot rows (original local order)
     double* ys = xp + k;                                // k
     double* bp = ys + k;                                // k   pivot rows in pivot order
@@ -50,14 +156,13 @@ __global__ __launch_bounds__(NT) void k_fwd(DevView V, int list_off, int top_mod
     for (int i = tid; i < k; i += NT) xp[i] = V.xw[c0 + i];
     for (int i = k + tid; i < m; i += NT) xu[i - k] = 0.0;
     if (top_mode && V.top_rhs) {
-        const double* tr = V.top_rhs + V.top_rhs_off[s];
+        const double* tr = V.top_rhs + V.top_rhs_off[M.s];
         __syncthreads();
         for (int i = tid; i < m; i += NT) { if (i < k) xp[i] += tr[i]; else xu[i - k] += tr[i]; }
     }
     __syncthreads();
     for (int cp = M.ch0; cp < M.ch1; ++cp) {
         const ChildMeta Cm = V.cmeta[cp];
-        const int ch = Cm.ch; (void)ch;
         if (top_mode && V.top_rhs && Cm.owner >= 0) continue;
         const int base = Cm.relbase, mc = Cm.mc;
         for (int t = tid; t < mc; t += NT) {
@@ -106,7 +211,7 @@ __global__ __launch_bounds__(NT) void k_bwd(DevView V, int list_off)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr int NW = NT / 64;
     const FrontMeta M = V.fmeta[list_off + blockIdx.x];
-    const int s = M.s, c0 = M.c0, k = M.k, r0 = M.r0, m = M.m; (void)s; (void)c0; (void)r0; (void)k;
+    const int c0 = M.c0, k = M.k, r0 = M.r0, m = M.m;
     double* ws = reinterpret_cast<double*>(smem_raw);   // k
     double* xu = ws + k;                                // m-k gathered ancestor values (LDS classes)
     for (int i = k + tid; i < m; i += NT) xu[i - k] = V.xw[V.sn_rows[r0 + i]];
@@ -337,6 +442,78 @@ __global__ __launch_bounds__(64) void k_bwd_mid(DevView V, int list_off)
 // then the children's contributions (forward) or the ancestors' solution entries (backward), then arithmetic.  The sweeps are
 // bound by (dependent round trips) x (fronts / resident wavefronts), not by bytes.  KP = compile-time bound on the pivot count.
 // ------------------------------------------------------------------------------------------------
+// The body of ONE front on its LPF lanes (lane li; xs, bp, ys, xus, w: the front's rows of the LDS arrays), called once per front by the pair kernels and
+// once per link by the leaf chains (k_fwd_leafchain / k_bwd_leafchain): one definition, so the two agree bit for bit.  The gather of the children between
+// the forward phases stays with each kernel: four children from memory there, one from LDS here.  So do the three guarded loads that open phase 1 (the
+// lane's right-hand side entry, pivot position and D): written out in the kernel they stay three branches, out of a shared function the compiler merges
+// them into one, which costs k_fwd_pair two registers.
+// forward, phase 1: the lane's row of L11^{-1} (a pivot lane) or of the panel (an update lane)
+template <int KP>
+__device__ __forceinline__ void small_ld_rows(double (&mrow)[KP], double (&lrow)[KP], const double* Mg, const double* Lg, const int k, const int m, const int ldp, const int li)
+{
+    const bool piv = li < k, upd = li >= k && li < m;
+#pragma unroll
+    for (int p = 0; p < KP; ++p) {
+        mrow[p] = (piv && p <= li) ? Mg[li + (size_t)p * k] : 0.0;
+        lrow[p] = (upd && p < k) ? Lg[li + (size_t)p * ldp] : 0.0;
+    }
+}
+// forward, phase 3, behind the gather into xs: y (returned, and left in ys), the update row's  xs - L21 y  handed to put(value) on the update lanes.
+// z = D^{-1} y stays with each kernel, as every kernel's does (see PivD).
+template <int KP, int LPF, class Put>
+__device__ __forceinline__ double small_fwd_solve(const int k, const int m, const int li, const int lpv, const double (&mrow)[KP], const double (&lrow)[KP], const double* xs, double* bp, double* ys, Put put)
+{
+    const bool piv = li < k, upd = li >= k && li < m;
+    bp[li] = piv ? xs[lpv] : 0.0;
+    __syncthreads();
+    double y = 0.0;
+#pragma unroll
+    for (int p = 0; p < KP; ++p) y += mrow[p] * bp[p];
+    ys[li] = piv ? y : 0.0;
+    if (li == 0) ys[LPF] = 0.0;
+    __syncthreads();
+    if (upd) {
+        double t = 0.0;
+#pragma unroll
+        for (int p = 0; p < KP; ++p) t += lrow[p] * ys[p];
+        put(xs[li] - t);
+    }
+    return y;
+}
+// backward, all three phases: the front record's loads, the ancestors' solution entries, arithmetic
+template <int KP, int LPF, class Rec>
+__device__ __forceinline__ void small_bwd(const DevView& V, const Rec& R, const int k, const int m, const int li, double* xus, double* w)
+{
+    const int c0 = R.c0, r0 = R.r0, ldp = R.ldp;
+    const bool piv = li < k, upd = li >= k && li < m;
+    // ---- phase 1 ----
+    const double zbv = piv ? V.zb[c0 + li] : 0.0;
+    const int lpv = piv ? V.lperm[c0 + li] : 0;
+    const int ridx = upd ? V.sn_rows[r0 + li] : 0;
+    const double* Mg = V.minv + R.minv_off;
+    const double* Lg = V.L + R.panel_off;
+    double mcol[KP], lcol[LPF];
+#pragma unroll
+    for (int q = 0; q < KP; ++q) mcol[q] = (piv && li + q < k) ? Mg[li + q + (size_t)li * k] : 0.0;      // Minv(li + q, li)
+#pragma unroll
+    for (int i = 0; i < LPF; ++i) lcol[i] = (piv && k + i < m) ? Lg[k + i + (size_t)li * ldp] : 0.0;        // L(k + i, li)
+    // ---- phase 2: the ancestors' solution entries ----
+    xus[li] = upd ? V.xw[ridx] : 0.0;
+    __syncthreads();
+    // ---- phase 3 ----
+    double t = 0.0;
+#pragma unroll
+    for (int i = 0; i < LPF; ++i) t += lcol[i] * xus[(k + i) & (LPF - 1)];
+    w[li] = piv ? zbv - t : 0.0;
+    __syncthreads();
+    if (piv) {
+        double a = 0.0;
+#pragma unroll
+        for (int q = 0; q < KP; ++q) a += mcol[q] * w[(li + q) & (LPF - 1)];
+        V.xw[c0 + lpv] = a;
+    }
+}
+
 template <int KP, int LPF = 32>      // LPF lanes per front: 32 (order <= 32, two fronts per wavefront) or 16 (levels whose fronts all have order <= 16: four)
 __global__ __launch_bounds__(64) void k_fwd_pair(DevView V, int list_off, int nfronts)
 {
@@ -349,19 +526,12 @@ __global__ __launch_bounds__(64) void k_fwd_pair(DevView V, int list_off, int nf
     const int c0 = Mp->c0, k = act ? Mp->k : 0, m = act ? Mp->m : 0, ch0 = Mp->ch0, ch1 = act ? Mp->ch1 : Mp->ch0, ldp = Mp->ldp;
     const long long cvo = Mp->cv;
     // ---- phase 1: depends on the front record only ----
-    const bool piv = li < k, upd = li >= k && li < m;
+    const bool piv = li < k;
     const double xwv = piv ? V.xw[c0 + li] : 0.0;
     const int lpv = piv ? V.lperm[c0 + li] : 0;
-    int pt = 1; double dq = 0.0, oq = 0.0, oq1 = 0.0;
-    if (piv) { pt = V.ptype[c0 + li]; dq = V.dinv[c0 + li]; oq = V.doff[c0 + li]; oq1 = li > 0 ? V.doff[c0 + li - 1] : 0.0; }
-    const double* Mg = V.minv + Mp->minv_off;
-    const double* Lg = V.L + Mp->panel_off;
+    const PivD D = ld_pivd(V, c0, li, piv);
     double mrow[KP], lrow[KP];
-#pragma unroll
-    for (int p = 0; p < KP; ++p) {
-        mrow[p] = (piv && p <= li) ? Mg[li + (size_t)p * k] : 0.0;
-        lrow[p] = (upd && p < k) ? Lg[li + (size_t)p * ldp] : 0.0;
-    }
+    small_ld_rows(mrow, lrow, V.minv + Mp->minv_off, V.L + Mp->panel_off, k, m, ldp, li);
     int cmc[4], crel[4]; long long ccv[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -383,25 +553,12 @@ __global__ __launch_bounds__(64) void k_fwd_pair(DevView V, int list_off, int nf
         if (li < mc) xs[h][V.rel[V.cmeta[cp].relbase + li]] += V.cvec[V.cmeta[cp].cvbase + li];
         __syncthreads();
     }
-    bp[h][li] = piv ? xs[h][lpv] : 0.0;
-    __syncthreads();
-    double y = 0.0;
-#pragma unroll
-    for (int p = 0; p < KP; ++p) y += mrow[p] * bp[h][p];
-    ys[h][li] = piv ? y : 0.0;
-    if (li == 0) ys[h][LPF] = 0.0;
-    __syncthreads();
-    if (upd) {
-        double t = 0.0;
-#pragma unroll
-        for (int p = 0; p < KP; ++p) t += lrow[p] * ys[h][p];
-        V.cvec[cvo + li] = xs[h][li] - t;
-    }
+    const double y = small_fwd_solve<KP, LPF>(k, m, li, lpv, mrow, lrow, xs[h], bp[h], ys[h], [&](const double r) { V.cvec[cvo + li] = r; });
     if (piv) {
         double z;
-        if (pt == 1) z = y * dq;
-        else if (pt == 2) z = dq * y + oq * ys[h][li + 1];
-        else z = oq1 * ys[h][li - 1] + dq * y;
+        if (D.pt == 1) z = y * D.dq;
+        else if (D.pt == 2) z = D.dq * y + D.oq * ys[h][li + 1];
+        else z = D.oq1 * ys[h][li - 1] + D.dq * y;
         V.zb[c0 + li] = z;
     }
 }
@@ -414,40 +571,14 @@ __global__ __launch_bounds__(64) void k_bwd_pair(DevView V, int list_off, int nf
     const int f = FPW * (int)blockIdx.x + h;
     const bool act = f < nfronts;
     const FrontMeta* Mp = V.fmeta + list_off + (act ? f : 0);
-    const int c0 = Mp->c0, k = act ? Mp->k : 0, m = act ? Mp->m : 0, r0 = Mp->r0, ldp = Mp->ldp;
-    const bool piv = li < k, upd = li >= k && li < m;
-    // ---- phase 1 ----
-    const double zbv = piv ? V.zb[c0 + li] : 0.0;
-    const int lpv = piv ? V.lperm[c0 + li] : 0;
-    const int ridx = upd ? V.sn_rows[r0 + li] : 0;
-    const double* Mg = V.minv + Mp->minv_off;
-    const double* Lg = V.L + Mp->panel_off;
-    double mcol[KP], lcol[LPF];
-#pragma unroll
-    for (int q = 0; q < KP; ++q) mcol[q] = (piv && li + q < k) ? Mg[li + q + (size_t)li * k] : 0.0;      // Minv(li + q, li)
-#pragma unroll
-    for (int i = 0; i < LPF; ++i) lcol[i] = (piv && k + i < m) ? Lg[k + i + (size_t)li * ldp] : 0.0;        // L(k + i, li)
-    // ---- phase 2: the ancestors' solution entries ----
-    xus[h][li] = upd ? V.xw[ridx] : 0.0;
-    __syncthreads();
-    // ---- phase 3 ----
-    double t = 0.0;
-#pragma unroll
-    for (int i = 0; i < LPF; ++i) t += lcol[i] * xus[h][(k + i) & (LPF - 1)];
-    w[h][li] = piv ? zbv - t : 0.0;
-    __syncthreads();
-    if (piv) {
-        double a = 0.0;
-#pragma unroll
-        for (int q = 0; q < KP; ++q) a += mcol[q] * w[h][(li + q) & (LPF - 1)];
-        V.xw[c0 + lpv] = a;
-    }
+    small_bwd<KP, LPF>(V, *Mp, act ? Mp->k : 0, act ? Mp->m : 0, li, xus[h], w[h]);
 }
 
 // ------------------------------------------------------------------------------------------------
 // LEAF CHAINS in the sweeps (see k_leaf_chain): a 16-lane row walks its chain -- forward from the leaf up, the contribution vector of a link handed to
 // the next one through LDS (only the last link's goes to memory), backward from the top link down (a link reads the entries its ancestors INSIDE the chain
-// have just stored: same CU, a barrier in between) -- one launch per sweep for all the levels of the chains.  Arithmetic of k_fwd_pair / k_bwd_pair<16, 16>.
+// have just stored: same CU, a barrier in between) -- one launch per sweep for all the levels of the chains.  A link's body is that of a front of
+// k_fwd_pair / k_bwd_pair<16, 16>: small_ld_rows, small_fwd_solve, small_bwd.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void k_fwd_leafchain(DevView V, int nchains)
 {
@@ -469,19 +600,12 @@ __global__ __launch_bounds__(64) void k_fwd_leafchain(DevView V, int nchains)
         const LeafLink K1 = Lc[min(t + 1, nlc - 1)];          // (the next link's record: on its way while this link is solved)
         const int c0 = K0.c0, k = act ? K0.k : 0, m = act ? K0.m : 0, ldp = K0.ldp;
         const long long cvo = K0.cv;
-        const bool piv = li < k, upd = li >= k && li < m;
+        const bool piv = li < k;
         const double xwv = piv ? V.xw[c0 + li] : 0.0;
         const int lpv = piv ? V.lperm[c0 + li] : 0;
-        int pt = 1; double dq = 0.0, oq = 0.0, oq1 = 0.0;
-        if (piv) { pt = V.ptype[c0 + li]; dq = V.dinv[c0 + li]; oq = V.doff[c0 + li]; oq1 = li > 0 ? V.doff[c0 + li - 1] : 0.0; }
-        const double* Mg = V.minv + K0.minv_off;
-        const double* Lg = V.L + K0.panel_off;
+        const PivD D = ld_pivd(V, c0, li, piv);
         double mrow[KP], lrow[KP];
-#pragma unroll
-        for (int p = 0; p < KP; ++p) {
-            mrow[p] = (piv && p <= li) ? Mg[li + (size_t)p * k] : 0.0;
-            lrow[p] = (upd && p < k) ? Lg[li + (size_t)p * ldp] : 0.0;
-        }
+        small_ld_rows(mrow, lrow, V.minv + K0.minv_off, V.L + K0.panel_off, k, m, ldp, li);
         // the child (the previous link): its contribution vector is in cvs
         const int mc = (act && t > 0) ? mprev - kprev : 0;
         const int tg = li < mc ? V.rel[relprev + li] : -1;
@@ -490,27 +614,12 @@ __global__ __launch_bounds__(64) void k_fwd_leafchain(DevView V, int nchains)
         __syncthreads();
         if (tg >= 0) xs[h][tg] += cv;
         __syncthreads();
-        bp[h][li] = piv ? xs[h][lpv] : 0.0;
-        __syncthreads();
-        double y = 0.0;
-#pragma unroll
-        for (int p = 0; p < KP; ++p) y += mrow[p] * bp[h][p];
-        ys[h][li] = piv ? y : 0.0;
-        if (li == 0) ys[h][LPF] = 0.0;
-        __syncthreads();
-        if (upd) {
-            double tt = 0.0;
-#pragma unroll
-            for (int p = 0; p < KP; ++p) tt += lrow[p] * ys[h][p];
-            const double r = xs[h][li] - tt;
-            cvs[h][li - k] = r;
-            if (t == nl - 1) V.cvec[cvo + li] = r;
-        }
+        const double y = small_fwd_solve<KP, LPF>(k, m, li, lpv, mrow, lrow, xs[h], bp[h], ys[h], [&](const double r) { cvs[h][li - k] = r; if (t == nl - 1) V.cvec[cvo + li] = r; });
         if (piv) {
             double z;
-            if (pt == 1) z = y * dq;
-            else if (pt == 2) z = dq * y + oq * ys[h][li + 1];
-            else z = oq1 * ys[h][li - 1] + dq * y;
+            if (D.pt == 1) z = y * D.dq;
+            else if (D.pt == 2) z = D.dq * y + D.oq * ys[h][li + 1];
+            else z = D.oq1 * ys[h][li - 1] + D.dq * y;
             V.zb[c0 + li] = z;
         }
         __syncthreads();
@@ -535,31 +644,8 @@ __global__ __launch_bounds__(64) void k_bwd_leafchain(DevView V, int nchains)
         const int t = nl - 1 - u;                         // the top link first
         const bool act = t >= 0;
         const LeafLink K1 = Lc[max(t - 1, 0)];            // (the next link's record: on its way while this link is solved)
-        const int c0 = K0.c0, k = act ? K0.k : 0, m = act ? K0.m : 0, r0 = K0.r0, ldp = K0.ldp;
-        const bool piv = li < k, upd = li >= k && li < m;
-        const double zbv = piv ? V.zb[c0 + li] : 0.0;
-        const int lpv = piv ? V.lperm[c0 + li] : 0;
-        const int ridx = upd ? V.sn_rows[r0 + li] : 0;
-        const double* Mg = V.minv + K0.minv_off;
-        const double* Lg = V.L + K0.panel_off;
-        double mcol[KP], lcol[LPF];
-#pragma unroll
-        for (int q = 0; q < KP; ++q) mcol[q] = (piv && li + q < k) ? Mg[li + q + (size_t)li * k] : 0.0;
-#pragma unroll
-        for (int i = 0; i < LPF; ++i) lcol[i] = (piv && k + i < m) ? Lg[k + i + (size_t)li * ldp] : 0.0;
-        xus[h][li] = upd ? V.xw[ridx] : 0.0;              // (ancestors inside the chain: stored by this row one iteration ago, barrier below)
-        __syncthreads();
-        double tt = 0.0;
-#pragma unroll
-        for (int i = 0; i < LPF; ++i) tt += lcol[i] * xus[h][(k + i) & (LPF - 1)];
-        w[h][li] = piv ? zbv - tt : 0.0;
-        __syncthreads();
-        if (piv) {
-            double a = 0.0;
-#pragma unroll
-            for (int q = 0; q < KP; ++q) a += mcol[q] * w[h][(li + q) & (LPF - 1)];
-            V.xw[c0 + lpv] = a;
-        }
+        // (ancestors inside the chain: their entries of xw were stored by this row one iteration ago, barrier below)
+        small_bwd<KP, LPF>(V, K0, act ? K0.k : 0, act ? K0.m : 0, li, xus[h], w[h]);
         __syncthreads();
         K0 = K1;
     }
@@ -609,22 +695,7 @@ __global__ __launch_bounds__(256) void k_fwd_grp(DevView V, int list_off, int to
         const int rem = M.gcols - done;
         for (int p = tid; p < k; p += 256) { const int lp = V.lperm[c0 + p]; bp[p] = V.xw[c0 + lp] + cv[lp]; }
         __syncthreads();
-        const double* Mg = V.minv + G.minv_off;
-        {   // y = Minv (P b): 4 threads per row (columns p = part, part + 4, ...), combined through LDS
-            const int q = tid >> 2, part = tid & 3;
-            double a = 0.0;
-            for (int q2 = q; q2 < k; q2 += 64) {
-                a = 0.0;
-                int p = part;
-                for (; p + 12 <= q2; p += 16) {
-                    const double m0 = Mg[q2 + (size_t)p * k], m1 = Mg[q2 + (size_t)(p + 4) * k], m2 = Mg[q2 + (size_t)(p + 8) * k], m3 = Mg[q2 + (size_t)(p + 12) * k];
-                    a += m0 * bp[p] + m1 * bp[p + 4] + m2 * bp[p + 8] + m3 * bp[p + 12];
-                }
-                for (; p <= q2; p += 4) a += Mg[q2 + (size_t)p * k] * bp[p];
-                a += __shfl_xor(a, 1); a += __shfl_xor(a, 2);
-                if (part == 0) ys[q2] = a;
-            }
-        }
+        minv_rows_quad(V.minv + G.minv_off, k, bp, ys, tid);
         __syncthreads();
         for (int q = tid; q < k; q += 256) {
             const int pt = V.ptype[c0 + q];
@@ -668,21 +739,7 @@ __global__ __launch_bounds__(256) void k_fwd_solo(DevView V, int list_off)
     double* cv = V.cvec + M.cv;
     for (int p = tid; p < k; p += 256) { const int lp = V.lperm[c0 + p]; bp[p] = V.xw[c0 + lp] + (M.solo == 1 ? cv[lp] : 0.0); }
     __syncthreads();
-    const double* Mg = V.minv + M.minv_off;
-    {
-        const int part = tid & 3;
-        for (int q = tid >> 2; q < k; q += 64) {
-            double a = 0.0;
-            int p = part;
-            for (; p + 12 <= q; p += 16) {
-                const double m0 = Mg[q + (size_t)p * k], m1 = Mg[q + (size_t)(p + 4) * k], m2 = Mg[q + (size_t)(p + 8) * k], m3 = Mg[q + (size_t)(p + 12) * k];
-                a += m0 * bp[p] + m1 * bp[p + 4] + m2 * bp[p + 8] + m3 * bp[p + 12];
-            }
-            for (; p <= q; p += 4) a += Mg[q + (size_t)p * k] * bp[p];
-            a += __shfl_xor(a, 1); a += __shfl_xor(a, 2);
-            if (part == 0) ys[q] = a;
-        }
-    }
+    minv_rows_quad(V.minv + M.minv_off, k, bp, ys, tid);
     __syncthreads();
     if (rb < 0) {
         for (int q = tid; q < k; q += 256) {
@@ -697,19 +754,12 @@ __global__ __launch_bounds__(256) void k_fwd_solo(DevView V, int list_off)
     }
     const int i = k + rb * 64 + lane;
     const bool ok = i < m;
-    const double* Lg = V.L + M.panel_off + (ok ? i : k);
     double t0 = 0.0, t1 = 0.0;
-    for (int p = wave * 8; p < k; p += 32) {
-        double l[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) l[u] = (p + u < k) ? Lg[(size_t)(p + u) * M.ldp] : 0.0;
-#pragma unroll
-        for (int u = 0; u < 8; u += 2) { t0 += l[u] * ((p + u < k) ? ys[p + u] : 0.0); t1 += l[u + 1] * ((p + u + 1 < k) ? ys[p + u + 1] : 0.0); }
-    }
+    upd_row_acc(V.L + M.panel_off + (ok ? i : k), M.ldp, k, ys, wave, t0, t1);
     red[wave][lane] = t0 + t1;
     __syncthreads();
     if (wave == 0 && ok) {
-        const double t = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+        const double t = red4(red, lane);
         cv[i] = (M.solo == 1 ? cv[i] : 0.0) - t;
     }
 }
@@ -732,8 +782,7 @@ __global__ __launch_bounds__(256) void k_fwd_solo64(DevView V, int list_off)
     const double* Mg = V.minv + M.minv_off;
     const int q = tid >> 2, part = tid & 3;
     double mreg[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) { const int p = part + 4 * u; mreg[u] = (q < k && p <= q) ? Mg[q + (size_t)p * k] : 0.0; }
+    ld_minv_row16(mreg, Mg, k, tid);
     const int i = k + rb * 64 + lane;
     const bool ok = rb >= 0 && i < m;
     const double* Lg = V.L + M.panel_off + (ok ? i : k);
@@ -741,25 +790,21 @@ __global__ __launch_bounds__(256) void k_fwd_solo64(DevView V, int list_off)
 #pragma unroll
     for (int u = 0; u < 16; ++u) { const int p = wave * 8 + (u & 7) + 32 * (u >> 3); lreg[u] = (ok && p < k) ? Lg[(size_t)p * M.ldp] : 0.0; }
     const double cvi = (ok && wave == 0 && M.solo == 1) ? cv[i] : 0.0;
-    int pt = 1; double dq = 0.0, oq = 0.0, oq1 = 0.0;
-    if (rb < 0 && tid < k) { pt = V.ptype[c0 + tid]; dq = V.dinv[c0 + tid]; oq = V.doff[c0 + tid]; oq1 = tid > 0 ? V.doff[c0 + tid - 1] : 0.0; }
+    const PivD D = ld_pivd(V, c0, tid, rb < 0 && tid < k);
     // ---- dependent on the pivot order ----
     if (tid < 64) bp[tid] = tid < k ? V.xw[c0 + lpv] + (M.solo == 1 ? cv[lpv] : 0.0) : 0.0;      // (ALL 64 entries: the product below runs over them with zeros of mreg, and 0 x a NaN left in LDS by an earlier kernel is NaN)
     __syncthreads();
     {
-        double a = 0.0;
-#pragma unroll
-        for (int u = 0; u < 16; ++u) a += mreg[u] * bp[(part + 4 * u) & 63];
-        a += __shfl_xor(a, 1); a += __shfl_xor(a, 2);
+        const double a = quad_dot16(mreg, bp, part);
         if (part == 0 && q < k) ys[q] = a;
     }
     __syncthreads();
     if (rb < 0) {
         if (tid < k) {
             double z;
-            if (pt == 1) z = ys[tid] * dq;
-            else if (pt == 2) z = dq * ys[tid] + oq * ys[tid + 1];
-            else z = oq1 * ys[tid - 1] + dq * ys[tid];
+            if (D.pt == 1) z = ys[tid] * D.dq;
+            else if (D.pt == 2) z = D.dq * ys[tid] + D.oq * ys[tid + 1];
+            else z = D.oq1 * ys[tid - 1] + D.dq * ys[tid];
             V.zb[c0 + tid] = z;
         }
         return;
@@ -772,13 +817,12 @@ __global__ __launch_bounds__(256) void k_fwd_solo64(DevView V, int list_off)
     }
     red[wave][lane] = t0 + t1;
     __syncthreads();
-    if (wave == 0 && ok) cv[i] = cvi - ((red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]));
+    if (wave == 0 && ok) cv[i] = cvi - red4(red, lane);
 }
 
 __global__ __launch_bounds__(256) void k_fwd_grp_upd(DevView V, int list_off)
 {
-    // 64 rows per workgroup (one per lane); the group's columns are dealt to the 4 wavefronts in blocks of 8 (8 coalesced
-    // loads in flight per lane), the 4 partial sums are combined through LDS in fixed order
+    // 64 rows per workgroup (one per lane), the columns of the group's links one link after the other (upd_row_acc, red4)
     __shared__ double ys[256];
     __shared__ double red[4][64];
     const FrontMeta M = V.fmeta[list_off + blockIdx.y];
@@ -799,21 +843,12 @@ __global__ __launch_bounds__(256) void k_fwd_grp_upd(DevView V, int list_off)
     cb = 0;
     for (int j = 0; j < nl; ++j) {
         const GroupLink G = V.gtab[M.gbase + j];
-        const double* Lg = V.L + G.panel_off + (G.m - M.m) + (ok ? i : M.k);
-        const double* y = ys + cb;
-        const int k = G.k;
-        for (int p = wave * 8; p < k; p += 32) {
-            double l[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) l[u] = (p + u < k) ? Lg[(size_t)(p + u) * G.ldp] : 0.0;
-#pragma unroll
-            for (int u = 0; u < 8; u += 2) { t0 += l[u] * ((p + u < k) ? y[p + u] : 0.0); t1 += l[u + 1] * ((p + u + 1 < k) ? y[p + u + 1] : 0.0); }
-        }
-        cb += k;
+        upd_row_acc(V.L + G.panel_off + (G.m - M.m) + (ok ? i : M.k), G.ldp, G.k, ys + cb, wave, t0, t1);
+        cb += G.k;
     }
     red[wave][lane] = t0 + t1;
     __syncthreads();
-    if (wave == 0 && ok) V.cvec[M.cv + i] -= (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+    if (wave == 0 && ok) V.cvec[M.cv + i] -= red4(red, lane);
 }
 
 __global__ __launch_bounds__(256) void k_bwd_grp_dot(DevView V, int list_off)
@@ -853,8 +888,29 @@ __global__ __launch_bounds__(256) void k_bwd_grp_dot(DevView V, int list_off)
     }
 }
 
+// A 256-row x 64-column block of a panel in the registers of a workgroup of 4 wavefronts, lv[pass][column of the pass][row strip]: wavefront `wave` holds
+// the columns wave * 4 + 16 ps + u < k, lane `lane` their rows lane + 64 s < nrow (Lg: the lane's first row of the panel's first column); zeros elsewhere.
+// CLAMP: the address of a column >= k is that of column 0 (the chain sweep's dot workgroups).
+template <bool CLAMP>
+__device__ __forceinline__ void ld_panel_block(double (&lv)[4][4][4], const double* Lg, const int ldp, const int k, const int wave, const int lane, const int nrow)
+{
+    const bool v0 = lane < nrow, v1 = lane + 64 < nrow, v2 = lane + 128 < nrow, v3 = lane + 192 < nrow;
+#pragma unroll
+    for (int ps = 0; ps < 4; ++ps)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int col = wave * 4 + 16 * ps + u;
+            const bool cv = col < k;
+            const double* c = Lg + (size_t)(CLAMP && !cv ? 0 : col) * ldp;
+            lv[ps][u][0] = (cv && v0) ? c[0] : 0.0; lv[ps][u][1] = (cv && v1) ? c[64] : 0.0;
+            lv[ps][u][2] = (cv && v2) ? c[128] : 0.0; lv[ps][u][3] = (cv && v3) ? c[192] : 0.0;
+        }
+}
+// a column of the block against the lane's four solution entries; the wavefront's sum over the lanes is the caller's (wave_sum here, wave_sum_dpp in the chain sweep)
+__device__ __forceinline__ double strip_dot(const double (&l)[4], const double x0, const double x1, const double x2, const double x3) { return (l[0] * x0 + l[1] * x1) + (l[2] * x2 + l[3] * x3); }
+
 // per-link (one link per solve unit), k <= 64 variants of k_bwd_grp_dot / k_bwd_grp with the loads that only depend on the front
-// record hoisted to the top (same arithmetic, same order of summation)
+// record hoisted to the top (same order of summation: part_sum4 is k_bwd_grp's, the dot products sum as k_bwd_grp_dot's)
 __global__ __launch_bounds__(256) void k_bwd_dot64(DevView V, int list_off)
 {
     const FrontMeta M = V.fmeta[list_off + blockIdx.y];
@@ -864,18 +920,8 @@ __global__ __launch_bounds__(256) void k_bwd_dot64(DevView V, int list_off)
     const int nrow = min(256, M.m - ibase), k = M.k;
     const bool v0 = lane < nrow, v1 = lane + 64 < nrow, v2 = lane + 128 < nrow, v3 = lane + 192 < nrow;
     // the panel entries first (they depend on the front record only) ...
-    const double* Lg = V.L + M.panel_off + ibase + lane;
-    double lv[4][4][4];                                      // [pass][column of the pass][row strip]
-#pragma unroll
-    for (int ps = 0; ps < 4; ++ps)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int col = wave * 4 + 16 * ps + u;
-            const bool cv = col < k;
-            const double* c = Lg + (size_t)col * M.ldp;
-            lv[ps][u][0] = (cv && v0) ? c[0] : 0.0; lv[ps][u][1] = (cv && v1) ? c[64] : 0.0;
-            lv[ps][u][2] = (cv && v2) ? c[128] : 0.0; lv[ps][u][3] = (cv && v3) ? c[192] : 0.0;
-        }
+    double lv[4][4][4];
+    ld_panel_block<false>(lv, V.L + M.panel_off + ibase + lane, M.ldp, k, wave, lane, nrow);
     // ... then the two dependent hops to the solution entries of the rows
     const int r0i = M.r0 + ibase;
     const double x0 = v0 ? V.xw[V.sn_rows[r0i + lane]] : 0.0, x1 = v1 ? V.xw[V.sn_rows[r0i + lane + 64]] : 0.0;
@@ -886,8 +932,7 @@ __global__ __launch_bounds__(256) void k_bwd_dot64(DevView V, int list_off)
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int col = wave * 4 + 16 * ps + u;
-            double t = (lv[ps][u][0] * x0 + lv[ps][u][1] * x1) + (lv[ps][u][2] * x2 + lv[ps][u][3] * x3);
-            t = wave_sum(t);
+            const double t = wave_sum(strip_dot(lv[ps][u], x0, x1, x2, x3));
             if (lane == 0 && col < k) part[col] = t;
         }
 }
@@ -902,24 +947,13 @@ __global__ __launch_bounds__(256) void k_bwd_fin64(DevView V, int list_off)
     const double* Mg = V.minv + M.minv_off;
     const int pcol = tid >> 2, part4 = tid & 3;
     double mreg[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) { const int q = pcol + part4 + 4 * u; mreg[u] = (pcol < k && q < k) ? Mg[q + (size_t)pcol * k] : 0.0; }
+    ld_minv_col16(mreg, Mg, k, pcol, part4);
     const int lpv = (part4 == 0 && pcol < k) ? V.lperm[c0 + pcol] : 0;
     if (tid < 64) ws[tid] = 0.0;
     __syncthreads();
-    if (tid < k) {
-        double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
-        int c = 0;
-        for (; c + 3 < nch; c += 4) { t0 += part[(size_t)c * M.gcols + tid]; t1 += part[(size_t)(c + 1) * M.gcols + tid];
-                                      t2 += part[(size_t)(c + 2) * M.gcols + tid]; t3 += part[(size_t)(c + 3) * M.gcols + tid]; }
-        for (; c < nch; ++c) t0 += part[(size_t)c * M.gcols + tid];
-        ws[tid] = V.zb[c0 + tid] - ((t0 + t1) + (t2 + t3));
-    }
+    if (tid < k) { const double t = part_sum4(part, nch, M.gcols, tid); ws[tid] = V.zb[c0 + tid] - t; }
     __syncthreads();
-    double a = 0.0;
-#pragma unroll
-    for (int u = 0; u < 16; ++u) a += mreg[u] * ws[(pcol + part4 + 4 * u) & 63];       // (entries beyond k are zero in mreg)
-    a += __shfl_xor(a, 1); a += __shfl_xor(a, 2);
+    const double a = quad_dot16(mreg, ws, pcol + part4);       // (entries beyond k are zero in mreg)
     if (part4 == 0 && pcol < k) V.xw[c0 + lpv] = a;
 }
 
@@ -937,14 +971,7 @@ __global__ __launch_bounds__(256) void k_bwd_grp(DevView V, int list_off)
         const int k = G.k, c0 = G.c0;
         cb -= k;                                           // first group column of this link
         const int rem = M.gcols - cb - k;                  // pivots of the later links = this link's first update rows
-        for (int p = tid; p < k; p += 256) {
-            double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
-            int c = 0;
-            for (; c + 3 < nch; c += 4) { t0 += part[(size_t)c * M.gcols + cb + p]; t1 += part[(size_t)(c + 1) * M.gcols + cb + p];
-                                          t2 += part[(size_t)(c + 2) * M.gcols + cb + p]; t3 += part[(size_t)(c + 3) * M.gcols + cb + p]; }
-            for (; c < nch; ++c) t0 += part[(size_t)c * M.gcols + cb + p];
-            ws[p] = V.zb[c0 + p] - ((t0 + t1) + (t2 + t3));
-        }
+        for (int p = tid; p < k; p += 256) { const double t = part_sum4(part, nch, M.gcols, cb + p); ws[p] = V.zb[c0 + p] - t; }
         for (int i = tid; i < rem; i += 256) xs[i] = V.xw[V.sn_rows[G.r0 + k + i]];
         __syncthreads();
         if (rem > 0) {
@@ -961,21 +988,7 @@ __global__ __launch_bounds__(256) void k_bwd_grp(DevView V, int list_off)
             }
             __syncthreads();
         }
-        const double* Mg = V.minv + G.minv_off;
-        {   // x_p = sum_{q >= p} Minv(q,p) w_q : 4 threads per column (contiguous quarter-interleaved walk), combined by shuffles
-            const int part = tid & 3;
-            for (int p = tid >> 2; p < k; p += 64) {
-                double a = 0.0;
-                int q = p + part;
-                for (; q + 12 < k; q += 16) {
-                    const double m0 = Mg[q + (size_t)p * k], m1 = Mg[q + 4 + (size_t)p * k], m2 = Mg[q + 8 + (size_t)p * k], m3 = Mg[q + 12 + (size_t)p * k];
-                    a += m0 * ws[q] + m1 * ws[q + 4] + m2 * ws[q + 8] + m3 * ws[q + 12];
-                }
-                for (; q < k; q += 4) a += Mg[q + (size_t)p * k] * ws[q];
-                a += __shfl_xor(a, 1); a += __shfl_xor(a, 2);
-                if (part == 0) V.xw[c0 + V.lperm[c0 + p]] = a;
-            }
-        }
+        minv_cols_quad(V, V.minv + G.minv_off, c0, k, ws, tid);
         __syncthreads();
     }
 }
@@ -1134,7 +1147,7 @@ __global__ __launch_bounds__(320) void k_fwd_chain(DevView V, int wg0)
     const int k = Me.k, c0 = Me.c0;
     const int nprev = is_link ? w : C.nlinks;
     double mreg[16], lrA[16], lrB[16];
-    int pt = 1; double dq = 0.0, oq = 0.0, oq1 = 0.0;
+    PivD D = {1, 0.0, 0.0, 0.0};
     auto fetch_block = [&](double (&lr)[16], const int i) {      // my rows of link i's panel
         const ChainLink L = V.chlink[C.link0 + i];
         const double* Lb = V.L + uni(L.panel_off) + (roff - uni(L.koff));      // (uniform base + 32-bit lane offsets: one address register pair, not 16)
@@ -1146,12 +1159,10 @@ __global__ __launch_bounds__(320) void k_fwd_chain(DevView V, int wg0)
     double xb = 0.0;
     if (!poller) {
         if (is_link) {
-            const double* Mg = V.minv + Me.minv_off;
-#pragma unroll
-            for (int u = 0; u < 16; ++u) { const int pp = part + 4 * u; mreg[u] = (row < k && pp <= row) ? Mg[row + (size_t)pp * k] : 0.0; }      // Minv(row, pp)
+            ld_minv_row16(mreg, V.minv + Me.minv_off, k, tid);
             if (tid < 64) bps[tid] = 0.0;          // (entries beyond k meet zeros of mreg below: they must not be whatever an earlier kernel left in LDS -- 0 x NaN)
             if (tid < k) ipos[V.lperm[c0 + tid]] = tid;
-            if (part == 0 && row < k) { pt = V.ptype[c0 + row]; dq = V.dinv[c0 + row]; oq = V.doff[c0 + row]; oq1 = row > 0 ? V.doff[c0 + row - 1] : 0.0; }
+            D = ld_pivd(V, c0, row, part == 0 && row < k);
             if (rok) xb = V.xw[c0 + row];
         }
         if (nprev > 0) fetch_block(lrA, 0);
@@ -1193,13 +1204,10 @@ __global__ __launch_bounds__(320) void k_fwd_chain(DevView V, int wg0)
         dst[lane] = tag_await(V.ytag + lc0[i & 63], lane, lkk[i & 63], ep, nprev - 1 - i, err);
     };
     auto step = [&](double (&lr)[16], const double* ym, const int i) {
-        double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-        for (int u = 0; u < 16; u += 2) { a0 += lr[u] * ym[part + 4 * u]; a1 += lr[u + 1] * ym[part + 4 * u + 4]; }
+        double a0, a1;
+        quad_dot16_eo(lr, ym, part, a0, a1);
         if (i + 2 < nprev) fetch_block(lr, i + 2);          // two hops ahead
-        double t = a0 + a1;
-        t += dpp_f64<0xB1>(t); t += dpp_f64<0x4E>(t);       // the 4 lanes of a row are a DPP quad
-        acc -= t;
+        acc -= quad_sum_dpp(a0 + a1);
     };
     for (int i = 0; i < nprev; i += 2) {
         if (poller) poll(i, ymsg[0]);
@@ -1221,11 +1229,9 @@ __global__ __launch_bounds__(320) void k_fwd_chain(DevView V, int wg0)
     }
     if (part == 0 && row < k) bps[myipos] = acc;              // P b
     __syncthreads();
-    double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-    for (int u = 0; u < 16; u += 2) { a0 += mreg[u] * bps[part + 4 * u]; a1 += mreg[u + 1] * bps[part + 4 * u + 4]; }      // (mreg is zero beyond the row)
-    double y = a0 + a1;
-    y += dpp_f64<0xB1>(y); y += dpp_f64<0x4E>(y);
+    double a0, a1;
+    quad_dot16_eo(mreg, bps, part, a0, a1);      // (mreg is zero beyond the row)
+    const double y = quad_sum_dpp(a0 + a1);
     if (part == 0 && row < k) { v2d m; m.x = y; m.y = ep; st_tag(V.ytag + c0 + row, m); }
     if (tr && tid == 0) tr[3] = wall_clock64();
     // off the chain's critical path: z = D^{-1} y for the backward sweep
@@ -1233,9 +1239,9 @@ __global__ __launch_bounds__(320) void k_fwd_chain(DevView V, int wg0)
     __syncthreads();
     if (part == 0 && row < k) {
         double z;
-        if (pt == 1) z = y * dq;
-        else if (pt == 2) z = dq * y + oq * yss[row + 1];
-        else z = oq1 * yss[row - 1] + dq * y;
+        if (D.pt == 1) z = y * D.dq;
+        else if (D.pt == 2) z = D.dq * y + D.oq * yss[row + 1];
+        else z = D.oq1 * yss[row - 1] + D.dq * y;
         V.ybuf[c0 + row] = y;
         V.zb[c0 + row] = z;
     }
@@ -1269,18 +1275,8 @@ __global__ __launch_bounds__(320) void k_bwd_chain(DevView V, int wg0)
         const ChainLink Me = uni(V.chlink[C.link0 + C.nlinks - 1 - jj]);
         const int k = Me.k, toff = C.ktot - Me.koff, ibase = b * 256, nrow = min(256, C.tail - ibase);
         const bool v0 = lane < nrow, v1 = lane + 64 < nrow, v2 = lane + 128 < nrow, v3 = lane + 192 < nrow;
-        const double* Lg = V.L + Me.panel_off + toff + ibase + lane;
-        double lv[4][4][4];                                      // [pass][column of the pass][row strip]
-#pragma unroll
-        for (int ps = 0; ps < 4; ++ps)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int cc = wave * 4 + 16 * ps + u;
-                const bool cv = cc < k;
-                const double* c = Lg + (size_t)(cv ? cc : 0) * Me.ldp;
-                lv[ps][u][0] = (cv && v0) ? c[0] : 0.0; lv[ps][u][1] = (cv && v1) ? c[64] : 0.0;
-                lv[ps][u][2] = (cv && v2) ? c[128] : 0.0; lv[ps][u][3] = (cv && v3) ? c[192] : 0.0;
-            }
+        double lv[4][4][4];
+        ld_panel_block<true>(lv, V.L + Me.panel_off + toff + ibase + lane, Me.ldp, k, wave, lane, nrow);
         const int r0i = Me.r0 + toff + ibase + lane;
         const int i0 = v0 ? V.sn_rows[r0i] : 0, i1 = v1 ? V.sn_rows[r0i + 64] : 0, i2 = v2 ? V.sn_rows[r0i + 128] : 0, i3 = v3 ? V.sn_rows[r0i + 192] : 0;
         flags_await(V.sflag_b, V.chwait, C.pw0, C.pw1, epoch, err);
@@ -1292,8 +1288,7 @@ __global__ __launch_bounds__(320) void k_bwd_chain(DevView V, int wg0)
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int cc = wave * 4 + 16 * ps + u;
-                double t = (lv[ps][u][0] * x0 + lv[ps][u][1] * x1) + (lv[ps][u][2] * x2 + lv[ps][u][3] * x3);
-                t = wave_sum_dpp(t);
+                const double t = wave_sum_dpp(strip_dot(lv[ps][u], x0, x1, x2, x3));
                 if (lane == 0 && cc < k) st_coh(&dp[cc], t);
             }
         if (tr && tid == 0) tr[2] = wall_clock64();
@@ -1318,9 +1313,7 @@ __global__ __launch_bounds__(320) void k_bwd_chain(DevView V, int wg0)
         for (int u = 0; u < 16; ++u) lr[u] = (col < k && part + 4 * u < kl) ? Lb[off + 4 * u] : 0.0;
     };
     if (!poller) {
-        const double* Mg = V.minv + Me.minv_off;
-#pragma unroll
-        for (int u = 0; u < 16; ++u) { const int q = col + part + 4 * u; mreg[u] = (col < k && q < k) ? Mg[q + (size_t)col * k] : 0.0; }      // Minv(q, col), q >= col
+        ld_minv_col16(mreg, V.minv + Me.minv_off, k, col, part);
         if (col < k) lpv = V.lperm[c0 + col];
         if (nlater > 0) fetch_block(lrA, 0);
         if (nlater > 1) fetch_block(lrB, 1);
@@ -1348,13 +1341,10 @@ __global__ __launch_bounds__(320) void k_bwd_chain(DevView V, int wg0)
         dst[lane] = tag_await(V.xtag + lc0[i & 63], lane, lkk[i & 63], ep, nlater - 1 - i, err);
     };
     auto step = [&](double (&lr)[16], const double* xm, const int i) {
-        double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-        for (int u = 0; u < 16; u += 2) { a0 += lr[u] * xm[part + 4 * u]; a1 += lr[u + 1] * xm[part + 4 * u + 4]; }
+        double a0, a1;
+        quad_dot16_eo(lr, xm, part, a0, a1);
         if (i + 2 < nlater) fetch_block(lr, i + 2);
-        double t = a0 + a1;
-        t += dpp_f64<0xB1>(t); t += dpp_f64<0x4E>(t);
-        wv -= t;
+        wv -= quad_sum_dpp(a0 + a1);
     };
     for (int i = 0; i < nlater; i += 2) {
         if (poller) poll(i, xmsg[0]);
@@ -1369,11 +1359,9 @@ __global__ __launch_bounds__(320) void k_bwd_chain(DevView V, int wg0)
     if (poller) return;
     if (part == 0) ws[col] = wv;
     __syncthreads();
-    double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-    for (int u = 0; u < 16; u += 2) { a0 += mreg[u] * ws[(col + part + 4 * u) & 63]; a1 += mreg[u + 1] * ws[(col + part + 4 * u + 4) & 63]; }     // (mreg is zero beyond k)
-    double x = a0 + a1;
-    x += dpp_f64<0xB1>(x); x += dpp_f64<0x4E>(x);
+    double a0, a1;
+    quad_dot16_eo(mreg, ws, col + part, a0, a1);     // (mreg is zero beyond k)
+    const double x = quad_sum_dpp(a0 + a1);
     if (part == 0 && col < k) {
         v2d m; m.x = x; m.y = ep;
         st_tag(V.xtag + c0 + lpv, m);
