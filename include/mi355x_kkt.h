@@ -375,6 +375,55 @@ int  mi355x_kkt_lbfgs_resto_info(mi355x_kkt_handle h, int* resto, int* special, 
 int  mi355x_kkt_lbfgs_push_mapped(mi355x_kkt_handle h, const double* sx, const double* yx, int64_t len, int on_device, int* outcome);
 int  mi355x_kkt_lbfgs_push_resto_mapped(mi355x_kkt_handle h, const double* sx, const double* ypartx, int64_t len, int on_device, double eta, int* outcome);
 
+/* ---- the quasi-Newton pair (s, y) formed on the device from the resident Jacobians ---------------------------------------------------------------
+ * What the same updater does before every update (IpLimMemQuasiNewtonUpdater.cpp:276-308):  s = x_k - x_(k-1) (:282) and
+ *   y = (grad_f_k - grad_f_(k-1)) + J_c,k^T y_c + J_d,k^T y_d - J_c,k-1^T y_c - J_d,k-1^T y_d   (:304-307; the restoration phase drops the grad_f term: ypart, :297-300)
+ * -- there four host products over nnz(J) per iteration.  Here the current Jacobian values are the device-resident sources of two segments of the value
+ * assembly (_assembly_define / _assembly_upload), the previous ones a snapshot kept next to them, and one kernel pass forms
+ *   s[j] = x[j] - x_last[j],   y[j] = (grad_f[j] - gf_last[j]) + sum over the entries (i, t) of column j of (J_cur[t] - J_last[t]) lam[i],   lam = y_c | y_d.
+ * The difference PER ENTRY is a stated deviation from the reference's order of four products: an entry that did not change contributes an exact 0 (linear
+ * constraints contribute exactly nothing), the cancellation happens before the multiplication; the difference to the reference's order is rounding only
+ * (tests/support/qn_pair_spec.py: both orders within (k_j + 4) 2^-52 (|gf_j| + |gf_last_j| + sum (|J_cur| + |J_last|) |lam|), k_j entries in column j).
+ * Every sum runs in a fixed order, there are no atomics on doubles: the result is bitwise reproducible.
+ *   _qn_pair_check   stand-alone, HOST, no handle, no GPU: the validation _define performs on dims4 = {nx, ns, nc, nd}, the 1-based triplets and the two
+ *                  ranges [off, off + len) of the triplet list; SUCCESS, or FATAL with the reason in msg (capacity bytes, may be NULL)
+ *   _qn_pair_define  needs _analyse and _assembly_define.  irn, jcn: the 1-based triplets of _analyse, as _pd_define takes them; seg_jc, seg_jd: the assembly
+ *                  segments that hold J_c and J_d (negative, or a segment of length 0: the block is absent).  nx + ns + nc + nd = n, ns = nd; every entry
+ *                  of the J_c segment has one index in the x block [1, nx] and the other in the c block, of the J_d segment in the x and the d block
+ *                  (either orientation; duplicates stay separate and sum).  FATAL names the argument and the first offending triplet position; nothing
+ *                  reaches the device before the check has passed, which is why no kernel can index out of range.  The definition is stated in the
+ *                  caller's numbering: it survives factorisations and delayed-pivot structure edits; a new _analyse or _assembly_define ends it.
+ *   _qn_pair_store   the reference's last_x_ = curr_x, last_grad_f_, last_jac_c_, last_jac_d_ (:243-246, :700-703): x_last <- x, gf_last <- grad_f (NULL: the restoration
+ *                  variant, y will be ypart), J_last <- a COPY of the segments' current device SOURCES (not of the assembled values: scale and shift of
+ *                  _factor_assembled do not enter; a later _assembly_upload does not change it).  x == NULL: "roll" -- x and grad_f are those the last _form
+ *                  was given, nothing is uploaded (FATAL when no pair is formed).  Marks "stored", clears "formed".
+ *   _qn_pair_form    FATAL unless something is stored, and when grad_f is NULL here but was not in _store or the other way round.  x, grad_f (nx), y_c (nc),
+ *                  y_d (nd): host memory, or -- on_device != 0 -- device memory, complete before the call and free again when it returns.  Reads whatever
+ *                  the segment sources hold NOW: upload the current Jacobians first.  *amax_s (may be NULL) = max |s|, over the indices of the row map
+ *                  when one is set (_lowrank_rowmap), over all nx otherwise (a NaN counts as +inf): what the reference's skip of a tiny step needs
+ *                  (s_new->Amax() < 100 eps, :350-357 -- that test stays with the caller).  One download (the scalar) and one synchronisation, only when
+ *                  amax_s is not NULL (device vectors: one synchronisation either way, they are free when the call returns).
+ *   _qn_pair_push    FATAL unless a pair is formed and a history defined.  Pushes the formed DEVICE vectors through the existing paths, no vector makes a host
+ *                  round trip: with a row map the path of _lbfgs_push_mapped / _push_resto_mapped (on_device, len = nx; the map must lie inside the x
+ *                  block), without one that of _lbfgs_push_device / _push_resto_device on the first `rows` entries (rows <= nx, else FATAL).  A restoration
+ *                  history takes eta and needs a pair formed without grad_f; a plain history ignores eta and needs one formed with grad_f; a mismatch
+ *                  is FATAL.  Outcomes are those of the push that ran; bitwise the same as pushing the vectors of _get by hand.
+ *   _qn_pair_get     what: 0 s, 1 y (nx; need a formed pair), 2 x_last, 3 grad_f_last (nx; FATAL on a snapshot stored without grad_f), 4 Jc_last, 5 Jd_last
+ *                  (the segment lengths; 2..5 need a stored snapshot); FATAL when `capacity` (doubles) is too small
+ *   _qn_pair_info    outputs may be NULL; nnz_j: entries of the column view; form_ms: host ms of the last _form
+ *   _qn_pair_clear   undefines: frees the view, the snapshot and the pair
+ * The kernel runs 1, 8 or 64 lanes per column, picked per definition from the structure alone (mean and longest column: qn_pair_host.h qp_pick_lpc);
+ * _get_launch_plan "qn_pair" reports it.  Arguments and the state rules are checked before the device is touched; single-GPU handles only. */
+int  mi355x_kkt_qn_pair_check(int64_t nnz, const int32_t* dims4, const int32_t* irn, const int32_t* jcn, int64_t off_jc, int64_t len_jc, int64_t off_jd, int64_t len_jd,
+                              char* msg, int64_t capacity);
+int  mi355x_kkt_qn_pair_define(mi355x_kkt_handle h, const int32_t* dims4, const int32_t* irn, const int32_t* jcn, int seg_jc, int seg_jd);
+int  mi355x_kkt_qn_pair_store(mi355x_kkt_handle h, const double* x, const double* grad_f, int on_device);
+int  mi355x_kkt_qn_pair_form(mi355x_kkt_handle h, const double* x, const double* grad_f, const double* y_c, const double* y_d, int on_device, double* amax_s);
+int  mi355x_kkt_qn_pair_push(mi355x_kkt_handle h, double eta, int* outcome);
+int  mi355x_kkt_qn_pair_get(mi355x_kkt_handle h, int what, double* out, int64_t capacity);
+int  mi355x_kkt_qn_pair_info(mi355x_kkt_handle h, int* defined, int* stored, int* formed, int* nx, int64_t* nnz_j, double* form_ms);
+int  mi355x_kkt_qn_pair_clear(mi355x_kkt_handle h);
+
 int  mi355x_kkt_set_pivtol(mi355x_kkt_handle h, double u);
 int  mi355x_kkt_set_pivtolmax(mi355x_kkt_handle h, double umax);
 /* IncreaseQuality (IpSparseSymLinearSolverInterface.hpp:220): raises u <- min(pivtolmax, u^0.75) (the rule of
@@ -452,6 +501,8 @@ int  mi355x_kkt_get_symbolic(mi355x_kkt_handle h, int what, int* out, int64_t ca
  *   "lc_ptr" / "lc_fronts" (leaf chains: their fronts, leaf first), "df_runs" ({lv0, lv1, tab0, nlev, nq} per k_front_df run),
  *   "chain_segs" (9 ints per data-flow sweep segment), "chain_links" ({s, k, koff, fi} per link), "chain_descs" ({link0, nlinks, tail, ktot, s0, init}
  *   per chain), "join" ({base, count, maxm, who} per kind), "exchange" ({step, glo, gsz, arena doubles, top-rhs doubles} per range),
+ *   "qn_pair" {defined, lanes per column of k_qn_pair (1, 8 or 64), longest column, nx, entries of the column view as (low, high) halves} -- the launch of
+ *   _qn_pair_form (state of the handle, not of the analysis),
  *   "col_owner", "stat_owner", "scalars" {levels, exchange steps, leaf-chain levels, leaf chains, look-ahead, grouped, tfuse fronts, big fronts, stages}.
  *   What a system REACHES -- the fields the kernels and the launch code branch on (the tests show with them that a fixture runs the path it names):
  *   "path_bits" one int per launch-list entry: 1 contribution block formed by its update (tfuse), 2 assembles itself (selfasm), 4 solo (fused forward

@@ -9,6 +9,7 @@
 #include "env_knobs.h"
 #include "lbfgs_host.h"      // the small algebra of an L-BFGS push: mi355x_kkt_lbfgs_coefficients is this header alone
 #include "lowrank_host.h"    // the validation of a row map: mi355x_kkt_lowrank_rowmap_check is this header alone
+#include "qn_pair_host.h"    // the validation and the state rules of the quasi-Newton pair: mi355x_kkt_qn_pair_check is this header alone
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -639,6 +640,102 @@ int mi355x_kkt_lbfgs_resto_info(mi355x_kkt_handle h, int* resto, int* special, d
     if (resto) *resto = 0; if (special) *special = 0; if (eta) *eta = 0.0;
     return lowrank_call(h, "lbfgs_resto_info", false, [&] { h->num->lbfgs_resto_info(resto, special, eta); return true; });
 }
+// ---- the quasi-Newton pair (s, y) formed on the device from the resident Jacobians (IpLimMemQuasiNewtonUpdater.cpp:276-308) ----
+// The order of every call: the handle is analysed, every argument, the multi-GPU refusal, the state rules (qn_pair_host.h: host state, they answer
+// without a device), then the device.
+// host only, no handle, no device: the validation qn_pair_define performs (qn_pair_host.h)
+int mi355x_kkt_qn_pair_check(int64_t nnz, const int32_t* dims4, const int32_t* irn, const int32_t* jcn, int64_t off_jc, int64_t len_jc, int64_t off_jd, int64_t len_jd, char* msg, int64_t capacity)
+{
+    std::string why; bool ok = false;
+    try { ok = qp_check((long long)nnz, dims4, irn, jcn, QpSegs{(long long)off_jc, (long long)len_jc, (long long)off_jd, (long long)len_jd}, why); } catch (...) { ok = false; why = "unexpected exception"; }
+    if (msg && capacity > 0) { const size_t k = std::min<size_t>(why.size(), (size_t)capacity - 1); std::memcpy(msg, why.data(), k); msg[k] = 0; }
+    return ok ? MI355X_KKT_SUCCESS : MI355X_KKT_FATAL;
+}
+#define QP_MULTI() do { if (h->opts.nranks > 1) LR_FAIL("not supported on a multi-GPU handle"); } while (0)
+int mi355x_kkt_qn_pair_define(mi355x_kkt_handle h, const int32_t* dims4, const int32_t* irn, const int32_t* jcn, int seg_jc, int seg_jd)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "qn_pair_define";
+    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
+    if (!dims4) LR_FAIL("dims4 is null");
+    const long long sum = (long long)dims4[0] + dims4[1] + dims4[2] + dims4[3];
+    if (sum != h->sym.n) LR_FAIL("dims4: nx + ns + nc + nd = " + std::to_string(sum) + " must equal n = " + std::to_string(h->sym.n));
+    QpSegs g;
+    const int nseg = h->num ? h->num->assembly_info(-1, nullptr, nullptr) : 0;
+    if (seg_jc >= nseg) LR_FAIL("seg_jc = " + std::to_string(seg_jc) + " is out of range: the assembly has " + std::to_string(nseg) + " segments (assembly_define first)");
+    if (seg_jd >= nseg) LR_FAIL("seg_jd = " + std::to_string(seg_jd) + " is out of range: the assembly has " + std::to_string(nseg) + " segments (assembly_define first)");
+    if (seg_jc >= 0 && seg_jc == seg_jd) LR_FAIL("seg_jc and seg_jd name the same segment");
+    if (seg_jc >= 0) h->num->assembly_info(seg_jc, &g.off_jc, &g.len_jc);
+    if (seg_jd >= 0) h->num->assembly_info(seg_jd, &g.off_jd, &g.len_jd);
+    std::string why;
+    try { if (!qp_check(h->sym.nnz_in, dims4, irn, jcn, g, why)) LR_FAIL(why); } catch (...) { LR_FAIL("unexpected exception"); }
+    return lowrank_call(h, name, false, [&] { return h->num->qn_pair_define(dims4, irn, jcn, seg_jc, seg_jd, g); });
+}
+int mi355x_kkt_qn_pair_store(mi355x_kkt_handle h, const double* x, const double* grad_f, int on_device)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "qn_pair_store";
+    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
+    if (!x && grad_f) LR_FAIL("x is null (roll) but grad_f is not: a roll takes both from the last qn_pair_form");
+    QP_MULTI();
+    std::string why;
+    if (!qp_store_ok(h->num->qn_pair_state(), !x, why)) LR_FAIL(why);
+    return lowrank_call(h, name, false, [&] { return h->num->qn_pair_store(x, grad_f, on_device != 0); });
+}
+int mi355x_kkt_qn_pair_form(mi355x_kkt_handle h, const double* x, const double* grad_f, const double* y_c, const double* y_d, int on_device, double* amax_s)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "qn_pair_form";
+    if (amax_s) *amax_s = 0.0;
+    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
+    if (!x) LR_FAIL("x is null");
+    QP_MULTI();
+    const QpState& st = h->num->qn_pair_state();
+    std::string why;
+    if (!qp_form_ok(st, grad_f != nullptr, why)) LR_FAIL(why);
+    if (st.nc > 0 && !y_c) LR_FAIL("y_c is null with nc > 0");
+    if (st.nd > 0 && !y_d) LR_FAIL("y_d is null with nd > 0");
+    return lowrank_call(h, name, false, [&] { return h->num->qn_pair_form(x, grad_f, y_c, y_d, on_device != 0, amax_s); });
+}
+int mi355x_kkt_qn_pair_push(mi355x_kkt_handle h, double eta, int* outcome)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "qn_pair_push";
+    if (outcome) *outcome = 1;
+    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
+    QP_MULTI();
+    int rows = 0, resto = 0, mr = 0; long long last = -1; std::string why;
+    h->num->lbfgs_info(&rows, nullptr, nullptr, nullptr, nullptr, nullptr); h->num->lbfgs_resto_info(&resto, nullptr, nullptr); h->num->lowrank_rowmap_info(&mr, &last);
+    if (!qp_push_ok(h->num->qn_pair_state(), rows, resto != 0, mr, last, why)) LR_FAIL(why);
+    if (resto && (!(eta > 0.0) || !std::isfinite(eta))) LR_FAIL("eta must be positive and finite (a restoration-phase history)");
+    int oc = 1;
+    const int st = lowrank_call(h, name, false, [&] { return h->num->qn_pair_push(eta, &oc); });
+    if (st == MI355X_KKT_SUCCESS && outcome) *outcome = oc;
+    return st;
+}
+int mi355x_kkt_qn_pair_get(mi355x_kkt_handle h, int what, double* out, int64_t capacity)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    const char* name = "qn_pair_get";
+    if (!h->analysed) LR_FAIL("the handle is not analysed (analyse() first)");
+    if (what < 0 || what > 5) LR_FAIL("what must be in [0, 5] (s, y, x_last, grad_f_last, Jc_last, Jd_last)");
+    if (capacity < 0) LR_FAIL("capacity must be >= 0");
+    if (capacity > 0 && !out) LR_FAIL("out is null with capacity > 0");
+    QP_MULTI();
+    std::string why;
+    const long long need = qp_get_need(h->num->qn_pair_state(), what, why);
+    if (need < 0) LR_FAIL(why);
+    if (capacity < need) LR_FAIL("capacity is below the " + std::to_string(need) + " doubles of this array");
+    return lowrank_call(h, name, false, [&] { return h->num->qn_pair_get(what, out, (long long)capacity); });
+}
+int mi355x_kkt_qn_pair_info(mi355x_kkt_handle h, int* defined, int* stored, int* formed, int* nx, int64_t* nnz_j, double* form_ms)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    if (defined) *defined = 0; if (stored) *stored = 0; if (formed) *formed = 0; if (nx) *nx = 0; if (nnz_j) *nnz_j = 0; if (form_ms) *form_ms = 0.0;
+    return lowrank_call(h, "qn_pair_info", false, [&] { h->num->qn_pair_info(defined, stored, formed, nx, nnz_j, form_ms); return true; });
+}
+int mi355x_kkt_qn_pair_clear(mi355x_kkt_handle h) { return lowrank_call(h, "qn_pair_clear", false, [&] { return h->num->qn_pair_clear(); }); }
+#undef QP_MULTI
 #undef LR_FAIL
 
 int mi355x_kkt_solve(mi355x_kkt_handle h, int nrhs, double* rhs, int ld)
@@ -780,6 +877,11 @@ int mi355x_kkt_get_launch_plan(mi355x_kkt_handle h, int nranks, int rank, const 
     if (!h->analysed) { h->err = "get_launch_plan: analyse() first"; return MI355X_KKT_FATAL; }
     if (nranks != std::max(1, h->so.nranks) || rank < 0 || rank >= nranks) { h->err = "get_launch_plan: nranks is the analysis's, 0 <= rank < nranks"; return MI355X_KKT_FATAL; }
     try {
+        if (std::string(what) == "qn_pair") {      // the launch of qn_pair_form: host state of the engine, not part of the factor / solve plan
+            *count = 6;
+            if (out) { if (cap < 6) { h->err = "get_launch_plan: buffer too small"; return MI355X_KKT_FATAL; } h->num->qn_pair_plan(out); }
+            return MI355X_KKT_SUCCESS;
+        }
         const LaunchPlan P = build_launch_plan(h->sym, plan_inputs_from_env(nranks, rank, nranks > 1, 0));
         if (!P.error.empty()) { h->err = P.error; return MI355X_KKT_FATAL; }
         std::vector<int> v;

@@ -7,6 +7,7 @@
 //       (mid_solve: the load-batched solve kernels of the fronts of order 33..128, k_fwd_mid / k_bwd_mid; off: k_fwd / k_bwd -- numeric.hip reads it itself)
 //   MI355X_KKT_TUNE=name=value[,...]    numeric thresholds of the schedule (defaults are the measured optima; tests force a path with them):
 //       la_wgs la_min_nt la_min_tiles grp_rbw_max grp_maxchains fuse_dt_maxwg chain_solve_maxc fastpiv_floor
+//       (qn_lpc=1|8|64: the lanes per column of k_qn_pair instead of qp_pick_lpc's choice, read by qn_pair_define: tools/qn_pair_time.py measures the alternatives)
 // Both are read when a handle is set up (analyse / restructure), `optimistic` at the first factorisation of the process.
 #pragma once
 #include <cstdlib>

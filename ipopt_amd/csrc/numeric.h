@@ -2,6 +2,7 @@
 // Host code (api.cpp) owns a Numeric object per solver handle.
 #pragma once
 #include "symbolic.h"
+#include "qn_pair_host.h"      // QpSegs, QpState (host only)
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -132,6 +133,20 @@ public:
     // a restoration-phase history (LbDefine::dr; lbfgs_host.h "the restoration phase") takes resto pushes only (LbPush::resto; a plain push is refused,
     // and the other way round); every other lbfgs_* call serves it unchanged.  lbfgs_get what: 1 is Ypart; 10 G, 11 R, 12 eta_col, 13 dv, 14 DR.
     void   lbfgs_resto_info(int* resto, int* special, double* eta) const;
+    // the quasi-Newton pair (s, y) formed from the resident Jacobians (IpLimMemQuasiNewtonUpdater.cpp:276-308; qn_pair_host.h): a column view of [J_c; J_d] over two
+    // segments of the value assembly (g: their ranges, validated by qp_check before the call), a snapshot of x, grad_f and the segments' sources (store), one
+    // kernel pass for s = x - x_last, y = (grad_f - gf_last) + sum (J_cur - J_last) lam (form), and the push of the formed device vectors through lbfgs_push.
+    // assembly_info: number of assembly segments and the range of `seg`; qn_pair_state / qn_pair_plan: host state, answer without a device.
+    int    assembly_info(int seg, long long* off, long long* len) const;
+    bool   qn_pair_define(const int32_t* dims4, const int32_t* irn, const int32_t* jcn, int seg_jc, int seg_jd, const QpSegs& g);
+    bool   qn_pair_store(const double* x, const double* grad_f, bool device);      // x == nullptr: roll
+    bool   qn_pair_form(const double* x, const double* grad_f, const double* y_c, const double* y_d, bool device, double* amax_s);
+    bool   qn_pair_push(double eta, int* outcome);
+    bool   qn_pair_get(int what, double* out, long long capacity);
+    void   qn_pair_info(int* defined, int* stored, int* formed, int* nx, int64_t* nnz_j, double* form_ms) const;
+    void   qn_pair_plan(int* out6) const;                // {defined, lanes per column, longest column, nx, entries low, high}
+    const QpState& qn_pair_state() const;
+    bool   qn_pair_clear();
     long long factor_count() const;                  // bumped by every factorisation (the refactorisations of a delayed-pivot loop included) and every structure edit
     // communicator of a multi-GPU handle: with one set, factor()/solve_*() run the whole distributed sequence themselves
     bool   set_comm_rccl(const void* unique_id128);                                   // RCCL (dlopen'ed), ncclCommInitRank(nranks, id, rank)

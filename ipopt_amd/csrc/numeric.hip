@@ -42,6 +42,7 @@
 #include "device_owner.h"      // DeviceOwner, HIPCHK
 #include "lowrank_host.h"      // the host Cholesky of the low-rank update
 #include "lbfgs_host.h"        // the small algebra of the limited-memory BFGS updater
+#include "qn_pair_host.h"      // the column view and the state rules of the quasi-Newton pair formed on the device
 
 namespace mi355x {
 
@@ -70,6 +71,7 @@ static constexpr double ZERO_REL = 1e-14;                // zero-pivot test rela
 #include "kernels_match.hip.inc"
 #include "kernels_lowrank.hip.inc"
 #include "kernels_lbfgs.hip.inc"
+#include "kernels_qn_pair.hip.inc"
 // ------------------------------------------------------------------------------------------------
 // host-side orchestration
 // ------------------------------------------------------------------------------------------------
@@ -102,6 +104,7 @@ public:
     DeviceOwner own_pd{err_};          // until pd_define or release(false): the primal-dual workspace
     DeviceOwner own_lr{err_};          // until lowrank_set / lowrank_clear or release(false): the low-rank update (caller's numbering: survives a restructure, like own_pd)
     DeviceOwner own_lb{err_};          // until lbfgs_define / lbfgs_clear or release(false): the L-BFGS history (caller's numbering, like own_lr)
+    DeviceOwner own_qn{err_};          // until qn_pair_define / qn_pair_clear, assembly_define or release(false): the pair (s, y) formed from the resident Jacobians (caller's numbering, like own_lb)
     DeviceOwner own_map{err_};         // until lowrank_rowmap or release(false): the row map of the low-rank update (caller's numbering; lowrank_clear / lbfgs_clear leave it alone)
     DevView V{};
     int* d_stats = nullptr;
@@ -259,6 +262,7 @@ public:
         long long total = 0;
         for (int q = 0; q < nseg; ++q) { if (off[q] != total || len[q] < 0) { err_ = "assembly_define: segments must tile [0, nnz) in order"; return false; } total += len[q]; }
         if (total != S->nnz_in) { err_ = "assembly_define: segments do not cover the nnz triplet values"; return false; }
+        qn_pair_clear();                            // (its view names segments of the assembly that ends here)
         own_asm.clear(); asm_.nseg = 0;
         asm_dirty = true; scale_valid = false;      // the sources are zero again: whatever was equilibrated last is another matrix
         double *asm_pool = nullptr, *asm_hpool = nullptr;
@@ -465,6 +469,7 @@ public:
             own_pd.clear(); pd_ready = false;
             lowrank_clear();
             lbfgs_clear();
+            qn_pair_clear();
             own_map.clear(); rmap = {};
             own_handle.clear(); h_vals = nullptr; h_stats = nullptr; ev0 = ev1 = nullptr; V.tvals = nullptr; d_user_scale = nullptr; prof_ev.clear(); prof_used = 0; prof_kind.clear();
             if (stream3) { (void)hipStreamDestroy(stream3); stream3 = nullptr; }
@@ -1712,6 +1717,147 @@ public:
         return true;
     }
 
+    // ---------------- the quasi-Newton pair (s, y) from the resident Jacobians (IpLimMemQuasiNewtonUpdater.cpp:276-308) ----------------
+    // qn_pair_define builds the column view of [J_c; J_d] (qn_pair_host.h) over two segments of the value assembly; qn_pair_store keeps x, grad_f and a COPY
+    // of the segments' current sources (the reference's last_x_, last_grad_f_, last_jac_c_, last_jac_d_); qn_pair_form runs k_qn_pair once over the
+    // current sources and the snapshot; qn_pair_push hands the formed device vectors to lbfgs_push.  Caller's numbering, like own_lb: survives
+    // factorisations and structure edits; assembly_define ends it (the segments it names are gone).  Everything runs on the solver's stream.
+    struct QnPair {                            // everything of the pair but its arena (own_qn): qn_pair_clear() is own_qn.clear(); qn = {};
+        QpState st; QpSegs g; int seg_jc = -1, seg_jd = -1, lpc = 0, maxlen = 0; long long nent = 0; double form_ms = 0;
+        const int *ptr = nullptr, *ent = nullptr;
+        double *x_last = nullptr, *gf_last = nullptr, *x_cur = nullptr, *gf_cur = nullptr, *s = nullptr, *y = nullptr, *lam = nullptr, *J_last = nullptr;
+        double* stage = nullptr;                                            // pinned: x | grad_f | y_c | y_d of one call
+        unsigned long long *amax_d = nullptr, *amax_h = nullptr;
+        hipEvent_t up = nullptr; bool up_pending = false;                   // the last upload out of `stage`: the next call waits for it before it writes there
+    } qn;
+    void qn_pair_clear() { own_qn.clear(); qn = {}; }
+    const QpState& qn_pair_state() const { return qn.st; }
+    int assembly_info(int seg, long long* off, long long* len) const {
+        if (seg >= 0 && seg < asm_.nseg) { if (off) *off = asm_.off[seg]; if (len) *len = asm_.len[seg]; }
+        return asm_.nseg;
+    }
+    void qn_pair_plan(int* out6) const {
+        out6[0] = qn.st.defined ? 1 : 0; out6[1] = qn.lpc; out6[2] = qn.maxlen; out6[3] = qn.st.nx; out6[4] = (int)(qn.nent & 0xffffffffll); out6[5] = (int)(qn.nent >> 32);
+    }
+    // host vectors of one call -> the pinned stage -> device, on the stream (dst[q] == nullptr or len[q] == 0: skipped)
+    bool qn_upload(const double* const* src, double* const* dst, const long long* len, int count) {
+        if (qn.up_pending) { HIPCHK(hipEventSynchronize(qn.up)); qn.up_pending = false; }
+        double* h = qn.stage;
+        for (int q = 0; q < count; ++q) {
+            if (!src[q] || !dst[q] || len[q] <= 0) continue;
+            std::memcpy(h, src[q], (size_t)len[q] * sizeof(double));
+            HIPCHK(hipMemcpyAsync(dst[q], h, (size_t)len[q] * sizeof(double), hipMemcpyHostToDevice, stream));
+            h += len[q];
+        }
+        HIPCHK(hipEventRecord(qn.up, stream)); qn.up_pending = true;
+        return true;
+    }
+    // the arguments have passed qp_check (api.cpp) with the segments g of the CURRENT assembly: nothing below can index out of range
+    bool qn_pair_define(const int32_t* dims4, const int32_t* irn, const int32_t* jcn, int seg_jc, int seg_jd, const QpSegs& g) {
+        DeviceGuard guard(dev);
+        if (!ready || asm_.nseg == 0) { err_ = "qn_pair_define: analyse() and assembly_define() first"; return false; }
+        if (multi) { err_ = "qn_pair_define: not supported on a multi-GPU handle"; return false; }
+        HIPCHK(hipStreamSynchronize(stream));
+        qn_pair_clear();
+        QpView v;
+        qp_build(dims4, irn, jcn, g, v);
+        const int nx = dims4[0], nc = dims4[2], nd = dims4[3];
+        qn.g = g; qn.seg_jc = g.len_jc > 0 ? seg_jc : -1; qn.seg_jd = g.len_jd > 0 ? seg_jd : -1; qn.nent = g.len_jc + g.len_jd; qn.maxlen = v.maxlen;
+        // qp_pick_lpc: from the structure alone.  (MI355X_KKT_TUNE=qn_lpc=1|8|64 forces an instantiation: tools/qn_pair_time.py measures the others with it)
+        const long long forced = knob_int("qn_lpc", 0);
+        qn.lpc = forced == 1 || forced == 8 || forced == 64 ? (int)forced : qp_pick_lpc(nx, qn.nent, v.maxlen);
+        DeviceOwner& O = own_qn;
+        const size_t nv = (size_t)nx, nl = (size_t)nc + nd;
+        if (!O.upload(v.ptr, &qn.ptr) || !O.upload(v.ent, &qn.ent) || !O.zeroed(&qn.x_last, nv) || !O.zeroed(&qn.gf_last, nv) || !O.zeroed(&qn.x_cur, nv) || !O.zeroed(&qn.gf_cur, nv) ||
+            !O.zeroed(&qn.s, nv) || !O.zeroed(&qn.y, nv) || !O.zeroed(&qn.lam, nl) || !O.zeroed(&qn.J_last, (size_t)qn.nent) || !O.pinned(&qn.stage, 2 * nv + nl) ||
+            !O.zeroed(&qn.amax_d, 1) || !O.pinned(&qn.amax_h, 1) || !O.event(&qn.up, hipEventDisableTiming)) { qn_pair_clear(); return false; }
+        HIPCHK(hipDeviceSynchronize());            // (the zero fills ran on the default stream: device_owner.h)
+        qn.st.nx = nx; qn.st.nc = nc; qn.st.nd = nd; qn.st.len_jc = g.len_jc; qn.st.len_jd = g.len_jd; qn.st.defined = true;
+        return true;
+    }
+    // x == nullptr: roll -- the vectors the last form was given become the snapshot's (the buffers change places: no copy, no upload)
+    bool qn_pair_store(const double* x, const double* gf, bool device) {
+        DeviceGuard guard(dev);
+        std::string why;
+        if (!qp_store_ok(qn.st, !x, why)) { err_ = "qn_pair_store: " + why; return false; }
+        const size_t vb = (size_t)qn.st.nx * sizeof(double);
+        bool has_gf = gf != nullptr;
+        if (!x) { std::swap(qn.x_last, qn.x_cur); std::swap(qn.gf_last, qn.gf_cur); has_gf = qn.st.formed_gf; }
+        else if (device) {
+            if (vb) HIPCHK(hipMemcpyAsync(qn.x_last, x, vb, hipMemcpyDeviceToDevice, stream));
+            if (vb && gf) HIPCHK(hipMemcpyAsync(qn.gf_last, gf, vb, hipMemcpyDeviceToDevice, stream));
+        } else {
+            const double* src[2] = {x, gf}; double* dst[2] = {qn.x_last, qn.gf_last}; const long long len[2] = {qn.st.nx, qn.st.nx};
+            if (!qn_upload(src, dst, len, 2)) return false;
+        }
+        // the snapshot of the Jacobians: the segments' SOURCES (scale and shift of the assembly do not enter), copied -- a later assembly_upload leaves it alone
+        if (qn.g.len_jc > 0) HIPCHK(hipMemcpyAsync(qn.J_last, asm_.src[qn.seg_jc], (size_t)qn.g.len_jc * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        if (qn.g.len_jd > 0) HIPCHK(hipMemcpyAsync(qn.J_last + qn.g.len_jc, asm_.src[qn.seg_jd], (size_t)qn.g.len_jd * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        if (x && device) HIPCHK(hipStreamSynchronize(stream));      // (the caller's vectors are free again when the call returns)
+        qn.st.stored = true; qn.st.stored_gf = has_gf; qn.st.formed = false;
+        return true;
+    }
+    template <int LPC> void qn_launch(const QpDev& Q, bool resto) {
+        const dim3 g(grid1d((long long)LPC * std::max(Q.nx, 1)));
+        if (resto) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_qn_pair<LPC, true>), g, dim3(256), 0, stream, Q);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_qn_pair<LPC, false>), g, dim3(256), 0, stream, Q);
+    }
+    // amax: max |s| over the row map's indices, or over all nx; nullptr: nothing is downloaded and (host vectors) nothing waited for
+    bool qn_pair_form(const double* x, const double* gf, const double* yc, const double* yd, bool device, double* amax) {
+        DeviceGuard guard(dev);
+        std::string why;
+        if (!qp_form_ok(qn.st, gf != nullptr, why)) { err_ = "qn_pair_form: " + why; return false; }
+        if (rmap.rows > 0 && rmap.h.back() >= qn.st.nx && amax) { err_ = "qn_pair_form: the row map reaches beyond the x block: amax_s cannot be taken over it"; return false; }
+        const auto t0 = std::chrono::steady_clock::now();
+        const long long nx = qn.st.nx, nc = qn.st.nc, nd = qn.st.nd;
+        const double* src[4] = {x, gf, yc, yd}; double* dst[4] = {qn.x_cur, qn.gf_cur, qn.lam, qn.lam + nc}; const long long len[4] = {nx, nx, nc, nd};
+        if (device) { for (int q = 0; q < 4; ++q) if (src[q] && len[q] > 0) HIPCHK(hipMemcpyAsync(dst[q], src[q], (size_t)len[q] * sizeof(double), hipMemcpyDeviceToDevice, stream)); }
+        else if (!qn_upload(src, dst, len, 4)) return false;
+        QpDev Q;
+        Q.nx = (int)nx; Q.len_jc = (int)qn.g.len_jc; Q.ptr = qn.ptr; Q.ent = (const int2*)qn.ent;
+        Q.jc = qn.seg_jc >= 0 ? asm_.src[qn.seg_jc] : nullptr; Q.jd = qn.seg_jd >= 0 ? asm_.src[qn.seg_jd] : nullptr; Q.jlast = qn.J_last; Q.lam = qn.lam;
+        Q.x = qn.x_cur; Q.xl = qn.x_last; Q.gf = qn.gf_cur; Q.gfl = qn.gf_last; Q.s = qn.s; Q.y = qn.y;
+        const bool resto = !gf;
+        if (nx > 0) { if (qn.lpc == 1) qn_launch<1>(Q, resto); else if (qn.lpc == 8) qn_launch<8>(Q, resto); else qn_launch<64>(Q, resto); }
+        HIPCHK(hipGetLastError());
+        if (amax) {
+            const int rows = rmap.rows > 0 ? rmap.rows : (int)nx;
+            HIPCHK(hipMemsetAsync(qn.amax_d, 0, sizeof(unsigned long long), stream));
+            if (rows > 0) hipLaunchKernelGGL(k_qn_amax, dim3(grid1d(rows)), dim3(256), 0, stream, (const double*)qn.s, rows, rmap.rows > 0 ? rmap.d : (const int*)nullptr, qn.amax_d);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(qn.amax_h, qn.amax_d, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));      // the one download and the one synchronisation of a form
+            std::memcpy(amax, qn.amax_h, sizeof(double));
+        } else if (device) HIPCHK(hipStreamSynchronize(stream));      // (the caller's device vectors are free again when the call returns)
+        qn.st.formed = true; qn.st.formed_gf = !resto;
+        qn.form_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return true;
+    }
+    // the formed device vectors through the existing push: under a row map as x-block vectors of nx entries (lbfgs_push_mapped, on_device), else the
+    // first `rows` entries (lbfgs_push_device); a restoration-phase history takes ypart and eta
+    bool qn_pair_push(double eta, int* outcome) {
+        std::string why;
+        const bool hist_resto = lb.defined && lb.par.resto;
+        if (!qp_push_ok(qn.st, lb.defined ? lb.rows : 0, hist_resto, rmap.rows, rmap.rows > 0 ? (long long)rmap.h.back() : -1, why)) { *outcome = 1; err_ = "qn_pair_push: " + why; return false; }
+        LbPush p{qn.s, qn.y, rmap.rows > 0 ? (long long)qn.st.nx : 0, true, hist_resto, hist_resto ? eta : 0.0};
+        return lbfgs_push(p, outcome);
+    }
+    bool qn_pair_get(int what, double* out, long long capacity) {
+        DeviceGuard guard(dev);
+        std::string why;
+        const long long need = qp_get_need(qn.st, what, why);
+        if (need < 0) { err_ = "qn_pair_get: " + why; return false; }
+        if (capacity < need) { err_ = "qn_pair_get: capacity is below the " + std::to_string(need) + " doubles of this array"; return false; }
+        HIPCHK(hipStreamSynchronize(stream));
+        const double* d = what == 0 ? qn.s : what == 1 ? qn.y : what == 2 ? qn.x_last : what == 3 ? qn.gf_last : what == 4 ? qn.J_last : qn.J_last + qn.g.len_jc;
+        if (need > 0) HIPCHK(hipMemcpy(out, d, (size_t)need * sizeof(double), hipMemcpyDeviceToHost));
+        return true;
+    }
+    void qn_pair_info(int* defined, int* stored, int* formed, int* nx, int64_t* nnz_j, double* form_ms) const {
+        if (defined) *defined = qn.st.defined; if (stored) *stored = qn.st.stored; if (formed) *formed = qn.st.formed;
+        if (nx) *nx = qn.st.nx; if (nnz_j) *nnz_j = qn.nent; if (form_ms) *form_ms = qn.form_ms;
+    }
+
     // ---------------- multi-GPU orchestration (eager launches) ----------------
     bool launch_fronts(const std::vector<FactorLaunch>& list) {
         if (!run_factor_list(list)) return false;
@@ -2025,6 +2171,16 @@ bool Numeric::lbfgs_reset() { return p_->lbfgs_reset(); }
 bool Numeric::lbfgs_clear() { DeviceGuard guard(p_->dev); if (p_->stream) (void)hipStreamSynchronize(p_->stream); p_->lbfgs_clear(); return true; }
 void Numeric::lbfgs_info(int* rows, int* max_history, int* memory, double* sigma, int* skipped_in_a_row, double* push_ms) const { p_->lbfgs_info(rows, max_history, memory, sigma, skipped_in_a_row, push_ms); }
 bool Numeric::lbfgs_get(int what, double* out, long long capacity) { return p_->lbfgs_get(what, out, capacity); }
+int  Numeric::assembly_info(int seg, long long* off, long long* len) const { return p_->assembly_info(seg, off, len); }
+bool Numeric::qn_pair_define(const int32_t* dims4, const int32_t* irn, const int32_t* jcn, int seg_jc, int seg_jd, const QpSegs& g) { return p_->qn_pair_define(dims4, irn, jcn, seg_jc, seg_jd, g); }
+bool Numeric::qn_pair_store(const double* x, const double* grad_f, bool device) { return p_->qn_pair_store(x, grad_f, device); }
+bool Numeric::qn_pair_form(const double* x, const double* grad_f, const double* y_c, const double* y_d, bool device, double* amax_s) { return p_->qn_pair_form(x, grad_f, y_c, y_d, device, amax_s); }
+bool Numeric::qn_pair_push(double eta, int* outcome) { return p_->qn_pair_push(eta, outcome); }
+bool Numeric::qn_pair_get(int what, double* out, long long capacity) { return p_->qn_pair_get(what, out, capacity); }
+void Numeric::qn_pair_info(int* defined, int* stored, int* formed, int* nx, int64_t* nnz_j, double* form_ms) const { p_->qn_pair_info(defined, stored, formed, nx, nnz_j, form_ms); }
+void Numeric::qn_pair_plan(int* out6) const { p_->qn_pair_plan(out6); }
+const QpState& Numeric::qn_pair_state() const { return p_->qn_pair_state(); }
+bool Numeric::qn_pair_clear() { DeviceGuard guard(p_->dev); if (p_->stream) (void)hipStreamSynchronize(p_->stream); p_->qn_pair_clear(); return true; }
 bool Numeric::ruiz_triplet(int device, int n, int nnz, const int* irn, const int* jcn, const double* a, int base, int sweeps, double* out, std::string& err)
 {
     int ndev = 0;

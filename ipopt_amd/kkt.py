@@ -78,6 +78,7 @@ ABI_SYMBOLS = [
     "mi355x_kkt_lbfgs_define_sr1", "mi355x_kkt_lbfgs_undo", "mi355x_kkt_lbfgs_sr1_info", "mi355x_kkt_lbfgs_sr1_coefficients",
     "mi355x_kkt_lbfgs_define_resto", "mi355x_kkt_lbfgs_push_resto", "mi355x_kkt_lbfgs_push_resto_device", "mi355x_kkt_lbfgs_resto_info",
     "mi355x_kkt_lowrank_rowmap", "mi355x_kkt_lowrank_rowmap_get", "mi355x_kkt_lowrank_rowmap_check", "mi355x_kkt_lbfgs_push_mapped", "mi355x_kkt_lbfgs_push_resto_mapped",
+    "mi355x_kkt_qn_pair_check", "mi355x_kkt_qn_pair_define", "mi355x_kkt_qn_pair_store", "mi355x_kkt_qn_pair_form", "mi355x_kkt_qn_pair_push", "mi355x_kkt_qn_pair_get", "mi355x_kkt_qn_pair_info", "mi355x_kkt_qn_pair_clear",
 ]
 LOWRANK_MAX = 32
 LBFGS_MAX = 32
@@ -175,6 +176,14 @@ def load_library():
     lib.mi355x_kkt_lowrank_rowmap_check.argtypes = [C.c_int64, C.c_int, vp, C.c_int64, C.c_char_p, C.c_int64]
     lib.mi355x_kkt_lbfgs_push_mapped.argtypes = [vp, vp, vp, C.c_int64, C.c_int, ip]
     lib.mi355x_kkt_lbfgs_push_resto_mapped.argtypes = [vp, vp, vp, C.c_int64, C.c_int, C.c_double, ip]
+    lib.mi355x_kkt_qn_pair_check.argtypes = [C.c_int64, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_char_p, C.c_int64]
+    lib.mi355x_kkt_qn_pair_define.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
+    lib.mi355x_kkt_qn_pair_store.argtypes = [vp, vp, vp, C.c_int]
+    lib.mi355x_kkt_qn_pair_form.argtypes = [vp, vp, vp, vp, vp, C.c_int, dp]
+    lib.mi355x_kkt_qn_pair_push.argtypes = [vp, C.c_double, ip]
+    lib.mi355x_kkt_qn_pair_get.argtypes = [vp, C.c_int, vp, C.c_int64]
+    lib.mi355x_kkt_qn_pair_info.argtypes = [vp, ip, ip, ip, ip, C.POINTER(C.c_int64), dp]
+    lib.mi355x_kkt_qn_pair_clear.argtypes = [vp]
     lib.mi355x_kkt_set_comm_rccl.argtypes = [vp, vp]
     lib.mi355x_kkt_comm_shm_id.argtypes = [vp, C.c_int]
     lib.mi355x_kkt_set_comm_shm.argtypes = [vp, vp]
@@ -220,6 +229,21 @@ def lowrank_rowmap_check(n, idx, length=-1):
     idx = np.ascontiguousarray(idx, dtype=np.int32)
     msg = C.create_string_buffer(512)
     st = load_library().mi355x_kkt_lowrank_rowmap_check(int(n), idx.size, idx.ctypes.data if idx.size else None, int(length), msg, 512)
+    return st == 0, msg.value.decode()
+
+
+def qn_pair_check(nnz, dims4, irn, jcn, off_jc, len_jc, off_jd, len_jd):
+    """host only, no handle, no GPU: (ok, reason) of include/mi355x_kkt.h's mi355x_kkt_qn_pair_check -- the validation qn_pair_define performs on
+    dims4 = (nx, ns, nc, nd), the 1-based triplets and the ranges [off, off + len) of the J_c and J_d segments in the triplet list"""
+    d = np.ascontiguousarray(dims4, dtype=np.int32)
+    if d.shape != (4,):
+        raise KKTError("qn_pair_check: dims4 must hold nx, ns, nc, nd")
+    r = np.ascontiguousarray(irn, dtype=np.int32); c = np.ascontiguousarray(jcn, dtype=np.int32)
+    if r.ndim != 1 or r.shape != c.shape or r.size < int(nnz):
+        raise KKTError("qn_pair_check: irn and jcn must be vectors of nnz entries")
+    msg = C.create_string_buffer(512)
+    st = load_library().mi355x_kkt_qn_pair_check(int(nnz), d.ctypes.data, r.ctypes.data if r.size else None, c.ctypes.data if c.size else None,
+                                                 int(off_jc), int(len_jc), int(off_jd), int(len_jd), msg, 512)
     return st == 0, msg.value.decode()
 
 
@@ -330,6 +354,7 @@ class KKTSolver:
         if self.lib.mi355x_kkt_assembly_define(self._h, len(ln), off.ctypes.data, ln.ctypes.data) != 0:
             raise KKTError("assembly_define: " + self.last_error())
         self._seg_len = ln
+        self._qn_dims = self._qn_segs = None      # (a new assembly ends a qn_pair definition)
 
     def assembly_set(self, seg, values):
         p = self.lib.mi355x_kkt_assembly_buffer(self._h, int(seg))
@@ -614,6 +639,97 @@ class KKTSolver:
         if self.lib.mi355x_kkt_lbfgs_resto_info(self._h, C.byref(r), C.byref(sp), C.byref(eta)) != 0:
             raise KKTError("lbfgs_resto_info: " + self.last_error())
         return {"resto": bool(r.value), "special": bool(sp.value), "eta": eta.value}
+
+    # --- the quasi-Newton pair (s, y) formed on the device from the resident Jacobians (include/mi355x_kkt.h; reference IpLimMemQuasiNewtonUpdater.cpp:276-308) ---
+    def qn_pair_define(self, dims4, irn, jcn, seg_jc, seg_jd):
+        """dims4 = (nx, ns, nc, nd); irn, jcn: the 1-based triplets of initialize_structure; seg_jc, seg_jd: the assembly segments of J_c, J_d (negative: absent)"""
+        d = np.ascontiguousarray(dims4, dtype=np.int32)
+        if d.shape != (4,):
+            raise KKTError("qn_pair_define: dims4 must hold nx, ns, nc, nd")
+        r = np.ascontiguousarray(irn, dtype=np.int32); c = np.ascontiguousarray(jcn, dtype=np.int32)
+        if r.shape != (self._nnz,) or c.shape != (self._nnz,):
+            raise KKTError("qn_pair_define: irn and jcn must be the nnz triplets of initialize_structure")
+        if self.lib.mi355x_kkt_qn_pair_define(self._h, d.ctypes.data, r.ctypes.data if r.size else None, c.ctypes.data if c.size else None, int(seg_jc), int(seg_jd)) != 0:
+            raise KKTError("qn_pair_define: " + self.last_error())
+        self._qn_dims = [int(v) for v in d]
+        self._qn_segs = tuple(int(self._seg_len[q]) if q >= 0 else 0 for q in (int(seg_jc), int(seg_jd)))
+
+    def _qn_vec(self, name, v, k):
+        if v is None:
+            return None
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if k is not None and v.shape != (k,):      # (k None: nothing is defined, which the library says itself)
+            raise KKTError(f"{name} must be a vector of {k}")
+        return v
+
+    def _qn_len(self):
+        return getattr(self, "_qn_dims", None) or [None, None, None, None]
+
+    def qn_pair_store(self, x=None, grad_f=None):
+        """x, grad_f: host vectors of nx; grad_f None: the restoration variant; x None: roll (the vectors of the last qn_pair_form become the snapshot's)"""
+        nx = self._qn_len()[0]
+        x = self._qn_vec("qn_pair_store: x", x, nx); grad_f = self._qn_vec("qn_pair_store: grad_f", grad_f, nx)
+        if self.lib.mi355x_kkt_qn_pair_store(self._h, None if x is None else x.ctypes.data, None if grad_f is None else grad_f.ctypes.data, 0) != 0:
+            raise KKTError("qn_pair_store: " + self.last_error())
+
+    def qn_pair_store_device(self, dx_ptr, dgf_ptr=None):
+        """device vectors of nx, complete before the call; dgf_ptr None / 0: the restoration variant"""
+        if self.lib.mi355x_kkt_qn_pair_store(self._h, C.c_void_p(dx_ptr), C.c_void_p(dgf_ptr) if dgf_ptr else None, 1) != 0:
+            raise KKTError("qn_pair_store: " + self.last_error())
+
+    def qn_pair_form(self, x, grad_f, y_c, y_d, amax=True):
+        """host vectors of nx, nx, nc, nd (grad_f None: the restoration variant; y_c / y_d may be None or empty for an absent block); -> max |s| (over the
+        row map's indices when one is set), or None with amax=False (then nothing is downloaded)"""
+        nx, _, nc, nd = self._qn_len()
+        x = self._qn_vec("qn_pair_form: x", x, nx); grad_f = self._qn_vec("qn_pair_form: grad_f", grad_f, nx)
+        y_c = self._qn_vec("qn_pair_form: y_c", y_c if nc else None, nc); y_d = self._qn_vec("qn_pair_form: y_d", y_d if nd else None, nd)
+        p = lambda v: None if v is None else v.ctypes.data      # (a vector of 0 entries still has an address: grad_f of nx = 0 is not "absent")
+        a = C.c_double(0.0)
+        if self.lib.mi355x_kkt_qn_pair_form(self._h, p(x), p(grad_f), p(y_c), p(y_d), 0, C.byref(a) if amax else None) != 0:
+            raise KKTError("qn_pair_form: " + self.last_error())
+        return a.value if amax else None
+
+    def qn_pair_form_device(self, dx_ptr, dgf_ptr, dyc_ptr, dyd_ptr, amax=True):
+        """device vectors, complete before the call and free again when it returns; a pointer None / 0: absent"""
+        q = lambda v: C.c_void_p(v) if v else None
+        a = C.c_double(0.0)
+        if self.lib.mi355x_kkt_qn_pair_form(self._h, q(dx_ptr), q(dgf_ptr), q(dyc_ptr), q(dyd_ptr), 1, C.byref(a) if amax else None) != 0:
+            raise KKTError("qn_pair_form: " + self.last_error())
+        return a.value if amax else None
+
+    def qn_pair_push(self, eta=0.0) -> int:
+        """the formed device vectors into the defined history (eta: a restoration-phase history only); -> outcome as lbfgs_push"""
+        oc = C.c_int(0)
+        if self.lib.mi355x_kkt_qn_pair_push(self._h, float(eta), C.byref(oc)) != 0:
+            raise KKTError("qn_pair_push: " + self.last_error())
+        return oc.value
+
+    def qn_pair_get(self, what) -> np.ndarray:
+        """what: "s" | "y" | "x_last" | "grad_f_last" | "Jc_last" | "Jd_last", or 0..5"""
+        w = {"s": 0, "y": 1, "x_last": 2, "grad_f_last": 3, "Jc_last": 4, "Jd_last": 5}.get(what, what)
+        I = self.qn_pair_info()
+        out = np.zeros(I["nx"] if w <= 3 else I["len_jc"] if w == 4 else I["len_jd"])
+        if self.lib.mi355x_kkt_qn_pair_get(self._h, int(w), out.ctypes.data if out.size else None, out.size) != 0:
+            raise KKTError("qn_pair_get: " + self.last_error())
+        return out
+
+    def qn_pair_info(self) -> dict:
+        """defined, stored, formed, nx, nnz_j (entries of the column view), form_ms; and from the launch report: lpc (lanes per column of the kernel),
+        max_column (its longest column); len_jc, len_jd as qn_pair_define saw the segments"""
+        d, st, f, nx, nz, ms = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0), C.c_double(0.0)
+        if self.lib.mi355x_kkt_qn_pair_info(self._h, C.byref(d), C.byref(st), C.byref(f), C.byref(nx), C.byref(nz), C.byref(ms)) != 0:
+            raise KKTError("qn_pair_info: " + self.last_error())
+        plan = self.launch_plan("qn_pair")
+        out = {"defined": bool(d.value), "stored": bool(st.value), "formed": bool(f.value), "nx": nx.value, "nnz_j": nz.value, "form_ms": ms.value,
+               "lpc": int(plan[1]), "max_column": int(plan[2]), "len_jc": 0, "len_jd": 0}
+        if d.value and getattr(self, "_qn_segs", None) is not None:
+            out["len_jc"], out["len_jd"] = self._qn_segs
+        return out
+
+    def qn_pair_clear(self):
+        if self.lib.mi355x_kkt_qn_pair_clear(self._h) != 0:
+            raise KKTError("qn_pair_clear: " + self.last_error())
+        self._qn_dims = self._qn_segs = None
 
     # --- multi-GPU communicator (include/mi355x_kkt.h): after one of these, multi_solve / factor_device / solve_device* of a
     #     handle created with nranks > 1 run the distributed sequence inside the library ---
