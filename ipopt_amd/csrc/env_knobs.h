@@ -3,8 +3,9 @@
 //
 //   MI355X_KKT_DISABLE=name[,name...]   switches a KEPT fast path off, so that the tests can compare it bitwise with the plain path underneath:
 //       lookahead chain_solve fuse_dt fastpiv asm_pull pair_solve selfasm xcd_tiles xcd_affine fuse_upd grouped tfuse leafchain side_small
-//       front_df p1_small norestore optimistic subcomm blockcache thread_pool purify solve_ctx keep_scale mid_solve
+//       front_df p1_small norestore optimistic subcomm blockcache thread_pool purify solve_ctx keep_scale mid_solve trsm_regs
 //       (mid_solve: the load-batched solve kernels of the fronts of order 33..128, k_fwd_mid / k_bwd_mid; off: k_fwd / k_bwd -- numeric.hip reads it itself)
+//       (trsm_regs: the panel solve of the fronts with k <= 64 with its L11 operands in registers, trsm_rows_regs; off: trsm_rows_impl with L11 staged in LDS -- numeric.hip reads it itself)
 //   MI355X_KKT_TUNE=name=value[,...]    numeric thresholds of the schedule (defaults are the measured optima; tests force a path with them):
 //       la_wgs la_min_nt la_min_tiles grp_rbw_max grp_maxchains fuse_dt_maxwg chain_solve_maxc fastpiv_floor
 //       (qn_lpc=1|8|64: the lanes per column of k_qn_pair instead of qp_pick_lpc's choice, read by qn_pair_define: tools/qn_pair_time.py measures the alternatives)

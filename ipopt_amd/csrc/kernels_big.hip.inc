@@ -356,7 +356,11 @@ __device__ __forceinline__ void trsm_rows_impl(const DevView& V, const FrontMeta
         const int i = ibase + r;
         const bool ok0 = i < m && r < rlim, ok1 = i + 1 < m && r + 1 < rlim;
         double* Wv = W + i; double* Pv = P + i; double uv = V.pivtol; double* Auv = T.Au ? T.Au + r : nullptr; const double* Asv = As + r;
-        asm volatile("" : "+v"(Wv), "+v"(Pv), "+v"(uv), "+v"(Auv), "+v"(Asv));
+        // (Asv is NOT pinned: behind the asm its address space is unknown, the loads become FLAT ones, and the loop's base pointer is biased by the
+        //  Asv[(j - 1) * 65] of a 2x2 pivot's second column to Asv - 520 with an instruction offset of 520 -- the hardware picks the aperture of a flat
+        //  access from the base alone, and As starts the workgroup's LDS: for j < 8 the base lies BELOW the LDS aperture and the load of a rejected block's
+        //  panel faults, HSA_STATUS_ERROR_MEMORY_APERTURE_VIOLATION.  Left to the compiler the accesses are ds_read: no aperture, no flat path)
+        asm volatile("" : "+v"(Wv), "+v"(Pv), "+v"(uv), "+v"(Auv));
         if (Auv) for (int j = k + jq; j < kp16; j += 8) { Auv[j * 65] = 0.0; Auv[1 + j * 65] = 0.0; }
         bool big = false;
         if (his) {        // behind the blocked factorisation every pivot is 1x1: straight-line body
@@ -560,7 +564,183 @@ __device__ __forceinline__ void trsm_store_l(const DevView& V, const FrontMeta& 
         else if (ok0) P[i + (size_t)j * ldp] = Lr[r + j * 65];
     }
 }
-template <bool WIDEK>          // WIDEK: the level has panels of more than 64 columns (wide_panels option): L11 is not staged in LDS
+// The panel solve of k_big_trsm for k <= 64 with the L11 operands in REGISTERS (MI355X_KKT_DISABLE=trsm_regs: trsm_rows_impl<true> as before).
+// trsm_rows_impl stages L11 in LDS (Ls, 33 KB at k = 64, half of it zeros): 76.8 KB per workgroup, two workgroups per CU, and the launches ran at the
+// latency of a workgroup's load chain (record -> pivot data, L11 -> barrier -> panel rows through lperm) times the rounds of resident workgroups.
+// The column loop reads L11 only as the strictly sub-diagonal 16 x 16 blocks, each as the MFMA operand L11(c16 + l15, 4u + l4), 4u < c16: 24 doubles per
+// lane, the same set in every wavefront -- loaded here straight from the panel in that layout.  The layout is trsm_layout(.., no_ls = true): As, Is, pivot
+// data, 43.5 KB at k = 64, three workgroups per CU.  The panel rows are requested in NATURAL column order in the same batch as everything else -- behind
+// the blocked factorisation (hasis: natural pivot order, 1x1 pivots) that is the order wanted and nothing waits for hasis or lperm; behind the strict loop
+// the rows are permuted in place (the in_as branch of trsm_rows_impl) and the diagonal blocks inverted from the panel (Lat() of STAGED_L = false).
+// Operand values and MFMA sequence are those of trsm_rows_impl: W21, L21 and the failed-pivot marks come out bit for bit the same.
+// (host side: bytes of trsm_layout(.., k, false, true))
+static size_t trsm_regs_lds_bytes(int k)
+{
+    const size_t kp16 = (size_t)((k + 15) & ~15);
+    return (65 * kp16 + 17 * kp16 + 2 * (size_t)k) * sizeof(double) + (size_t)(2 * k + 2) * sizeof(int) + 16;
+}
+__device__ __forceinline__ void trsm_rows_regs(const DevView& V, const FrontMeta& M, const TrsmLds& T, const int ibase)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const int s = M.s, c0 = M.c0, k = M.k, m = M.m;
+    double* P = V.L + M.panel_off;
+    const size_t ldp = (size_t)M.ldp;
+    double* W = V.wbuf + M.wb;
+    double* As = T.As; const double* Ds = T.Ds; const int* Ts = T.Ts;
+    const int kp16 = T.kp16;      // (<= 64)
+    // ONE batch of independent loads: pivot data, hasis, the diagonal-block inverses, the L11 operands, my rows of the panel
+    const bool pj = tid < k;
+    const double dv = pj ? V.dinv[c0 + tid] : 0.0, fv = pj ? V.doff[c0 + tid] : 0.0;
+    const int tv = pj ? V.ptype[c0 + tid] : 0, pv = pj ? V.lperm[c0 + tid] : 0;
+    const int his = V.hasis[s];
+    const int nis = (kp16 >> 4) * 272;
+    double isv[5];
+    {
+        const double* Ig = V.isg + (size_t)M.bigidx * ISG_STRIDE;
+#pragma unroll
+        for (int u = 0; u < 5; ++u) { const int idx = tid + 256 * u; isv[u] = (idx < nis) ? Ig[idx] : 0.0; }
+    }
+    double l11[24];               // block row b = 1, 2, 3 (columns [0, 16 b)): l11[2 b (b - 1) + u] = L11(16 b + l15, 4 u + l4), u < 4 b
+#pragma unroll
+    for (int b = 1; b < 4; ++b)
+#pragma unroll
+        for (int u = 0; u < 4 * b; ++u) { const int i = 16 * b + l15; l11[2 * b * (b - 1) + u] = (i < k) ? P[i + (size_t)(4 * u + l4) * ldp] : 0.0; }      // (column < 16 b <= i: strictly lower)
+    {
+        const int r = tid & 63, pq = tid >> 6;
+        double av[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) { const int p = pq + 4 * u; av[u] = (p < k && ibase + r < m) ? P[ibase + r + (size_t)p * ldp] : 0.0; }
+        if (pj) { T.Ds[tid] = dv; T.Ds[k + tid] = fv; T.Ts[tid] = tv; T.Lp[tid] = pv; }
+        if (his) {
+#pragma unroll
+            for (int u = 0; u < 5; ++u) { const int idx = tid + 256 * u; if (idx < nis) T.Is[idx] = isv[u]; }
+        }
+#pragma unroll
+        for (int u = 0; u < 16; ++u) { const int p = pq + 4 * u; if (p < kp16) As[r + p * 65] = av[u]; }
+    }
+    __syncthreads();
+    if (!his) {      // (workgroup-uniform; rare) behind the strict loop: the columns in pivot order, the diagonal blocks inverted by a 16-lane register substitution
+        const int r = tid & 63, pq = tid >> 6;
+        double av[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) { const int p = pq + 4 * u; av[u] = (p < k) ? As[r + T.Lp[p] * 65] : 0.0; }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 16; ++u) { const int p = pq + 4 * u; if (p < kp16) As[r + p * 65] = av[u]; }
+        auto Lat = [&](int i, int c) -> double { return (i < k && c < k && i > c) ? P[i + (size_t)c * ldp] : 0.0; };      // L11(i, c), strictly lower part, zero elsewhere
+        if (16 * wave < kp16) {      // block `wave` (kp16 <= 64: at most one per wavefront)
+            // the diagonal block goes through the place of its inverse, fetched in one round trip by the whole wavefront (unrolled over Lat() the
+            // substitution keeps its 120 loads in 240 registers); a wavefront's LDS accesses stay in program order: every read below precedes the stores
+            const int o = 16 * wave;
+            double* Ib = T.Is + wave * 272;
+            double lv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) lv[u] = Lat(o + l15, o + 4 * u + l4);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) Ib[l15 + (4 * u + l4) * 17] = lv[u];
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();
+            double x[16];                    // x = column `lane` of the inverse; column-oriented substitution: independent updates per step
+#pragma unroll
+            for (int i = 0; i < 16; ++i) x[i] = (i == lane) ? 1.0 : 0.0;
+            if (lane < 16) {
+#pragma unroll
+                for (int pp = 0; pp < 15; ++pp) {
+                    const double xp = (pp >= lane) ? x[pp] : 0.0;
+#pragma unroll
+                    for (int i = pp + 1; i < 16; ++i) x[i] = fma(-Ib[i + pp * 17], xp, x[i]);
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();
+            if (lane < 16) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) Ib[i + lane * 17] = x[i];
+            }
+        }
+        __syncthreads();
+    }
+    // the blocked substitution: trsm_rows_impl's column loop with the sub-diagonal operands out of l11[] (unrolled: registers are indexed statically)
+    const int r16 = wave * 16;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const int c16 = 16 * b;
+        if (c16 < kp16) {
+            v4f64 acc = (v4f64){0.0, 0.0, 0.0, 0.0};
+            double ob[12];
+#pragma unroll
+            for (int u = 0; u < 4 * b; ++u) ob[u] = As[r16 + l15 + (4 * u + l4) * 65];
+#pragma unroll
+            for (int u = 0; u < 4 * b; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(l11[2 * b * (b - 1) + u], ob[u], acc, 0, 0, 0);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) As[r16 + l15 + (c16 + l4 + 4 * g) * 65] -= acc[g];
+            double bv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) bv[u] = As[r16 + l15 + (c16 + 4 * u + l4) * 65];
+            const double* Ib = T.Is + b * 272;
+            v4f64 w = (v4f64){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int u = 0; u < 4; ++u) w = __builtin_amdgcn_mfma_f64_16x16x4f64(Ib[l15 + (4 * u + l4) * 17], bv[u], w, 0, 0, 0);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) As[r16 + l15 + (c16 + l4 + 4 * g) * 65] = w[g];
+        }
+    }
+    __syncthreads();
+    // L21 = W21 D^{-1}, the stores and the a posteriori threshold test: trsm_rows_impl's (two consecutive rows per lane, 16-byte stores, the loop-invariant
+    // pieces of the view pinned in VGPRs), without the staging copy
+    {
+        const int r = 2 * (tid & 31), jq = tid >> 5;
+        const int i = ibase + r;
+        const bool ok0 = i < m, ok1 = i + 1 < m;
+        double* Wv = W + i; double* Pv = P + i; double uv = V.pivtol; const double* Asv = As + r;
+        asm volatile("" : "+v"(Wv), "+v"(Pv), "+v"(uv));      // (not Asv: see trsm_rows_impl)
+        auto lval = [&](int j, double& l0, double& l1) {
+            const int pt = Ts[j];
+            const double w0 = Asv[j * 65], w1 = Asv[1 + j * 65];
+            if (pt == 1) { l0 = w0 * Ds[j]; l1 = w1 * Ds[j]; }
+            else if (pt == 2) { l0 = Ds[j] * w0 + Ds[k + j] * Asv[(j + 1) * 65]; l1 = Ds[j] * w1 + Ds[k + j] * Asv[1 + (j + 1) * 65]; }
+            else { l0 = Ds[k + j - 1] * Asv[(j - 1) * 65] + Ds[j] * w0; l1 = Ds[k + j - 1] * Asv[1 + (j - 1) * 65] + Ds[j] * w1; }
+        };
+        bool big = false;
+        if (his) {        // behind the blocked factorisation every pivot is 1x1: straight-line body
+#pragma unroll 4
+            for (int j = jq; j < k; j += 8) {
+                const double d = Ds[j];
+                const double w0 = Asv[j * 65], w1 = Asv[1 + j * 65];
+                const double l0 = w0 * d, l1 = w1 * d;
+                if (ok1) {
+                    *reinterpret_cast<double2a*>(&Wv[(size_t)j * m]) = (double2a){w0, w1};
+                    *reinterpret_cast<double2a*>(&Pv[(size_t)j * ldp]) = (double2a){l0, l1};
+                } else if (ok0) { Wv[(size_t)j * m] = w0; Pv[(size_t)j * ldp] = l0; }
+                big |= (ok0 && fabs(l0) * uv > 1.0) || (ok1 && fabs(l1) * uv > 1.0);
+            }
+        } else {
+            for (int j = jq; j < k; j += 8) {
+                const double w0 = Asv[j * 65], w1 = Asv[1 + j * 65];
+                double l0, l1;
+                lval(j, l0, l1);
+                if (ok1) {
+                    *reinterpret_cast<double2a*>(&Wv[(size_t)j * m]) = (double2a){w0, w1};
+                    *reinterpret_cast<double2a*>(&Pv[(size_t)j * ldp]) = (double2a){l0, l1};
+                } else if (ok0) { Wv[(size_t)j * m] = w0; Pv[(size_t)j * ldp] = l0; }
+                big |= (ok0 && fabs(l0) * uv > 1.0) || (ok1 && fabs(l1) * uv > 1.0);
+            }
+        }
+        // a multiplier above 1/u somewhere in my rows (rare): find the columns and count each once
+        if (__ballot(big) != 0ull) {
+            for (int j = jq; j < k; j += 8) {
+                const int pt = Ts[j];
+                double l0, l1;
+                lval(j, l0, l1);
+                if (((ok0 && fabs(l0) * uv > 1.0) || (ok1 && fabs(l1) * uv > 1.0)) && atomicExch(&V.colfail[c0 + j], 1) == 0) {
+                    atomicAdd(&V.apfail[s], 1);
+                    atomicOr(&V.zpiv[c0 + T.Lp[j]], 2);                    // a delayed pivot: the column (and its 2x2 partner) should have waited for the parent front
+                    if (pt != 1) atomicOr(&V.zpiv[c0 + T.Lp[pt == 2 ? j + 1 : j - 1]], 2);
+                }
+            }
+        }
+    }
+}
+template <bool WIDEK, bool REGS = false>          // WIDEK: the level has panels of more than 64 columns (wide_panels option): L11 is not staged in LDS; REGS: trsm_rows_regs (k <= 64)
 __global__ __launch_bounds__(256) void k_big_trsm(DevView V, int list_off, int rb0)
 {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -577,8 +757,9 @@ __global__ __launch_bounds__(256) void k_big_trsm(DevView V, int list_off, int r
         for (int q = M.aq0 + tid; q < M.aq1; q += 256) { const int pos = V.apos[q]; const int i = pos % m, c = pos / m; if (i >= ibase && i < ibase + 64) P[i + (size_t)c * ldp] += V.aval[q]; }
         __syncthreads();
     }
-    const TrsmLds T = trsm_layout(smem_raw, k, false, WIDEK);
-    trsm_rows_impl<!WIDEK>(V, M, T, ibase);
+    const TrsmLds T = trsm_layout(smem_raw, k, false, WIDEK || REGS);
+    if (REGS) trsm_rows_regs(V, M, T, ibase);
+    else      trsm_rows_impl<!WIDEK>(V, M, T, ibase);
 }
 
 // 32 x 32 block (rows i0.., columns cc0.. of the trailing matrix T of order mu) of  T -= sum over the links j0..jlast of a chain group  W L^T  on ONE wavefront,

@@ -721,7 +721,9 @@ public:
             case FO_REG_256_6:       LAUNCH_ON(r.kind, q, (k_front_reg<256, 6>), grid, block, lds, q, V, r.b0, a[0]); break;
             case FO_REG_256_8_FAST:  LAUNCH_ON(r.kind, q, (k_front_reg<256, 8, true>), grid, block, lds, q, V, r.b0, a[0]); break;
             case FO_REG_256_6_FAST4: LAUNCH_ON(r.kind, q, (k_front_reg<256, 6, true, 4>), grid, block, lds, q, V, r.b0, a[0]); break;
-            case FO_TRSM:            LAUNCH_ON(r.kind, q, k_big_trsm<false>, grid, block, trsm_lds_bytes(a[0], false), q, V, r.b0, 0); break;
+            case FO_TRSM:            if (trsm_regs_on) LAUNCH_ON(r.kind, q, (k_big_trsm<false, true>), grid, block, trsm_regs_lds_bytes(a[0]), q, V, r.b0, 0);      // (43.5 KB at k = 64: under the default limit, not in allow_large_lds())
+                                     else              LAUNCH_ON(r.kind, q, k_big_trsm<false>, grid, block, trsm_lds_bytes(a[0], false), q, V, r.b0, 0);
+                                     break;
             case FO_TRSM_WIDE:       LAUNCH_ON(r.kind, q, k_big_trsm<true>, grid, block, trsm_lds_bytes(a[0], false), q, V, r.b0, 0); break;
             case FO_DIAG_TRSM:       LAUNCH_ON(r.kind, q, k_big_diag_trsm, grid, block, std::max(diag_lds_bytes(a[1], 64), trsm_lds_bytes(a[1], true)), q, V, r.b0, a[0]); break;
             case FO_GRP_FUSED:       LAUNCH_ON(r.kind, q, k_grp_fused, grid, block, std::max(diag_lds_bytes(64, 64), GRP_DB_BYTES + trsm_lds_bytes(64, a[0] != 0)), q, V, r.b0, a[0], a[1], 0); break;
@@ -792,6 +794,7 @@ public:
     }
 
     bool norestore_on = !knob_disabled("norestore");      // (development knob: keep the safety copies of the pivot blocks in the optimistic schedule too)
+    bool trsm_regs_on = !knob_disabled("trsm_regs");      // FO_TRSM launches k_big_trsm<false, true> (trsm_rows_regs: L11 operands in registers, three workgroups per CU); off: k_big_trsm<false> with the staged L11
     bool optimistic = false;                 // (set per factorisation: which of P.factor_single runs)
     bool optimistic_ok = true;               // the optimistic schedule may be tried (false while a back-off runs: see factor())
     int  opt_backoff = 0, opt_wait = 0;      // after a fall-back: opt_wait factorisations on the full schedule, then one more optimistic try; every repeat doubles the wait (8 .. 256)
