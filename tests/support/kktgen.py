@@ -196,6 +196,22 @@ def block_diag(*systems):
     return _finish(off, rows, cols, vals) + (negs,)
 
 
+def with_diagonal(system, variables, value):
+    """the system with the WHOLE diagonal entry of each of `variables` (0-based) set to `value` (one value, or one per variable): every diagonal triplet
+    of the variable is zeroed -- the H diagonal and Sigma are separate triplets (kkt_from_blocks) -- and the value goes into the first of them.
+    Structure and couplings are untouched, so a tiny value against O(1) couplings is a pivot that the static-order kernels must reject.  The inertia is
+    no longer known by construction: None."""
+    n, r, c, v, _ = system
+    v = v.copy()
+    values = np.broadcast_to(np.asarray(value, dtype=np.float64), (len(variables),))
+    for x, val in zip(variables, values):
+        at = np.nonzero((r == c) & (r == int(x) + 1))[0]
+        assert at.size >= 1, x
+        v[at] = 0.0
+        v[at[0]] = val
+    return n, r, c, v, None
+
+
 def to_scipy(n, row, col, val):
     """full symmetric scipy CSR matrix of a one-triangle triplet list (duplicates summed)."""
     import scipy.sparse as sp

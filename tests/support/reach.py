@@ -99,6 +99,83 @@ def solve_reach(s):
     return F
 
 
+def small_reach(s):
+    """What the ONE-WAVEFRONT fronts (class FC_WAVE, order <= 32) of an analysed handle reach, under the MI355X_KKT_DISABLE / MI355X_KKT_TUNE of the moment.
+    Solve side (numeric.hip solve_sweep / solve_level restated): the leaf-chain prefix of k_fwd_leafchain / k_bwd_leafchain, and per level outside it and
+    outside the chain segments the instantiation taken -- "16x16" (k_*_pair<16, 16>: every front of the level of order <= 16, four per wavefront), "16"
+    (k_*_pair<16>: k <= 16), "32" (k_*_pair<32>), "k64" (k_fwd<64> / k_bwd<64>, pair_solve off).  Factor side (counted from the exported plan): the leaf
+    chains with their lengths and the input entries of their links, the data-flow runs with the fronts of order 17 .. 32 and the tagged contribution
+    squares inside them (launch_plan.cpp: a front of a run whose parent is a front of the same run publishes a 16- or 32-wide square), the launches of
+    the two factor schedules.  Sets are returned as sorted lists, histograms as sorted lists of (value, count)."""
+    I = s.info()
+    nl, nsn = I.num_levels, I.num_sn
+    colptr = s.symbolic(1, nsn + 1)
+    order = np.diff(s.symbolic(2, nsn + 1)); cols = np.diff(colptr)
+    parent, cls, level, alias = s.symbolic(4, nsn), s.symbolic(23, nsn), s.symbolic(5, nsn), s.symbolic(17, nsn)
+    acolptr = s.symbolic(7, I.n + 1)
+    lp = s.symbolic(13, nl * FC_COUNT + 1)
+    nchild = np.bincount(parent[parent >= 0], minlength=nsn)
+    gathered = nchild - (alias >= 0)
+    upd = order - cols
+    entries = acolptr[colptr[1:]] - acolptr[colptr[:-1]]      # input entries of a front's pivot columns (FrontMeta aq0 .. aq1)
+    wave = cls == FC_WAVE
+    A = {w: s.launch_plan(w).copy() for w in ("scalars", "path_scalars", "levels", "chain_segs", "lc_ptr", "lc_fronts", "df_runs", "tiny16",
+                                              "factor.single.full", "factor.single.opt")}
+    pair_solve, lc_levels, lc_nchains = int(A["path_scalars"][0]), int(A["scalars"][2]), int(A["scalars"][3])
+    lvl = A["levels"].reshape(-1, 10)
+    wave_mmax, wave_kmax = lvl[:, 8], lvl[:, 9]
+    in_seg = np.zeros(nl, dtype=bool)
+    for lv0, lv1, *_ in A["chain_segs"].reshape(-1, 9):
+        in_seg[lv0:lv1 + 1] = True
+    lcs = lc_levels if (pair_solve and lc_levels > 0 and not in_seg[:lc_levels].any()) else 0
+    F = dict(n=int(I.n), num_sn=int(nsn), num_levels=int(nl), pair_solve=pair_solve, lc_levels=lc_levels, lc_nchains=lc_nchains, leafchain_solve=lcs,
+             seg_levels=int(in_seg.sum()))
+    inst = {"16x16": [], "16": [], "32": [], "k64": []}
+    for lv in range(lcs, nl):
+        if in_seg[lv] or lp[lv * FC_COUNT + 1] == lp[lv * FC_COUNT]:
+            continue
+        inst["k64" if not pair_solve else "16x16" if wave_mmax[lv] <= 16 else "16" if wave_kmax[lv] <= 16 else "32"].append(lv)
+    F["solve_levels"] = inst
+    F["solve_level_counts"] = {k: len(v) for k, v in inst.items()}
+    on_pair32 = wave & np.isin(level, inst["32"])
+    F["pair32_k_over_16"] = int(np.sum(on_pair32 & (cols > 16)))
+    on_level = wave & np.isin(level, sum(inst.values(), []))
+    F["max_gathered_on_levels"] = int(gathered[on_level].max()) if on_level.any() else 0
+    # the fronts
+    F["classes"] = sorted({int(x) for x in cls})
+    F["shapes"] = sorted({(int(order[f]), int(cols[f]), int(nchild[f])) for f in np.nonzero(wave)[0]})
+    F["wave_fronts"] = int(wave.sum())
+    F["wave_k_over_16"] = int(np.sum(wave & (cols > 16)))
+    F["max_children"] = int(nchild[wave].max()) if wave.any() else 0
+    F["max_gathered"] = int(gathered[wave].max()) if wave.any() else 0
+    # leaf chains
+    ptr, lcf = A["lc_ptr"], A["lc_fronts"]
+    lens = np.diff(ptr) if lc_levels else np.zeros(0, dtype=int)
+    F["chain_lengths"] = sorted((int(a), int(b)) for a, b in zip(*np.unique(lens, return_counts=True)))
+    F["link_shapes"] = sorted({(int(order[f]), int(cols[f])) for f in lcf})
+    F["link_max_entries"] = int(entries[lcf].max()) if len(lcf) else 0
+    F["links_over_48_entries"] = int(np.sum(entries[lcf] > 48)) if len(lcf) else 0
+    F["root_links_k_eq_order"] = int(np.sum((parent[lcf] < 0) & (order[lcf] == cols[lcf]))) if len(lcf) else 0
+    # data-flow runs: (first level, last level, virtual workgroups)
+    runs = A["df_runs"].reshape(-1, 5)
+    F["df_runs"] = [(int(r[0]), int(r[1]), int(r[4])) for r in runs]
+    run_of = np.full(nsn, -1)
+    for q, r in enumerate(runs):
+        run_of[wave & (level >= r[0]) & (level <= r[1])] = q
+    F["df_fronts_17_32"] = int(np.sum((run_of >= 0) & (order > 16)))
+    tagged = (run_of >= 0) & (parent >= 0) & (upd > 0)
+    tagged[tagged] = run_of[parent[tagged]] == run_of[tagged]
+    F["tagged16"] = int(np.sum(tagged & (upd <= 16))); F["tagged32"] = int(np.sum(tagged & (upd > 16)))
+    F["tagged_rows"] = sorted({int(x) for x in upd[tagged]})
+    F["tagged_parents_17_32_children"] = int(max((np.sum(tagged & (parent == p)) for p in set(parent[tagged].tolist()) if order[p] > 16), default=0))
+    F["df_max_gathered"] = int(gathered[run_of >= 0].max()) if (run_of >= 0).any() else 0
+    # the two factor schedules: launches per kernel
+    for name, key in (("full", "factor.single.full"), ("opt", "factor.single.opt")):
+        recs = A[key].reshape(-1, REC)
+        F[name] = tuple(int(np.sum(recs[:, OP] == op)) for op in (FO_LEAF_CHAIN, FO_FRONT_DF, FO_FRONT_DPP16, FO_REG_64_4, FO_REG_64_2))
+    return F
+
+
 def reach(s):
     I = s.info()
     nl, nsn = I.num_levels, I.num_sn

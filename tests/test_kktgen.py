@@ -51,6 +51,28 @@ def test_clique_generator_has_the_structure_and_the_inertia_it_was_built_for():
     assert not K[:a[0], a[0]:].any() and np.array_equal(K[:a[0], :a[0]], kktgen.to_scipy(*a[:4]).toarray())
 
 
+def test_with_diagonal_replaces_the_whole_diagonal_entry_and_nothing_else():
+    """the H diagonal and Sigma are two triplets of one entry: both go, the value is put once; every other entry, the pattern and the input stay"""
+    S = kktgen.block_diag(kktgen.clique_kkt([9, 7], 3, 2, seed=3), kktgen.star_kkt(3, 4, 2, 5, seed=4))
+    n, r, c, v, neg = S
+    v0 = v.copy()
+    K0 = kktgen.to_scipy(n, r, c, v).toarray()
+    edit = [0, 5, 13, n - 1]                                # two clique variables, the first constraint row (13 primal variables before it), the last hub variable
+    assert [int(np.sum((r == c) & (r == x + 1))) for x in edit] == [2, 2, 1, 2]      # H diagonal + Sigma; the (2,2) block has one triplet
+    n2, r2, c2, v2, neg2 = kktgen.with_diagonal(S, edit, 1e-6)
+    assert n2 == n and neg2 is None and np.array_equal(r2, r) and np.array_equal(c2, c) and np.array_equal(v, v0) and v2 is not v
+    K = kktgen.to_scipy(n2, r2, c2, v2).toarray()
+    D = K - K0
+    assert np.count_nonzero(D) == len(edit) and all(D[x, x] != 0.0 for x in edit)
+    assert all(K[x, x] == 1e-6 for x in edit)
+    assert K0[13, 13] == 0.0                                # (a diagonal that was an explicit zero gets the value too)
+    off = (r != c)
+    assert np.array_equal(v2[off], v[off])
+    assert np.array_equal(kktgen.with_diagonal(S, [], 1e-6)[3], v)
+    K3 = kktgen.to_scipy(*kktgen.with_diagonal(S, [5, 0], [2.5, -3.0])[:4]).toarray()      # one value per variable
+    assert K3[5, 5] == 2.5 and K3[0, 0] == -3.0 and np.count_nonzero(K3 - K0) == 2
+
+
 def test_star_generator_has_the_structure_and_the_inertia_it_was_built_for():
     """leaf cliques that share the same variables of a hub clique: symmetric pattern, every clique dense, the leaves coupled through the hub only,
     inertia (n, 0, 0) by LAPACK's eigenvalues"""
