@@ -527,8 +527,30 @@ int  mi355x_kkt_get_symbolic(mi355x_kkt_handle h, int what, int* out, int64_t ca
  *   knows them (ops 3-9, 11; the pivot-block and panel kernels size theirs at launch from a[]);  a0..a3, the kernel's integer arguments, per op:
  *   0 {chains, last level}  1 {tab0, levels, virtual workgroups, last level}  2 {fronts, top_mode, raise-the-flag}  3-9 {flags}  10 {top_mode}
  *   11 {top_mode, ldi, maxch}  12 {staged, rbw}  13 {row blocks, kk}  14-17 {kk}  19 {part}  21 {tiles of part 2}  22-24 {event index: 0 the
- *   single-GPU schedule, 1 + i grouped schedule i;  24: a1 the level of the fork}. */
+ *   single-GPU schedule, 1 + i grouped schedule i;  24: a1 the level of the fork}.
+ *   The solve-block schedule (mi355x_kkt_set_solve_block; nranks = 1 only): "solve.single.block", the launches of ONE block of right-hand sides, the same
+ *   13 ints per record, in the order  bulk forward | top part of one column | bulk backward  (the loads, stores and refinement kernels around them are
+ *   element-wise launches per column and not listed).  `stream` holds the way the record is issued: 0 blocked (one launch of the kernel's *_rb form takes
+ *   every active column), 1 by column (the one-column kernel, once per active column; consecutive records of this kind are issued column by column), 2 top part (the levels from the first chain segment up: every
+ *   column runs through all records of kind 2 on its own, one column after the other).  op:
+ *       0 k_bump_epoch, 1 k_fwd_leafchain, 2 k_bwd_leafchain, 3 k_fwd_pair<16,16>, 4 k_fwd_pair<16>, 5 k_fwd_pair<32>, 6 k_bwd_pair<16,16>, 7 k_bwd_pair<16>,
+ *       8 k_bwd_pair<32>, 9 k_fwd_mid<1>, 10 k_fwd_mid<2>, 11 k_bwd_mid<1>, 12 k_bwd_mid<2>, 13 k_fwd<64> (order <= 32), 14 k_fwd<64> (order <= 64),
+ *       15 k_fwd<256>, 16 k_bwd<64> (order <= 32), 17 k_bwd<64> (order <= 64), 18 k_bwd<256>, 19 k_fwd_solo64, 20 k_fwd_solo, 21 k_fwd_grp,
+ *       22 k_fwd_grp_upd, 23 k_bwd_dot64, 24 k_bwd_fin64, 25 k_bwd_grp_dot, 26 k_bwd_grp, 27 k_fwd_chain, 28 k_bwd_chain;
+ *   b0: first launch-list entry (27, 28: first workgroup record; 1, 2: 0);  a0: fronts (3-8) / chains (1, 2) of the launch, else 0;  a1..a3: 0. */
 int  mi355x_kkt_get_launch_plan(mi355x_kkt_handle h, int nranks, int rank, const char* what, int* out, int64_t capacity, int64_t* count);
+
+/* ---- blocks of right-hand sides in the solves (single-GPU handles; opt-in).  on != 0: a solve call with nrhs >= 2 (solve, solve_device*, the inner solves
+ * of lowrank_update / lowrank_solve*) takes its right-hand sides through the bulk of the tree MI355X_KKT_SOLVE_BLOCK at a time -- one launch per (level,
+ * class) for all columns of a block where the kernel has a blocked form, the front's part of L read once --, and through the chain sweeps at the top of
+ * the tree one column after the other.  Every solution column is bit for bit what a solve of its own gives.  A remainder of one column, nrhs = 1 and
+ * mi355x_kkt_profile take the usual path.  0 (the default): off.  Valid before and after the analysis; a multi-GPU handle is refused (FATAL).
+ * _solve_block_info (any pointer may be NULL; after the analysis, needs no device): the switch, the width, the first level of the top part (num_levels:
+ * no chain sweep), the launches of ONE FULL block of the current plan -- blocked launches, launches by column (width x the records of that kind), the
+ * launches of the top part PER COLUMN -- and the time of the last solve call that took the blocked path (0: none). ---- */
+#define MI355X_KKT_SOLVE_BLOCK 4
+int  mi355x_kkt_set_solve_block(mi355x_kkt_handle h, int on);
+int  mi355x_kkt_solve_block_info(mi355x_kkt_handle h, int* on, int* width, int* first_top_level, int* blocked_launches, int* bycol_launches, int* top_launches_per_column, double* last_ms);
 
 /* ---- measurement: device time per kernel kind (hip events around every launch of an eager, graph-less factor + one
  * solve -- on the stream the kernel is launched on: the look-ahead parts of the largest trailing updates run, and are

@@ -41,6 +41,7 @@ struct mi355x_kkt_handle_s {
                                    // wherever it is eliminated) -- later factorisations whose only complaint is zero pivots answer SINGULAR at once
     std::thread reaper;            // destroys the structure a delayed-pivot edit replaced (80-90 ms of unmapping at n = 10^6) off the caller's path
     ShmComm* shm = nullptr;        // the shared-memory communicator of set_comm_shm (owned; the Numeric object only holds the callbacks' context)
+    int solve_block = 0;           // mi355x_kkt_set_solve_block: survives analyse() (the engine is told again)
     std::string err;
     std::string setup_err;         // why the device set-up of the last analyse() failed (no device; the pool does not fit ...): every later "not ready" answer repeats it
     std::vector<double> host_vals_nodev;   // plain host staging buffer handed out when no device exists (values only, never computed on)
@@ -118,6 +119,7 @@ int mi355x_kkt_analyse(mi355x_kkt_handle h, int n, int nnz, const int* row, cons
         // device setup is attempted right away so that values_buffer() can hand out pinned memory;
         // without a GPU the symbolic result stays queryable and factor()/solve() fail loudly.
         h->num = new Numeric();
+        h->num->set_solve_block(h->solve_block != 0);
         NumericOptions no;
         no.device = h->opts.device; no.scaling = h->opts.scaling; no.pivtol = h->opts.pivtol; no.small = h->opts.small;
         no.pivtolmax = h->opts.pivtolmax > h->opts.pivtol ? h->opts.pivtolmax : h->opts.pivtol;
@@ -899,6 +901,14 @@ int mi355x_kkt_get_launch_plan(mi355x_kkt_handle h, int nranks, int rank, const 
             if (out) { if ((int64_t)v.size() > cap) { h->err = "get_launch_plan: buffer too small"; return MI355X_KKT_FATAL; } std::copy(v.begin(), v.end(), out); }
             return MI355X_KKT_SUCCESS;
         }
+        if (w == "solve.single.block") {      // the launches of one block of right-hand sides, FACTOR_LAUNCH_INTS ints per record
+            if (nranks != 1) { h->err = "get_launch_plan: the solve-block schedule is a single-GPU one"; return MI355X_KKT_FATAL; }
+            for (const FactorLaunch& r : build_solve_block_schedule(P, h->sym, plan_inputs_from_env(1, 0, false, 0)).rec)
+                put({r.op, r.stream, r.kind, r.gx, r.gy, r.block, r.lv, r.b0, r.lds, r.a[0], r.a[1], r.a[2], r.a[3]});
+            *count = (int64_t)v.size();
+            if (out) { if ((int64_t)v.size() > cap) { h->err = "get_launch_plan: buffer too small"; return MI355X_KKT_FATAL; } std::copy(v.begin(), v.end(), out); }
+            return MI355X_KKT_SUCCESS;
+        }
         const Sched* sc = w.rfind("single.", 0) == 0 ? &P.single : w.rfind("local.", 0) == 0 ? &P.local : nullptr;
         if (w.rfind("stage", 0) == 0) { const int d = atoi(w.c_str() + 5); if (d >= 0 && d < (int)P.stage.size()) sc = &P.stage[d]; }
         const std::string field = sc ? w.substr(w.find('.') + 1) : w;
@@ -939,6 +949,49 @@ int mi355x_kkt_get_launch_plan(mi355x_kkt_handle h, int nranks, int rank, const 
         if (out) { if ((int64_t)v.size() > cap) { h->err = "get_launch_plan: buffer too small"; return MI355X_KKT_FATAL; } std::copy(v.begin(), v.end(), out); }
         return MI355X_KKT_SUCCESS;
     } catch (...) { h->err = "get_launch_plan: unexpected exception"; return MI355X_KKT_FATAL; }
+}
+
+/* blocks of right-hand sides in the solves (numeric.hip solve_block; launch_plan.cpp build_solve_block_schedule) */
+int mi355x_kkt_set_solve_block(mi355x_kkt_handle h, int on)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    if (h->opts.nranks > 1) { h->err = "set_solve_block: not supported on a multi-GPU handle"; return MI355X_KKT_FATAL; }
+    h->solve_block = on ? 1 : 0;
+    if (h->num) h->num->set_solve_block(on != 0);
+    return MI355X_KKT_SUCCESS;
+}
+int mi355x_kkt_solve_block_info(mi355x_kkt_handle h, int* on, int* width, int* first_top_level, int* blocked_launches, int* bycol_launches, int* top_launches_per_column, double* last_ms)
+{
+    if (!h) return MI355X_KKT_FATAL;
+    if (on) *on = h->solve_block; if (width) *width = SOLVE_RB; if (first_top_level) *first_top_level = 0;
+    if (blocked_launches) *blocked_launches = 0; if (bycol_launches) *bycol_launches = 0; if (top_launches_per_column) *top_launches_per_column = 0;
+    if (last_ms) *last_ms = h->num ? h->num->last_solve_block_ms() : 0.0;
+    if (!h->analysed || h->opts.nranks > 1) return MI355X_KKT_SUCCESS;      // (no plan yet / not a single-GPU one: the switch and the width only)
+    try {
+        {   // the schedule the engine runs, where there is one (built at set-up); without a device the plan is built here, as get_launch_plan does
+            int ls = 0, nb = 0, nc = 0, nt = 0;
+            if (h->numeric_ready && h->num && h->num->solve_block_plan(&ls, &nb, &nc, &nt)) {
+                if (first_top_level) *first_top_level = ls;
+                if (blocked_launches) *blocked_launches = nb; if (bycol_launches) *bycol_launches = nc; if (top_launches_per_column) *top_launches_per_column = nt;
+                return MI355X_KKT_SUCCESS;
+            }
+        }
+        const PlanInputs in = plan_inputs_from_env(1, 0, false, 0);
+        const LaunchPlan P = build_launch_plan(h->sym, in);
+        if (!P.error.empty()) { h->err = P.error; return MI355X_KKT_FATAL; }
+        const SolveBlockSchedule B = build_solve_block_schedule(P, h->sym, in);
+        if (first_top_level) *first_top_level = B.first_top_level;
+        if (blocked_launches) *blocked_launches = B.blocked; if (bycol_launches) *bycol_launches = B.bycol; if (top_launches_per_column) *top_launches_per_column = B.top;
+        return MI355X_KKT_SUCCESS;
+    } catch (...) { h->err = "solve_block_info: unexpected exception"; return MI355X_KKT_FATAL; }
+}
+
+/* development aid, not part of the public header: the last blocked solve call split into its top part (the chain sweeps, column by column) and the rest */
+int mi355x_kkt_debug_solve_block_split(mi355x_kkt_handle h, double* total_ms, double* top_ms)
+{
+    if (!h || !h->num || !total_ms || !top_ms) return MI355X_KKT_FATAL;
+    *total_ms = h->num->last_solve_block_ms(); *top_ms = h->num->last_solve_block_top_ms();
+    return MI355X_KKT_SUCCESS;
 }
 
 int mi355x_kkt_profile(mi355x_kkt_handle h, int reps, double* ms, int* launches, int capacity)

@@ -39,7 +39,9 @@ __global__ void k_refine_finish(DevView V) { for (int i = blockIdx.x * blockDim.
 // ------------------------------------------------------------------------------------------------
 // z = D^{-1} y over 1x1 and 2x2 pivots is NOT among them: every kernel spells it out.  Moved into a shared function, with the same expressions, the step
 // gave other bits on tests/support/midfix.py hostile16, the one fixture with 2x2 pivots (which product of a * b + c * d goes into the fma is the compiler's
-// choice, and it chose differently there).  Shared is the load of what the step needs, for the kernels that request everything
+// choice, and it chose differently there).  It chose differently again when the pair, leaf-chain and mid kernels got their column loop (RB_ON below), so
+// THOSE kernels name the fma: the form the compiler had chosen for each of them -- pair / leaf chain  fma(d, y_j, o y_j+-1)  for both rows of a 2x2 pivot,
+// mid  fma(d, y_j, o y_j+1)  for its first and  fma(o, y_j-1, d y_j)  for its second row --, so one column and a block of columns agree.  Shared is the load of what the step needs, for the kernels that request everything
 // the front record gives before they wait for anything: pivot type, the row's diagonal entry of D^{-1}, the off-diagonal entries towards the next and
 // the previous row.
 struct PivD { int pt; double dq, oq, oq1; };
@@ -277,6 +279,142 @@ __device__ __forceinline__ void mid_acc(const double (&v)[MID_KB], const double*
     }
 }
 
+// BLOCKS OF RIGHT-HAND SIDES (the solve-block path of numeric.hip): the bodies below take NC columns through a front together.  What the front record
+// gives -- pivot order, D, the rows and columns of L11^{-1} and of the panel, the child records, the targets rel[...] -- is loaded once; per column there
+// are its entries of xw / zb / cvec (column c at c * sx / c * sx / c * scv doubles behind column 0), its slice of the LDS vectors and its accumulators.
+// Per column the operations and their order are those of one column (the kernels of one column ARE the NC = 1 instantiation); nc <= NC columns are
+// active (uniform over the launch), the others are neither read, written nor multiplied in.
+#define RB_ON(c) (NC == 1 || (c) < nc)
+template <int MR, int NC>
+__device__ __forceinline__ void fwd_mid_front(const DevView& V, const int list_off, const int nc, const size_t sx, const size_t scv)
+{
+    __shared__ double xp[NC][MID_KMAX], ys[NC][MID_KMAX + MID_KB], bp[NC][MID_KMAX + MID_KB], xu[NC][128];
+    const int tid = threadIdx.x;
+    const FrontMeta M = V.fmeta[list_off + blockIdx.x];
+    const int c0 = M.c0, k = M.k, m = M.m, ldp = M.ldp, ch0 = M.ch0, ch1 = M.ch1;
+    const double* Mg = V.minv + M.minv_off;
+    const double* Lg = V.L + M.panel_off;
+    // ---- phase 1: the front record gives every address.  The child records first (what phase 2 waits for): lane c of every wavefront loads child c's ----
+    const int nch = ch1 - ch0 < 4 ? ch1 - ch0 : 4;
+    int mcl = 0, rbl = 0; long long cbl = 0;
+    if (nch > 0) { const ChildMeta* Cl = V.cmeta + ch0 + ((tid & 3) < nch ? (tid & 3) : nch - 1); mcl = Cl->mc; rbl = Cl->relbase; cbl = Cl->cvbase; }
+    const bool piv = tid < k;
+    const int jc = piv ? tid : 0;
+    double xwv[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) if (RB_ON(c)) xwv[c] = V.xw[c * sx + (c0 + jc)];
+    const int lpv = V.lperm[c0 + jc];
+    double mrow[MID_KB], lrow[MR][MID_KB];
+    mid_ld_mrow(mrow, Mg, k, tid, 0);
+#pragma unroll
+    for (int r = 0; r < MR; ++r) mid_ld_lrow(lrow[r], Lg, k, m, ldp, k + tid + 64 * r, 0);
+    const int pt = V.ptype[c0 + jc];
+    const double dq = V.dinv[c0 + jc], oq = V.doff[c0 + jc], oq1 = V.doff[c0 + (jc > 0 ? jc - 1 : 0)];
+    // ---- phase 2: the children's contribution vectors (the first four children's in one batch) ----
+    int tg[4][MR]; double cv[NC][4][MR];
+    if (nch > 0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {      // (lanes c >= nch hold the last child's record again: valid addresses, no entry taken)
+            const int mc = c < nch ? __builtin_amdgcn_readlane(mcl, c) : 0, rb = __builtin_amdgcn_readlane(rbl, c);
+            const long long cb = ((long long)__builtin_amdgcn_readlane((int)(cbl >> 32), c) << 32) | (unsigned)__builtin_amdgcn_readlane((int)cbl, c);
+#pragma unroll
+            for (int r = 0; r < MR; ++r) {
+                const int t = tid + 64 * r; const bool on = t < mc;
+                const int g = V.rel[rb + (on ? t : 0)];
+#pragma unroll
+                for (int col = 0; col < NC; ++col) if (RB_ON(col)) cv[col][c][r] = V.cvec[col * scv + (cb + (on ? t : 0))];
+                tg[c][r] = on ? g : -1;
+            }
+        }
+    }
+    // ---- phase 3: arithmetic ----
+#pragma unroll
+    for (int col = 0; col < NC; ++col) if (RB_ON(col)) {
+        if (piv) xp[col][tid] = xwv[col];
+        for (int i = k + tid; i < m; i += 64) xu[col][i - k] = 0.0;
+    }
+    __syncthreads();
+    if (nch > 0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+#pragma unroll
+            for (int r = 0; r < MR; ++r) {
+                const int g = tg[c][r];
+                if (g >= 0) {
+#pragma unroll
+                    for (int col = 0; col < NC; ++col) if (RB_ON(col)) { if (g < k) xp[col][g] += cv[col][c][r]; else xu[col][g - k] += cv[col][c][r]; }
+                }
+            }
+            __syncthreads();
+        }
+        for (int cp = ch0 + 4; cp < ch1; ++cp) {                 // (more than four children: rare)
+            const ChildMeta Cm = V.cmeta[cp];
+            for (int t = tid; t < Cm.mc; t += 64) {
+                const int g = V.rel[Cm.relbase + t];
+#pragma unroll
+                for (int col = 0; col < NC; ++col) if (RB_ON(col)) {
+                    const double v = V.cvec[col * scv + (Cm.cvbase + t)];
+                    if (g < k) xp[col][g] += v; else xu[col][g - k] += v;
+                }
+            }
+            __syncthreads();
+        }
+    }
+#pragma unroll
+    for (int col = 0; col < NC; ++col) if (RB_ON(col)) { if (piv) bp[col][tid] = xp[col][lpv]; }
+    __syncthreads();
+    {   // y = Minv * (P b): thread j walks row j of the column-major inverse, even and odd columns p <= j apart
+        double a0[NC], a1[NC];
+#pragma unroll
+        for (int col = 0; col < NC; ++col) if (RB_ON(col)) { a0[col] = 0.0; a1[col] = 0.0; mid_acc(mrow, bp[col], tid + 1, a0[col], a1[col]); }
+        for (int pb = MID_KB; pb < k; pb += MID_KB) {
+            double mv[MID_KB]; mid_ld_mrow(mv, Mg, k, tid, pb);
+#pragma unroll
+            for (int col = 0; col < NC; ++col) if (RB_ON(col)) mid_acc(mv, bp[col] + pb, tid + 1 - pb, a0[col], a1[col]);
+        }
+#pragma unroll
+        for (int col = 0; col < NC; ++col) if (RB_ON(col)) { if (piv) ys[col][tid] = a0[col] + a1[col]; }
+    }
+    __syncthreads();
+    {   // c = (children) - L21 y: a thread's rows, even and odd columns apart
+        double t0[NC][MR], t1[NC][MR];
+#pragma unroll
+        for (int col = 0; col < NC; ++col) if (RB_ON(col)) {
+#pragma unroll
+            for (int r = 0; r < MR; ++r) { t0[col][r] = 0.0; t1[col][r] = 0.0; mid_acc(lrow[r], ys[col], k, t0[col][r], t1[col][r]); }
+        }
+        for (int jb = MID_KB; jb < k; jb += MID_KB) {
+            double lv[MR][MID_KB];
+#pragma unroll
+            for (int r = 0; r < MR; ++r) mid_ld_lrow(lv[r], Lg, k, m, ldp, k + tid + 64 * r, jb);
+#pragma unroll
+            for (int col = 0; col < NC; ++col) if (RB_ON(col)) {
+#pragma unroll
+                for (int r = 0; r < MR; ++r) mid_acc(lv[r], ys[col] + jb, k - jb, t0[col][r], t1[col][r]);
+            }
+        }
+#pragma unroll
+        for (int col = 0; col < NC; ++col) if (RB_ON(col)) {
+#pragma unroll
+            for (int r = 0; r < MR; ++r) { const int i = k + tid + 64 * r; if (i < m) V.cvec[col * scv + (M.cv + i)] = xu[col][i - k] - (t0[col][r] + t1[col][r]); }
+        }
+    }
+    if (piv) {
+        const int j = tid;
+#pragma unroll
+        for (int col = 0; col < NC; ++col) if (RB_ON(col)) {
+            double z;
+            if (pt == 1) z = ys[col][j] * dq;
+            else if (pt == 2) z = fma(dq, ys[col][j], oq * ys[col][j + 1]);      // (the fma is spelled out: see PivD)
+            else z = fma(oq1, ys[col][j - 1], dq * ys[col][j]);
+            V.zb[col * sx + (c0 + j)] = z;
+        }
+    }
+}
+// The forward kernel of ONE column stays as it was written, beside fwd_mid_front: as fwd_mid_front<MR, 1> the same statements took 114 instead of 99 VGPRs
+// for MR = 1 (the allocator spills fewer SGPRs and keeps more vector registers; every other one-column kernel of this file IS the NC = 1 instantiation of
+// its body, within two VGPRs of what it took before).  What holds the two together: tests/test_gpu_solve_block.py asks every column of a block for the
+// bits of a solve of its own.
 template <int MR>
 __global__ __launch_bounds__(64) void k_fwd_mid(DevView V, int list_off)
 {
@@ -362,17 +500,18 @@ __global__ __launch_bounds__(64) void k_fwd_mid(DevView V, int list_off)
         const int j = tid;
         double z;
         if (pt == 1) z = ys[j] * dq;
-        else if (pt == 2) z = dq * ys[j] + oq * ys[j + 1];
-        else z = oq1 * ys[j - 1] + dq * ys[j];
+        else if (pt == 2) z = fma(dq, ys[j], oq * ys[j + 1]);      // (the fma is spelled out: see PivD)
+        else z = fma(oq1, ys[j - 1], dq * ys[j]);
         V.zb[c0 + j] = z;
     }
 }
+template <int MR> __global__ __launch_bounds__(64) void k_fwd_mid_rb(DevView V, int list_off, int nc, size_t sx, size_t scv) { fwd_mid_front<MR, SOLVE_RB>(V, list_off, nc, sx, scv); }
 
 // backward: MID_KB columns per batch, rows lane and lane + 64 (MR = 2) of each per lane
-template <int MR>
-__global__ __launch_bounds__(64) void k_bwd_mid(DevView V, int list_off)
+template <int MR, int NC>
+__device__ __forceinline__ void bwd_mid_front(const DevView& V, const int list_off, const int nc, const size_t sx)
 {
-    __shared__ double ws[MID_KMAX + MID_KB], xu[128];
+    __shared__ double ws[NC][MID_KMAX + MID_KB], xu[NC][128];
     const int tid = threadIdx.x, lane = tid;
     const FrontMeta M = V.fmeta[list_off + blockIdx.x];
     const int c0 = M.c0, k = M.k, r0 = M.r0, m = M.m, ldp = M.ldp, nu = m - k;
@@ -384,7 +523,9 @@ __global__ __launch_bounds__(64) void k_bwd_mid(DevView V, int list_off)
     for (int r = 0; r < MR; ++r) { const int i = lane + 64 * r; ridx[r] = V.sn_rows[r0 + (i < nu ? k + i : 0)]; }
     const bool piv = tid < k;
     const int jc = piv ? tid : 0;
-    const double zbv = V.zb[c0 + jc];
+    double zbv[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) if (RB_ON(c)) zbv[c] = V.zb[c * sx + (c0 + jc)];
     double lcol[MID_KB][MR];
 #pragma unroll
     for (int q = 0; q < MID_KB; ++q)
@@ -396,18 +537,25 @@ __global__ __launch_bounds__(64) void k_bwd_mid(DevView V, int list_off)
     // ---- phase 2: the ancestors' solution entries (the fence keeps the scheduler from drawing the gather, and its wait, in front of the batch) ----
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int r = 0; r < MR; ++r) xu[lane + 64 * r] = V.xw[ridx[r]];      // (unconditional: rows >= nu hold the front's first row again and are never read)
+    for (int c = 0; c < NC; ++c) if (RB_ON(c)) {
+#pragma unroll
+        for (int r = 0; r < MR; ++r) xu[c][lane + 64 * r] = V.xw[c * sx + ridx[r]];      // (unconditional: rows >= nu hold the front's first row again and are never read)
+    }
     // ---- phase 3 ----
-    ws[piv ? tid : MID_KMAX + MID_KB - 1] = zbv;      // (unconditional: a store under `piv` draws the load into the branch, behind the gather)
+#pragma unroll
+    for (int c = 0; c < NC; ++c) if (RB_ON(c)) ws[c][piv ? tid : MID_KMAX + MID_KB - 1] = zbv[c];      // (unconditional: a store under `piv` draws the load into the branch, behind the gather)
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < MID_KB; ++q) {
         const int j = q;
-        double t = 0.0;
 #pragma unroll
-        for (int r = 0; r < MR; ++r) { const int i = lane + 64 * r; const double f = fma(lcol[q][r], xu[i], t); t = i < nu ? f : t; }
-        t = wave_sum(t);
-        if (lane == 0 && j < k) ws[j] -= t;
+        for (int c = 0; c < NC; ++c) if (RB_ON(c)) {
+            double t = 0.0;
+#pragma unroll
+            for (int r = 0; r < MR; ++r) { const int i = lane + 64 * r; const double f = fma(lcol[q][r], xu[c][i], t); t = i < nu ? f : t; }
+            t = wave_sum(t);
+            if (lane == 0 && j < k) ws[c][j] -= t;
+        }
     }
     for (int jb = MID_KB; jb < k; jb += MID_KB) {
         double lv[MID_KB][MR];
@@ -418,21 +566,32 @@ __global__ __launch_bounds__(64) void k_bwd_mid(DevView V, int list_off)
 #pragma unroll
         for (int q = 0; q < MID_KB; ++q) {
             const int j = jb + q;
-            double t = 0.0;
 #pragma unroll
-            for (int r = 0; r < MR; ++r) { const int i = lane + 64 * r; const double f = fma(lv[q][r], xu[i], t); t = i < nu ? f : t; }
-            t = wave_sum(t);
-            if (lane == 0 && j < k) ws[j] -= t;
+            for (int c = 0; c < NC; ++c) if (RB_ON(c)) {
+                double t = 0.0;
+#pragma unroll
+                for (int r = 0; r < MR; ++r) { const int i = lane + 64 * r; const double f = fma(lv[q][r], xu[c][i], t); t = i < nu ? f : t; }
+                t = wave_sum(t);
+                if (lane == 0 && j < k) ws[c][j] -= t;
+            }
         }
     }
     __syncthreads();
     {   // x_p = sum_{j >= p} Minv(j,p) w_j: thread p walks its own column of the inverse, rows p, p + 2, ... and p + 1, p + 3, ... apart
-        double a0 = 0.0, a1 = 0.0;
-        mid_acc(mcol, ws + jc, k - tid, a0, a1);
-        for (int qb = MID_KB; qb < k; qb += MID_KB) { double mv[MID_KB]; mid_ld_mcol(mv, Mg, k, tid, qb); mid_acc(mv, ws + (piv ? tid + qb < k ? tid + qb : 0 : 0), k - tid - qb, a0, a1); }
-        if (piv) V.xw[c0 + lpv] = a0 + a1;
+        double a0[NC], a1[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) if (RB_ON(c)) { a0[c] = 0.0; a1[c] = 0.0; mid_acc(mcol, ws[c] + jc, k - tid, a0[c], a1[c]); }
+        for (int qb = MID_KB; qb < k; qb += MID_KB) {
+            double mv[MID_KB]; mid_ld_mcol(mv, Mg, k, tid, qb);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) if (RB_ON(c)) mid_acc(mv, ws[c] + (piv ? tid + qb < k ? tid + qb : 0 : 0), k - tid - qb, a0[c], a1[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < NC; ++c) if (RB_ON(c)) { if (piv) V.xw[c * sx + (c0 + lpv)] = a0[c] + a1[c]; }
     }
 }
+template <int MR> __global__ __launch_bounds__(64) void k_bwd_mid(DevView V, int list_off) { bwd_mid_front<MR, 1>(V, list_off, 1, 0); }
+template <int MR> __global__ __launch_bounds__(64) void k_bwd_mid_rb(DevView V, int list_off, int nc, size_t sx) { bwd_mid_front<MR, SOLVE_RB>(V, list_off, nc, sx); }
 
 
 // ------------------------------------------------------------------------------------------------
@@ -460,34 +619,44 @@ __device__ __forceinline__ void small_ld_rows(double (&mrow)[KP], double (&lrow)
 }
 // forward, phase 3, behind the gather into xs: y (returned, and left in ys), the update row's  xs - L21 y  handed to put(value) on the update lanes.
 // z = D^{-1} y stays with each kernel, as every kernel's does (see PivD).
-template <int KP, int LPF, class Put>
-__device__ __forceinline__ double small_fwd_solve(const int k, const int m, const int li, const int lpv, const double (&mrow)[KP], const double (&lrow)[KP], const double* xs, double* bp, double* ys, Put put)
+// NC columns (see RB_ON): column c's rows of the LDS arrays lie CS (xs, bp) / CSY (ys) doubles behind column 0's; y[c] is returned per column, put(c, value)
+template <int KP, int LPF, int NC, int CS, int CSY, class Put>
+__device__ __forceinline__ void small_fwd_solve(const int k, const int m, const int li, const int lpv, const double (&mrow)[KP], const double (&lrow)[KP], const double* xs, double* bp, double* ys, const int nc, double (&y)[NC], Put put)
 {
     const bool piv = li < k, upd = li >= k && li < m;
-    bp[li] = piv ? xs[lpv] : 0.0;
-    __syncthreads();
-    double y = 0.0;
 #pragma unroll
-    for (int p = 0; p < KP; ++p) y += mrow[p] * bp[p];
-    ys[li] = piv ? y : 0.0;
-    if (li == 0) ys[LPF] = 0.0;
+    for (int c = 0; c < NC; ++c) if (RB_ON(c)) bp[c * CS + li] = piv ? xs[c * CS + lpv] : 0.0;
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < NC; ++c) if (RB_ON(c)) {
+        double yc = 0.0;
+#pragma unroll
+        for (int p = 0; p < KP; ++p) yc += mrow[p] * bp[c * CS + p];
+        ys[c * CSY + li] = piv ? yc : 0.0;
+        if (li == 0) ys[c * CSY + LPF] = 0.0;
+        y[c] = yc;
+    }
     __syncthreads();
     if (upd) {
-        double t = 0.0;
 #pragma unroll
-        for (int p = 0; p < KP; ++p) t += lrow[p] * ys[p];
-        put(xs[li] - t);
+        for (int c = 0; c < NC; ++c) if (RB_ON(c)) {
+            double t = 0.0;
+#pragma unroll
+            for (int p = 0; p < KP; ++p) t += lrow[p] * ys[c * CSY + p];
+            put(c, xs[c * CS + li] - t);
+        }
     }
-    return y;
 }
 // backward, all three phases: the front record's loads, the ancestors' solution entries, arithmetic
-template <int KP, int LPF, class Rec>
-__device__ __forceinline__ void small_bwd(const DevView& V, const Rec& R, const int k, const int m, const int li, double* xus, double* w)
+template <int KP, int LPF, int NC, int CS, class Rec>      // NC columns (see RB_ON): column c's rows of xus and w lie CS doubles behind column 0's
+__device__ __forceinline__ void small_bwd(const DevView& V, const Rec& R, const int k, const int m, const int li, double* xus, double* w, const int nc, const size_t sx)
 {
     const int c0 = R.c0, r0 = R.r0, ldp = R.ldp;
     const bool piv = li < k, upd = li >= k && li < m;
     // ---- phase 1 ----
-    const double zbv = piv ? V.zb[c0 + li] : 0.0;
+    double zbv[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) if (RB_ON(c)) zbv[c] = piv ? V.zb[c * sx + (c0 + li)] : 0.0;
     const int lpv = piv ? V.lperm[c0 + li] : 0;
     const int ridx = upd ? V.sn_rows[r0 + li] : 0;
     const double* Mg = V.minv + R.minv_off;
@@ -498,27 +667,34 @@ __device__ __forceinline__ void small_bwd(const DevView& V, const Rec& R, const 
 #pragma unroll
     for (int i = 0; i < LPF; ++i) lcol[i] = (piv && k + i < m) ? Lg[k + i + (size_t)li * ldp] : 0.0;        // L(k + i, li)
     // ---- phase 2: the ancestors' solution entries ----
-    xus[li] = upd ? V.xw[ridx] : 0.0;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) if (RB_ON(c)) xus[c * CS + li] = upd ? V.xw[c * sx + ridx] : 0.0;
     __syncthreads();
     // ---- phase 3 ----
-    double t = 0.0;
 #pragma unroll
-    for (int i = 0; i < LPF; ++i) t += lcol[i] * xus[(k + i) & (LPF - 1)];
-    w[li] = piv ? zbv - t : 0.0;
+    for (int c = 0; c < NC; ++c) if (RB_ON(c)) {
+        double t = 0.0;
+#pragma unroll
+        for (int i = 0; i < LPF; ++i) t += lcol[i] * xus[c * CS + ((k + i) & (LPF - 1))];
+        w[c * CS + li] = piv ? zbv[c] - t : 0.0;
+    }
     __syncthreads();
     if (piv) {
-        double a = 0.0;
 #pragma unroll
-        for (int q = 0; q < KP; ++q) a += mcol[q] * w[(li + q) & (LPF - 1)];
-        V.xw[c0 + lpv] = a;
+        for (int c = 0; c < NC; ++c) if (RB_ON(c)) {
+            double a = 0.0;
+#pragma unroll
+            for (int q = 0; q < KP; ++q) a += mcol[q] * w[c * CS + ((li + q) & (LPF - 1))];
+            V.xw[c * sx + (c0 + lpv)] = a;
+        }
     }
 }
 
-template <int KP, int LPF = 32>      // LPF lanes per front: 32 (order <= 32, two fronts per wavefront) or 16 (levels whose fronts all have order <= 16: four)
-__global__ __launch_bounds__(64) void k_fwd_pair(DevView V, int list_off, int nfronts)
+template <int KP, int LPF, int NC>      // LPF lanes per front: 32 (order <= 32, two fronts per wavefront) or 16 (levels whose fronts all have order <= 16: four)
+__device__ __forceinline__ void fwd_pair_front(const DevView& V, const int list_off, const int nfronts, const int nc, const size_t sx, const size_t scv)
 {
     constexpr int FPW = 64 / LPF;
-    __shared__ double xs[FPW][LPF], bp[FPW][LPF], ys[FPW][LPF + 1];
+    __shared__ double xs[NC][FPW][LPF], bp[NC][FPW][LPF], ys[NC][FPW][LPF + 1];
     const int lane = threadIdx.x, h = lane / LPF, li = lane % LPF;
     const int f = FPW * (int)blockIdx.x + h;
     const bool act = f < nfronts;
@@ -527,7 +703,9 @@ __global__ __launch_bounds__(64) void k_fwd_pair(DevView V, int list_off, int nf
     const long long cvo = Mp->cv;
     // ---- phase 1: depends on the front record only ----
     const bool piv = li < k;
-    const double xwv = piv ? V.xw[c0 + li] : 0.0;
+    double xwv[NC];
+#pragma unroll
+    for (int col = 0; col < NC; ++col) if (RB_ON(col)) xwv[col] = piv ? V.xw[col * sx + (c0 + li)] : 0.0;
     const int lpv = piv ? V.lperm[c0 + li] : 0;
     const PivD D = ld_pivd(V, c0, li, piv);
     double mrow[KP], lrow[KP];
@@ -540,39 +718,61 @@ __global__ __launch_bounds__(64) void k_fwd_pair(DevView V, int list_off, int nf
         cmc[c] = has ? Cp->mc : 0; crel[c] = Cp->relbase; ccv[c] = Cp->cvbase;
     }
     // ---- phase 2: the children's contribution vectors ----
-    int tg[4]; double cv[4];
+    int tg[4]; double cv[NC][4];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) { const bool on = li < cmc[c]; tg[c] = on ? V.rel[crel[c] + li] : -1; cv[c] = on ? V.cvec[ccv[c] + li] : 0.0; }
+    for (int c = 0; c < 4; ++c) {
+        const bool on = li < cmc[c]; tg[c] = on ? V.rel[crel[c] + li] : -1;
+#pragma unroll
+        for (int col = 0; col < NC; ++col) if (RB_ON(col)) cv[col][c] = on ? V.cvec[col * scv + (ccv[c] + li)] : 0.0;
+    }
     // ---- phase 3: arithmetic ----
-    xs[h][li] = xwv;
+#pragma unroll
+    for (int col = 0; col < NC; ++col) if (RB_ON(col)) xs[col][h][li] = xwv[col];
     __syncthreads();
 #pragma unroll
-    for (int c = 0; c < 4; ++c) { if (tg[c] >= 0) xs[h][tg[c]] += cv[c]; __syncthreads(); }
-    for (int cp = ch0 + 4; cp < ch1; ++cp) {                 // (more than four children: rare)
-        const int mc = V.cmeta[cp].mc;
-        if (li < mc) xs[h][V.rel[V.cmeta[cp].relbase + li]] += V.cvec[V.cmeta[cp].cvbase + li];
+    for (int c = 0; c < 4; ++c) {
+        if (tg[c] >= 0) {
+#pragma unroll
+            for (int col = 0; col < NC; ++col) if (RB_ON(col)) xs[col][h][tg[c]] += cv[col][c];
+        }
         __syncthreads();
     }
-    const double y = small_fwd_solve<KP, LPF>(k, m, li, lpv, mrow, lrow, xs[h], bp[h], ys[h], [&](const double r) { V.cvec[cvo + li] = r; });
+    for (int cp = ch0 + 4; cp < ch1; ++cp) {                 // (more than four children: rare)
+        const int mc = V.cmeta[cp].mc;
+        if (li < mc) {
+#pragma unroll
+            for (int col = 0; col < NC; ++col) if (RB_ON(col)) xs[col][h][V.rel[V.cmeta[cp].relbase + li]] += V.cvec[col * scv + (V.cmeta[cp].cvbase + li)];
+        }
+        __syncthreads();
+    }
+    double y[NC];
+    small_fwd_solve<KP, LPF, NC, FPW * LPF, FPW * (LPF + 1)>(k, m, li, lpv, mrow, lrow, xs[0][h], bp[0][h], ys[0][h], nc, y, [&](const int col, const double r) { V.cvec[col * scv + (cvo + li)] = r; });
     if (piv) {
-        double z;
-        if (D.pt == 1) z = y * D.dq;
-        else if (D.pt == 2) z = D.dq * y + D.oq * ys[h][li + 1];
-        else z = D.oq1 * ys[h][li - 1] + D.dq * y;
-        V.zb[c0 + li] = z;
+#pragma unroll
+        for (int col = 0; col < NC; ++col) if (RB_ON(col)) {
+            double z;
+            if (D.pt == 1) z = y[col] * D.dq;
+            else if (D.pt == 2) z = fma(D.dq, y[col], D.oq * ys[col][h][li + 1]);      // (the fma is spelled out: see PivD)
+            else z = fma(D.dq, y[col], D.oq1 * ys[col][h][li - 1]);
+            V.zb[col * sx + (c0 + li)] = z;
+        }
     }
 }
-template <int KP, int LPF = 32>
-__global__ __launch_bounds__(64) void k_bwd_pair(DevView V, int list_off, int nfronts)
+template <int KP, int LPF = 32> __global__ __launch_bounds__(64) void k_fwd_pair(DevView V, int list_off, int nfronts) { fwd_pair_front<KP, LPF, 1>(V, list_off, nfronts, 1, 0, 0); }
+template <int KP, int LPF = 32> __global__ __launch_bounds__(64) void k_fwd_pair_rb(DevView V, int list_off, int nfronts, int nc, size_t sx, size_t scv) { fwd_pair_front<KP, LPF, SOLVE_RB>(V, list_off, nfronts, nc, sx, scv); }
+template <int KP, int LPF, int NC>
+__device__ __forceinline__ void bwd_pair_front(const DevView& V, const int list_off, const int nfronts, const int nc, const size_t sx)
 {
     constexpr int FPW = 64 / LPF;
-    __shared__ double xus[FPW][LPF], w[FPW][LPF];
+    __shared__ double xus[NC][FPW][LPF], w[NC][FPW][LPF];
     const int lane = threadIdx.x, h = lane / LPF, li = lane % LPF;
     const int f = FPW * (int)blockIdx.x + h;
     const bool act = f < nfronts;
     const FrontMeta* Mp = V.fmeta + list_off + (act ? f : 0);
-    small_bwd<KP, LPF>(V, *Mp, act ? Mp->k : 0, act ? Mp->m : 0, li, xus[h], w[h]);
+    small_bwd<KP, LPF, NC, FPW * LPF>(V, *Mp, act ? Mp->k : 0, act ? Mp->m : 0, li, xus[0][h], w[0][h], nc, sx);
 }
+template <int KP, int LPF = 32> __global__ __launch_bounds__(64) void k_bwd_pair(DevView V, int list_off, int nfronts) { bwd_pair_front<KP, LPF, 1>(V, list_off, nfronts, 1, 0); }
+template <int KP, int LPF = 32> __global__ __launch_bounds__(64) void k_bwd_pair_rb(DevView V, int list_off, int nfronts, int nc, size_t sx) { bwd_pair_front<KP, LPF, SOLVE_RB>(V, list_off, nfronts, nc, sx); }
 
 // ------------------------------------------------------------------------------------------------
 // LEAF CHAINS in the sweeps (see k_leaf_chain): a 16-lane row walks its chain -- forward from the leaf up, the contribution vector of a link handed to
@@ -580,10 +780,11 @@ __global__ __launch_bounds__(64) void k_bwd_pair(DevView V, int list_off, int nf
 // have just stored: same CU, a barrier in between) -- one launch per sweep for all the levels of the chains.  A link's body is that of a front of
 // k_fwd_pair / k_bwd_pair<16, 16>: small_ld_rows, small_fwd_solve, small_bwd.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_fwd_leafchain(DevView V, int nchains)
+template <int NC>
+__device__ __forceinline__ void fwd_leafchain_row(const DevView& V, const int nchains, const int nc, const size_t sx, const size_t scv)
 {
     constexpr int KP = 16, LPF = 16, FPW = 4;
-    __shared__ double xs[FPW][LPF], bp[FPW][LPF], ys[FPW][LPF + 1], cvs[FPW][LPF];
+    __shared__ double xs[NC][FPW][LPF], bp[NC][FPW][LPF], ys[NC][FPW][LPF + 1], cvs[NC][FPW][LPF];
     const int lane = threadIdx.x, h = lane / LPF, li = lane % LPF;
     const int ch = FPW * (int)blockIdx.x + h;
     const bool cact = ch < nchains;
@@ -601,7 +802,9 @@ __global__ __launch_bounds__(64) void k_fwd_leafchain(DevView V, int nchains)
         const int c0 = K0.c0, k = act ? K0.k : 0, m = act ? K0.m : 0, ldp = K0.ldp;
         const long long cvo = K0.cv;
         const bool piv = li < k;
-        const double xwv = piv ? V.xw[c0 + li] : 0.0;
+        double xwv[NC];
+#pragma unroll
+        for (int col = 0; col < NC; ++col) if (RB_ON(col)) xwv[col] = piv ? V.xw[col * sx + (c0 + li)] : 0.0;
         const int lpv = piv ? V.lperm[c0 + li] : 0;
         const PivD D = ld_pivd(V, c0, li, piv);
         double mrow[KP], lrow[KP];
@@ -609,28 +812,40 @@ __global__ __launch_bounds__(64) void k_fwd_leafchain(DevView V, int nchains)
         // the child (the previous link): its contribution vector is in cvs
         const int mc = (act && t > 0) ? mprev - kprev : 0;
         const int tg = li < mc ? V.rel[relprev + li] : -1;
-        const double cv = li < mc ? cvs[h][li] : 0.0;
-        xs[h][li] = xwv;
+        double cv[NC];
+#pragma unroll
+        for (int col = 0; col < NC; ++col) if (RB_ON(col)) { cv[col] = li < mc ? cvs[col][h][li] : 0.0; xs[col][h][li] = xwv[col]; }
         __syncthreads();
-        if (tg >= 0) xs[h][tg] += cv;
+        if (tg >= 0) {
+#pragma unroll
+            for (int col = 0; col < NC; ++col) if (RB_ON(col)) xs[col][h][tg] += cv[col];
+        }
         __syncthreads();
-        const double y = small_fwd_solve<KP, LPF>(k, m, li, lpv, mrow, lrow, xs[h], bp[h], ys[h], [&](const double r) { cvs[h][li - k] = r; if (t == nl - 1) V.cvec[cvo + li] = r; });
+        double y[NC];
+        small_fwd_solve<KP, LPF, NC, FPW * LPF, FPW * (LPF + 1)>(k, m, li, lpv, mrow, lrow, xs[0][h], bp[0][h], ys[0][h], nc, y,
+            [&](const int col, const double r) { cvs[col][h][li - k] = r; if (t == nl - 1) V.cvec[col * scv + (cvo + li)] = r; });
         if (piv) {
-            double z;
-            if (D.pt == 1) z = y * D.dq;
-            else if (D.pt == 2) z = D.dq * y + D.oq * ys[h][li + 1];
-            else z = D.oq1 * ys[h][li - 1] + D.dq * y;
-            V.zb[c0 + li] = z;
+#pragma unroll
+            for (int col = 0; col < NC; ++col) if (RB_ON(col)) {
+                double z;
+                if (D.pt == 1) z = y[col] * D.dq;
+                else if (D.pt == 2) z = fma(D.dq, y[col], D.oq * ys[col][h][li + 1]);      // (the fma is spelled out: see PivD)
+                else z = fma(D.dq, y[col], D.oq1 * ys[col][h][li - 1]);
+                V.zb[col * sx + (c0 + li)] = z;
+            }
         }
         __syncthreads();
         kprev = k; mprev = m; relprev = K0.relbase;
         K0 = K1;
     }
 }
-__global__ __launch_bounds__(64) void k_bwd_leafchain(DevView V, int nchains)
+__global__ __launch_bounds__(64) void k_fwd_leafchain(DevView V, int nchains) { fwd_leafchain_row<1>(V, nchains, 1, 0, 0); }
+__global__ __launch_bounds__(64) void k_fwd_leafchain_rb(DevView V, int nchains, int nc, size_t sx, size_t scv) { fwd_leafchain_row<SOLVE_RB>(V, nchains, nc, sx, scv); }
+template <int NC>
+__device__ __forceinline__ void bwd_leafchain_row(const DevView& V, const int nchains, const int nc, const size_t sx)
 {
     constexpr int KP = 16, LPF = 16, FPW = 4;
-    __shared__ double xus[FPW][LPF], w[FPW][LPF];
+    __shared__ double xus[NC][FPW][LPF], w[NC][FPW][LPF];
     const int lane = threadIdx.x, h = lane / LPF, li = lane % LPF;
     const int ch = FPW * (int)blockIdx.x + h;
     const bool cact = ch < nchains;
@@ -645,11 +860,13 @@ __global__ __launch_bounds__(64) void k_bwd_leafchain(DevView V, int nchains)
         const bool act = t >= 0;
         const LeafLink K1 = Lc[max(t - 1, 0)];            // (the next link's record: on its way while this link is solved)
         // (ancestors inside the chain: their entries of xw were stored by this row one iteration ago, barrier below)
-        small_bwd<KP, LPF>(V, K0, act ? K0.k : 0, act ? K0.m : 0, li, xus[h], w[h]);
+        small_bwd<KP, LPF, NC, FPW * LPF>(V, K0, act ? K0.k : 0, act ? K0.m : 0, li, xus[0][h], w[0][h], nc, sx);
         __syncthreads();
         K0 = K1;
     }
 }
+__global__ __launch_bounds__(64) void k_bwd_leafchain(DevView V, int nchains) { bwd_leafchain_row<1>(V, nchains, 1, 0); }
+__global__ __launch_bounds__(64) void k_bwd_leafchain_rb(DevView V, int nchains, int nc, size_t sx) { bwd_leafchain_row<SOLVE_RB>(V, nchains, nc, sx); }
 
 // ================================================================================================
 // BIG fronts in the triangular solves: a CHAIN GROUP (<= 4 links of an in-place separator chain, <= 256 columns) is one

@@ -17,6 +17,7 @@ PlanInputs plan_inputs_from_env(int nranks, int rank, bool multi, int verbose)
     in.tfuse = !knob_disabled("tfuse"); in.fuse_upd = !knob_disabled("fuse_upd"); in.selfasm = !knob_disabled("selfasm");
     in.grouped = !knob_disabled("grouped"); in.xcd_tiles = !knob_disabled("xcd_tiles"); in.lookahead = !knob_disabled("lookahead");
     in.pair_solve = !knob_disabled("pair_solve"); in.p1_small = !knob_disabled("p1_small"); in.side_small = !knob_disabled("side_small");
+    in.mid_solve = !knob_disabled("mid_solve");
     in.la_wgs = (int)std::max(1ll, knob_int("la_wgs", in.la_wgs));
     in.la_min_nt = (int)std::max(3ll, knob_int("la_min_nt", in.la_min_nt));
     in.la_min_tiles = knob_int("la_min_tiles", in.la_min_tiles);     // (tests force 0)
@@ -791,6 +792,90 @@ std::vector<FactorLaunch> build_factor_schedule(const LaunchPlan& P, const Symbo
     }
     join(NL);      // (no fork outlives its list: the multi-rank schedules never fork -- build_launch_plan splits no update there -- and the single-GPU one ends here)
     return out;
+}
+
+// ---- the solve-block schedule: the launches of one block of right-hand sides (launch_plan.h SolveBlockKind).  level() is numeric.hip solve_level for the
+//      single-GPU schedule (top_mode 0), walk() the level loop of solve_sweep over [lv_lo, lv_hi) with its chain segments ----
+SolveBlockSchedule build_solve_block_schedule(const LaunchPlan& P, const Symbolic& Sy, const PlanInputs& in)
+{
+    SolveBlockSchedule B;
+    const Sched& sc = P.single;
+    const int NL = P.nlevels;
+    if (in.multi || sc.ptr.empty()) { B.first_top_level = NL; return B; }
+    auto bucket0 = [&](int lv, int fc) { return sc.base + sc.ptr[(size_t)lv * FC_COUNT + fc]; };
+    auto put = [&](int op, int sb, int kind, int lv, int b0, int gx, int gy, int block, size_t lds, int a0 = 0) {
+        B.rec.push_back(FactorLaunch{op, sb, kind, gx, gy, block, lv, b0, (int)lds, {a0, 0, 0, 0}}); };
+    auto lds_solve = [](int mmax, int kmax) { return (size_t)(mmax + 3 * kmax) * sizeof(double) + 16; };
+    const bool pair = P.pair_solve, mid = in.mid_solve && Sy.maxsupernode <= SOLVE_MID_KMAX;
+    // bulk: the kernels that have a blocked form go as SB_BLOCKED, the others as SB_BYCOL; top: everything SB_TOP
+    auto level = [&](int lv, bool forward, bool top) {
+        const int blk = top ? SB_TOP : SB_BLOCKED, col = top ? SB_TOP : SB_BYCOL;
+        for (int fc = 0; fc < FC_COUNT; ++fc) {
+            const int b0 = bucket0(lv, fc), nb = bucket0(lv, fc + 1) - b0;
+            if (nb == 0) continue;
+            const int g0 = sc.last0[lv], ng = sc.last1[lv] - g0, mm = sc.maxm[lv];
+            if (forward) {
+                if (fc == FC_WAVE && pair && P.wave_mmax[lv] <= 16) put(SO_FWD_PAIR16_16, blk, KK_FWD_WAVE, lv, b0, (nb + 3) / 4, 1, 64, 0, nb);
+                else if (fc == FC_WAVE && pair && P.wave_kmax[lv] <= 16) put(SO_FWD_PAIR16, blk, KK_FWD_WAVE, lv, b0, (nb + 1) / 2, 1, 64, 0, nb);
+                else if (fc == FC_WAVE && pair) put(SO_FWD_PAIR32, blk, KK_FWD_WAVE, lv, b0, (nb + 1) / 2, 1, 64, 0, nb);
+                else if (fc == FC_WAVE) put(SO_FWD_WAVE, col, KK_FWD_WAVE, lv, b0, nb, 1, 64, lds_solve(32, 32));
+                else if (fc == FC_LDS64 && mid) put(SO_FWD_MID1, blk, KK_FWD_LDS, lv, b0, nb, 1, 64, 0);
+                else if (fc == FC_LDS128 && mid) put(SO_FWD_MID2, blk, KK_FWD_LDS, lv, b0, nb, 1, 64, 0);
+                else if (fc == FC_LDS64) put(SO_FWD_LDS64, col, KK_FWD_LDS, lv, b0, nb, 1, 64, lds_solve(64, 64));
+                else if (fc == FC_LDS128) put(SO_FWD_LDS128, col, KK_FWD_LDS, lv, b0, nb, 1, 256, lds_solve(128, 128));
+                else if (ng <= 0) continue;
+                else if (sc.allsolo[lv] && sc.maxk[lv] <= 64) put(SO_FWD_SOLO64, col, KK_FWD_BIG, lv, g0, (mm + 63) / 64 + 1, ng, 256, 0);
+                else if (sc.allsolo[lv]) put(SO_FWD_SOLO, col, KK_FWD_BIG, lv, g0, (mm + 63) / 64 + 1, ng, 256, 0);
+                else { put(SO_FWD_GRP, col, KK_FWD_BIG, lv, g0, ng, 1, 256, 0);
+                       put(SO_FWD_GRP_UPD, col, KK_FWD_BIG_UPD, lv, g0, (mm + 63) / 64, ng, 256, 0); }
+            } else {
+                if (fc == FC_WAVE && pair && P.wave_mmax[lv] <= 16) put(SO_BWD_PAIR16_16, blk, KK_BWD_WAVE, lv, b0, (nb + 3) / 4, 1, 64, 0, nb);
+                else if (fc == FC_WAVE && pair && P.wave_kmax[lv] <= 16) put(SO_BWD_PAIR16, blk, KK_BWD_WAVE, lv, b0, (nb + 1) / 2, 1, 64, 0, nb);
+                else if (fc == FC_WAVE && pair) put(SO_BWD_PAIR32, blk, KK_BWD_WAVE, lv, b0, (nb + 1) / 2, 1, 64, 0, nb);
+                else if (fc == FC_WAVE) put(SO_BWD_WAVE, col, KK_BWD_WAVE, lv, b0, nb, 1, 64, lds_solve(32, 32));
+                else if (fc == FC_LDS64 && mid) put(SO_BWD_MID1, blk, KK_BWD_LDS, lv, b0, nb, 1, 64, 0);
+                else if (fc == FC_LDS128 && mid) put(SO_BWD_MID2, blk, KK_BWD_LDS, lv, b0, nb, 1, 64, 0);
+                else if (fc == FC_LDS64) put(SO_BWD_LDS64, col, KK_BWD_LDS, lv, b0, nb, 1, 64, lds_solve(64, 64));
+                else if (fc == FC_LDS128) put(SO_BWD_LDS128, col, KK_BWD_LDS, lv, b0, nb, 1, 256, lds_solve(128, 128));
+                else if (ng <= 0) continue;
+                else if (!Sy.solve_group && sc.maxk[lv] <= 64) {
+                    put(SO_BWD_DOT64, col, KK_BWD_BIG_DOT, lv, g0, (mm + 255) / 256, ng, 256, 0);
+                    put(SO_BWD_FIN64, col, KK_BWD_BIG, lv, g0, ng, 1, 256, 0);
+                } else {
+                    put(SO_BWD_GRP_DOT, col, KK_BWD_BIG_DOT, lv, g0, (mm + 255) / 256, ng, 256, 0);
+                    put(SO_BWD_GRP, col, KK_BWD_BIG, lv, g0, ng, 1, 256, 0); }
+            }
+        }
+    };
+    auto walk = [&](int lv_lo, int lv_hi, bool forward, bool top) {
+        for (int q = lv_lo; q < lv_hi; ++q) {
+            const int lv = forward ? q : lv_hi - 1 + lv_lo - q;
+            const int sgi = forward ? P.seg_at_lv0[lv] : P.seg_at_lv1[lv];
+            if (sgi < 0) { level(lv, forward, top); continue; }
+            const ChainSeg& sg = P.chain_segs[sgi];
+            if (forward) put(SO_FWD_CHAIN, SB_TOP, KK_FWD_BIG, lv, sg.wgf0, sg.nwg_f, 1, 320, 0);
+            else put(SO_BWD_CHAIN, SB_TOP, KK_BWD_BIG, lv, sg.wgb0, sg.nwg_b, 1, 320, 0);
+            q += sg.lv1 - sg.lv0;
+        }
+    };
+    int lcs = (P.pair_solve && P.lc_levels > 0) ? P.lc_levels : 0;
+    for (int lv = 0; lv < lcs; ++lv) if (P.seg_at_lv0[lv] >= 0) { lcs = 0; break; }
+    int ls = NL;
+    for (int lv = lcs; lv < NL; ++lv) if (P.seg_at_lv0[lv] >= 0) { ls = lv; break; }
+    B.first_top_level = ls;
+    if (lcs > 0) put(SO_FWD_LEAFCHAIN, SB_BLOCKED, KK_FWD_WAVE, 0, 0, (P.lc_nchains + 3) / 4, 1, 64, 0, P.lc_nchains);
+    walk(lcs, ls, true, false);
+    B.top0 = (int)B.rec.size();
+    if (ls < NL) {
+        put(SO_BUMP_EPOCH, SB_TOP, KK_SOLVE_PERM, ls, 0, 1, 1, 64, 0);
+        walk(ls, NL, true, true);
+        walk(ls, NL, false, true);
+    }
+    B.top1 = (int)B.rec.size();
+    walk(lcs, ls, false, false);
+    if (lcs > 0) put(SO_BWD_LEAFCHAIN, SB_BLOCKED, KK_BWD_WAVE, 0, 0, (P.lc_nchains + 3) / 4, 1, 64, 0, P.lc_nchains);
+    for (const FactorLaunch& r : B.rec) { if (r.stream == SB_BLOCKED) ++B.blocked; else if (r.stream == SB_BYCOL) B.bycol += SOLVE_RB; else ++B.top; }
+    return B;
 }
 
 } // namespace mi355x

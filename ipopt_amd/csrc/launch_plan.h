@@ -17,6 +17,7 @@ struct PlanInputs {
     bool chain_solve = true, fuse_dt = true, fastpiv = true, asm_pull = true, leafchain = true, front_df = true, tfuse = true, fuse_upd = true,
          selfasm = true, grouped = true, xcd_tiles = true, lookahead = true, pair_solve = true, p1_small = true;
     bool side_small = true;              // a handful of small fronts beside a level's bulk go to the side stream (build_factor_schedule)
+    bool mid_solve = true;               // fronts of order 33..128 on the solves' level launches: k_fwd_mid / k_bwd_mid (numeric.hip solve_level reads the same knob)
     int la_wgs = 1 << 20, la_min_nt = 8, grp_rbw_max = 8, chain_solve_maxc = 128, fuse_dt_maxwg = 448;
     long long la_min_tiles = 4000;
     double fastpiv_floor = 1e-4;         // (0.01 up to r03a: 9 % of the synth_1e6 blocks then took the strict loop and set the pace of their level: 23.1 -> 22.0 ms)
@@ -69,6 +70,31 @@ struct FactorLaunch { int op, stream, kind, gx, gy, block, lv, b0, lds, a[4]; };
 constexpr int FACTOR_LAUNCH_INTS = 13;       // the exported row: the fields in this order
 constexpr int SIDE_MAX_FRONTS = 16;
 
+// ---- the solve-block schedule (single-GPU handles, mi355x_kkt_set_solve_block): the right-hand sides of one call travel through the tree SOLVE_RB at a
+//      time.  One record per launch of ONE block, in the field layout of FactorLaunch; `stream` holds the SolveBlockKind:
+//        SB_BLOCKED  one launch of the *_rb form of the kernel takes all active columns
+//        SB_BYCOL    the launch is issued once per active column, the work vectors of the DevView pointing at that column
+//                    (a run of consecutive by-column records goes column by column: the pair of launches of a big-front level shares scratch)
+//        SB_TOP      a launch of the top part (levels >= first_top_level: from the first chain segment up), which every column runs through on its own, one
+//                    column after the other: epoch bump, forward walk, backward walk
+//      The records stand in the order  bulk forward | top part of ONE column | bulk backward;  the executor (numeric.hip run_solve_block) repeats the middle
+//      range per column.  The values are exported ("solve.single.block", include/mi355x_kkt.h): append, do not renumber.
+//      b0: first launch-list entry (FWD/BWD_CHAIN: first workgroup record), a[0]: fronts / chains of the launch (0 where the kernel takes none), a[1]: top_mode (0).
+constexpr int SOLVE_RB = 4;                  // columns per block (compile-time width of the *_rb kernels)
+constexpr int SOLVE_MID_KMAX = 64;           // = MID_KMAX of kernels_solve.hip.inc: the pivot count k_fwd_mid / k_bwd_mid take
+enum SolveOp { SO_BUMP_EPOCH = 0, SO_FWD_LEAFCHAIN, SO_BWD_LEAFCHAIN, SO_FWD_PAIR16_16, SO_FWD_PAIR16, SO_FWD_PAIR32, SO_BWD_PAIR16_16, SO_BWD_PAIR16, SO_BWD_PAIR32,
+               SO_FWD_MID1, SO_FWD_MID2, SO_BWD_MID1, SO_BWD_MID2,
+               SO_FWD_WAVE, SO_FWD_LDS64, SO_FWD_LDS128, SO_BWD_WAVE, SO_BWD_LDS64, SO_BWD_LDS128,      // k_fwd<64> (LDS for order 32 / 64), k_fwd<256>; k_bwd likewise
+               SO_FWD_SOLO64, SO_FWD_SOLO, SO_FWD_GRP, SO_FWD_GRP_UPD, SO_BWD_DOT64, SO_BWD_FIN64, SO_BWD_GRP_DOT, SO_BWD_GRP,
+               SO_FWD_CHAIN, SO_BWD_CHAIN, SO_COUNT };
+enum SolveBlockKind { SB_BLOCKED = 0, SB_BYCOL = 1, SB_TOP = 2 };
+struct SolveBlockSchedule {
+    std::vector<FactorLaunch> rec;
+    int first_top_level = 0;                 // L*: the first level >= the leaf-chain prefix that starts a chain segment (nlevels: none)
+    int top0 = 0, top1 = 0;                  // rec[top0, top1): the top part of one column
+    int blocked = 0, bycol = 0, top = 0;     // launches of one FULL block: blocked records, SOLVE_RB x by-column records; top records of ONE column
+};
+
 struct ExchangeLayout {
     std::vector<long long> aoff, troff;                  // per front: its arena square / top-rhs accumulator, or -1
     std::vector<long long> abeg, aend, tbeg, tend;       // per step: its part of the arena / of the top right-hand sides
@@ -118,11 +144,15 @@ struct LaunchPlan {
     std::vector<int> stat_owner, col_owner;
     // the factor schedules this handle can run (NumericImpl::setup: build_factor_schedule): one GPU, [0] the full one, [1] the optimistic one; multi-rank
     std::vector<FactorLaunch> factor_single[2], factor_local; std::vector<std::vector<FactorLaunch>> factor_stage;
+    SolveBlockSchedule solve_block;                      // one GPU: the blocked solve (NumericImpl::setup: build_solve_block_schedule)
 };
 LaunchPlan build_launch_plan(const Symbolic& Sy, const PlanInputs& in);
 // The factor schedule of one Sched as a flat list: every launch and every stream operation of the factorisation between the equilibration and the
 // statistics, in the order the executor (numeric.hip run_factor_list) issues them.  which: 0 = P.single, 1 = P.local, 2 + d = P.stage[d] (top_mode
 // and the grouped schedule P.grp[...] follow from it).  optimistic: the schedule without the strict launches the static-order kernels make idle.
 std::vector<FactorLaunch> build_factor_schedule(const LaunchPlan& P, const Symbolic& Sy, const PlanInputs& in, int which, bool optimistic);
+// The launches of one block of right-hand sides on the single-GPU schedule P.single (see SolveBlockKind): the per-class launch choice of numeric.hip
+// solve_level and the level walk of solve_sweep, restated as a list.
+SolveBlockSchedule build_solve_block_schedule(const LaunchPlan& P, const Symbolic& Sy, const PlanInputs& in);
 
 } // namespace mi355x

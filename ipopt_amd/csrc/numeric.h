@@ -61,6 +61,12 @@ public:
     double last_factor_ms() const;
     void   matching_stats(double* ms, int* rounds, int* unmatched) const;      // the last matching-scaling computation (scaling modes 3-6)
     double last_solve_ms() const;
+    // opt-in blocked solve of a single-GPU handle (launch_plan.h SolveBlockKind): nrhs >= 2 right-hand sides go through the tree SOLVE_RB at a time;
+    // last_solve_block_ms: the time of the last solve call that took that path (0: none)
+    void   set_solve_block(bool on);
+    double last_solve_block_ms() const;
+    double last_solve_block_top_ms() const;          // of that call: the part spent in the top part of its blocks (events around it)
+    bool   solve_block_plan(int* first_top_level, int* blocked, int* bycol, int* top) const;      // the schedule the engine runs (false: not set up, or multi-rank)
     const std::string& error() const;
     static constexpr int kNumKernelKinds = 18;
     bool   profile(int reps, double* ms, int* launches);

@@ -460,7 +460,7 @@ public:
                      comm_kind = 0; comm_range_fn = nullptr; }
         destroy_factor_graphs(); scale_valid = false; asm_dirty = true;
         if (g_solve) { (void)hipGraphExecDestroy(g_solve); g_solve = nullptr; }
-        own_struct.clear(); d_rhs = nullptr; d_rhs_cap = 0;
+        own_struct.clear(); d_rhs = nullptr; d_rhs_cap = 0; sblk = SolveBlk(); sblk_ev.clear(); sblk_ev_used = 0;
         la_ev.clear(); side_evF.clear(); side_evJ.clear();
         own_match.clear(); MV = MatchView{};
         if (!keep) {
@@ -596,6 +596,7 @@ public:
         if (!P.error.empty()) { err_ = P.error; return false; }
         // ... and the factor schedules this handle can run: one GPU, the full and the optimistic one (factor() picks); multi-rank, own subtrees and every step
         if (!multi) for (int o = 0; o < 2; ++o) P.factor_single[o] = build_factor_schedule(P, Sy, in, 0, o != 0);
+        if (!multi) P.solve_block = build_solve_block_schedule(P, Sy, in);
         else { P.factor_local = build_factor_schedule(P, Sy, in, 1, false); for (int d = 0; d < P.ndepth; ++d) P.factor_stage.push_back(build_factor_schedule(P, Sy, in, 2 + d, false)); }
         V.fastpiv = in.fastpiv ? 1 : 0; V.asm_pull = in.asm_pull ? 1 : 0; V.fastu = in.fastpiv_floor;
         df_grid_cap = 0;
@@ -977,6 +978,140 @@ public:
         return true;
     }
 
+    // ---- blocks of right-hand sides (opt-in: set_solve_block): the columns of one call travel through the bulk of the tree SOLVE_RB at a time -- the
+    //      leaf chains, the pair and the mid kernels take all active columns in ONE launch (kernels_solve.hip.inc *_rb: the front record, L and L11^{-1}
+    //      loaded once per front, every dependent round trip shared) --, and through the chain sweeps at the top one column after the other (their flags,
+    //      tags and epoch stay as they are; never two of them in flight).  The schedule is launch_plan.cpp build_solve_block_schedule; nothing is decided
+    //      here: the switch maps a SolveOp to its kernel.  SOLVE_RB columns of work vectors, contiguous (the kernels address column c by a stride),
+    //      allocated at the first blocked solve against the current structure (own_struct: release() and a restructure clear them). ----
+    static_assert(SOLVE_MID_KMAX == MID_KMAX, "launch_plan.h restates the pivot count of the mid kernels");
+    struct SolveBlk { double *xw = nullptr, *zb = nullptr, *cvec = nullptr, *bw = nullptr, *xacc = nullptr; };
+    SolveBlk sblk; bool solve_block_on = false; double solve_block_ms = 0.0;
+    // the split of a blocked call: events around the top part of every block (one contiguous stretch of the stream), summed behind the call's synchronisation
+    std::vector<hipEvent_t> sblk_ev; size_t sblk_ev_used = 0; double solve_block_top_ms = 0.0;
+    bool sblk_ensure() {
+        if (sblk.xw) return true;
+        const size_t n = (size_t)std::max(S->n, 1), cvd = (size_t)std::max<long long>(S->cvec_doubles, 1);
+        if (!dalloc(&sblk.xw, SOLVE_RB * n) || !dalloc(&sblk.zb, SOLVE_RB * n) || !dalloc(&sblk.bw, SOLVE_RB * n) || !dalloc(&sblk.xacc, SOLVE_RB * n) || !dalloc(&sblk.cvec, SOLVE_RB * cvd)) {
+            for (double* q : {sblk.xw, sblk.zb, sblk.bw, sblk.xacc, sblk.cvec}) if (q) own_struct.free_device(q);      // (nothing half allocated stays behind)
+            sblk = SolveBlk(); return false;
+        }
+        HIPCHK(hipDeviceSynchronize());      // (dalloc's zero fills ran on the default stream)
+        return true;
+    }
+    DevView sblk_view(int c) const {      // the DevView whose work vectors are column c of the block
+        const size_t n = (size_t)std::max(S->n, 1), cvd = (size_t)std::max<long long>(S->cvec_doubles, 1);
+        DevView W = V;
+        W.xw = sblk.xw + c * n; W.zb = sblk.zb + c * n; W.bw = sblk.bw + c * n; W.xacc = sblk.xacc + c * n; W.cvec = sblk.cvec + c * cvd;
+        return W;
+    }
+    // one record with the work vectors of W; nc > 0: the blocked form for nc columns from W's on
+    bool solve_block_launch(const FactorLaunch& r, const DevView& W, int nc) {
+        const dim3 g(r.gx, r.gy), b(r.block);
+        const size_t sx = (size_t)std::max(S->n, 1), scv = (size_t)std::max<long long>(S->cvec_doubles, 1);
+        const int b0 = r.b0, nf = r.a[0];
+        if (nc > 0) switch (r.op) {
+            case SO_FWD_LEAFCHAIN: LAUNCH(r.kind, k_fwd_leafchain_rb, g, b, 0, stream, W, nf, nc, sx, scv); break;
+            case SO_BWD_LEAFCHAIN: LAUNCH(r.kind, k_bwd_leafchain_rb, g, b, 0, stream, W, nf, nc, sx); break;
+            case SO_FWD_PAIR16_16: LAUNCH(r.kind, (k_fwd_pair_rb<16, 16>), g, b, 0, stream, W, b0, nf, nc, sx, scv); break;
+            case SO_FWD_PAIR16:    LAUNCH(r.kind, (k_fwd_pair_rb<16>), g, b, 0, stream, W, b0, nf, nc, sx, scv); break;
+            case SO_FWD_PAIR32:    LAUNCH(r.kind, (k_fwd_pair_rb<32>), g, b, 0, stream, W, b0, nf, nc, sx, scv); break;
+            case SO_BWD_PAIR16_16: LAUNCH(r.kind, (k_bwd_pair_rb<16, 16>), g, b, 0, stream, W, b0, nf, nc, sx); break;
+            case SO_BWD_PAIR16:    LAUNCH(r.kind, (k_bwd_pair_rb<16>), g, b, 0, stream, W, b0, nf, nc, sx); break;
+            case SO_BWD_PAIR32:    LAUNCH(r.kind, (k_bwd_pair_rb<32>), g, b, 0, stream, W, b0, nf, nc, sx); break;
+            case SO_FWD_MID1:      LAUNCH(r.kind, (k_fwd_mid_rb<1>), g, b, 0, stream, W, b0, nc, sx, scv); break;
+            case SO_FWD_MID2:      LAUNCH(r.kind, (k_fwd_mid_rb<2>), g, b, 0, stream, W, b0, nc, sx, scv); break;
+            case SO_BWD_MID1:      LAUNCH(r.kind, (k_bwd_mid_rb<1>), g, b, 0, stream, W, b0, nc, sx); break;
+            case SO_BWD_MID2:      LAUNCH(r.kind, (k_bwd_mid_rb<2>), g, b, 0, stream, W, b0, nc, sx); break;
+            default: err_ = "solve block: a record without a blocked kernel"; return false;
+        } else switch (r.op) {
+            case SO_BUMP_EPOCH:    LAUNCH(r.kind, k_bump_epoch, g, b, 0, stream, W.sepoch); break;
+            case SO_FWD_LEAFCHAIN: LAUNCH(r.kind, k_fwd_leafchain, g, b, 0, stream, W, nf); break;
+            case SO_BWD_LEAFCHAIN: LAUNCH(r.kind, k_bwd_leafchain, g, b, 0, stream, W, nf); break;
+            case SO_FWD_PAIR16_16: LAUNCH(r.kind, (k_fwd_pair<16, 16>), g, b, 0, stream, W, b0, nf); break;
+            case SO_FWD_PAIR16:    LAUNCH(r.kind, (k_fwd_pair<16>), g, b, 0, stream, W, b0, nf); break;
+            case SO_FWD_PAIR32:    LAUNCH(r.kind, (k_fwd_pair<32>), g, b, 0, stream, W, b0, nf); break;
+            case SO_BWD_PAIR16_16: LAUNCH(r.kind, (k_bwd_pair<16, 16>), g, b, 0, stream, W, b0, nf); break;
+            case SO_BWD_PAIR16:    LAUNCH(r.kind, (k_bwd_pair<16>), g, b, 0, stream, W, b0, nf); break;
+            case SO_BWD_PAIR32:    LAUNCH(r.kind, (k_bwd_pair<32>), g, b, 0, stream, W, b0, nf); break;
+            case SO_FWD_MID1:      LAUNCH(r.kind, (k_fwd_mid<1>), g, b, 0, stream, W, b0); break;
+            case SO_FWD_MID2:      LAUNCH(r.kind, (k_fwd_mid<2>), g, b, 0, stream, W, b0); break;
+            case SO_BWD_MID1:      LAUNCH(r.kind, (k_bwd_mid<1>), g, b, 0, stream, W, b0); break;
+            case SO_BWD_MID2:      LAUNCH(r.kind, (k_bwd_mid<2>), g, b, 0, stream, W, b0); break;
+            case SO_FWD_WAVE: case SO_FWD_LDS64: LAUNCH(r.kind, (k_fwd<64>), g, b, (size_t)r.lds, stream, W, b0, 0); break;
+            case SO_FWD_LDS128:    LAUNCH(r.kind, (k_fwd<256>), g, b, (size_t)r.lds, stream, W, b0, 0); break;
+            case SO_BWD_WAVE: case SO_BWD_LDS64: LAUNCH(r.kind, (k_bwd<64>), g, b, (size_t)r.lds, stream, W, b0); break;
+            case SO_BWD_LDS128:    LAUNCH(r.kind, (k_bwd<256>), g, b, (size_t)r.lds, stream, W, b0); break;
+            case SO_FWD_SOLO64:    LAUNCH(r.kind, k_fwd_solo64, g, b, 0, stream, W, b0); break;
+            case SO_FWD_SOLO:      LAUNCH(r.kind, k_fwd_solo, g, b, 0, stream, W, b0); break;
+            case SO_FWD_GRP:       LAUNCH(r.kind, k_fwd_grp, g, b, 0, stream, W, b0, 0); break;
+            case SO_FWD_GRP_UPD:   LAUNCH(r.kind, k_fwd_grp_upd, g, b, 0, stream, W, b0); break;
+            case SO_BWD_DOT64:     LAUNCH(r.kind, k_bwd_dot64, g, b, 0, stream, W, b0); break;
+            case SO_BWD_FIN64:     LAUNCH(r.kind, k_bwd_fin64, g, b, 0, stream, W, b0); break;
+            case SO_BWD_GRP_DOT:   LAUNCH(r.kind, k_bwd_grp_dot, g, b, 0, stream, W, b0); break;
+            case SO_BWD_GRP:       LAUNCH(r.kind, k_bwd_grp, g, b, 0, stream, W, b0); break;
+            case SO_FWD_CHAIN:     LAUNCH(r.kind, k_fwd_chain, g, b, 0, stream, W, b0); break;
+            case SO_BWD_CHAIN:     LAUNCH(r.kind, k_bwd_chain, g, b, 0, stream, W, b0); break;
+            default: err_ = "solve block: unknown record"; return false;
+        }
+        return true;
+    }
+    // the sweeps of one block of nc columns (2 <= nc <= SOLVE_RB) over the block's work vectors: bulk forward, the top part column by column, bulk backward
+    bool solve_block_core(int nc) {
+        const SolveBlockSchedule& B = P.solve_block;
+        const DevView W0 = sblk_view(0);
+        // A run of consecutive by-column records goes COLUMN by column: the two launches of a big-front level (k_fwd_grp + k_fwd_grp_upd, k_bwd_dot64 +
+        // k_bwd_fin64, k_bwd_grp_dot + k_bwd_grp) hand their partial results over in scratch all columns share (ybuf, gpart: written by the first, read by
+        // the second), so a column's pair stays back to back in stream order.
+        auto bulk = [&](int r0, int r1) {
+            for (int q = r0; q < r1; ) {
+                const FactorLaunch& r = B.rec[q];
+                if (r.stream == SB_BLOCKED) { if (!solve_block_launch(r, W0, nc)) return false; ++q; continue; }
+                int q1 = q; while (q1 < r1 && B.rec[q1].stream == SB_BYCOL) ++q1;
+                for (int c = 0; c < nc; ++c) { const DevView W = sblk_view(c); for (int p = q; p < q1; ++p) if (!solve_block_launch(B.rec[p], W, 0)) return false; }
+                q = q1;
+            }
+            return true;
+        };
+        const bool split = B.top1 > B.top0 && !sctx_tuning;
+        if (split) {
+            while (sblk_ev.size() < sblk_ev_used + 2) { hipEvent_t e = nullptr; if (!own_struct.event(&e)) return false; sblk_ev.push_back(e); }
+        }
+        if (!bulk(0, B.top0)) return false;
+        if (split) HIPCHK(hipEventRecord(sblk_ev[sblk_ev_used], stream));
+        for (int c = 0; c < nc; ++c) { const DevView W = sblk_view(c); for (int q = B.top0; q < B.top1; ++q) if (!solve_block_launch(B.rec[q], W, 0)) return false; }
+        if (split) { HIPCHK(hipEventRecord(sblk_ev[sblk_ev_used + 1], stream)); sblk_ev_used += 2; }
+        if (!bulk(B.top1, (int)B.rec.size())) return false;
+        HIPCHK(hipGetLastError());
+        return true;
+    }
+    // one block: load, (refinement by column around) the blocked core, store -- enqueue_solve / enqueue_solve_core for nc columns
+    bool solve_block(int nc, const double* dsrc, int lds_, double* drhs, int ld) {
+        const int n = S->n;
+        const int nref = opt.refine_steps > 0 ? opt.refine_steps : 0;
+        const dim3 g1(grid1d(n)), b1(256);
+        for (int c = 0; c < nc; ++c) {
+            const DevView W = sblk_view(c);
+            LAUNCH(KK_SOLVE_PERM, k_load_rhs, g1, b1, 0, stream, W, dsrc + (size_t)c * lds_);
+            if (nref > 0) LAUNCH(KK_SOLVE_PERM, k_save_rhs, g1, b1, 0, stream, W);
+        }
+        for (int pass = 0; pass <= nref; ++pass) {
+            if (pass > 0) for (int c = 0; c < nc; ++c) {
+                const DevView W = sblk_view(c);
+                LAUNCH(KK_SOLVE_PERM, k_refine_residual, g1, b1, 0, stream, W, pass == 1 ? 1 : 0);
+                LAUNCH(KK_SOLVE_PERM, k_refine_spmv, g1, b1, 0, stream, W);
+            }
+            if (!solve_block_core(nc)) return false;
+        }
+        for (int c = 0; c < nc; ++c) {
+            const DevView W = sblk_view(c);
+            if (nref > 0) LAUNCH(KK_SOLVE_PERM, k_refine_finish, g1, b1, 0, stream, W);
+            LAUNCH(KK_SOLVE_PERM, k_store_sol, g1, b1, 0, stream, W, drhs + (size_t)c * ld);
+        }
+        HIPCHK(hipGetLastError());
+        return true;
+    }
+
     // ---- several right-hand sides (MultiSolve with nrhs > 1, IpSparseSymLinearSolverInterface.hpp:190; the reference hands nrhs straight to ONE ma97_solve,
     //      IpMa97SolverInterface.cpp:790,805): a single solve is a LATENCY chain (1.8 of the ~6 TB/s a stream of L could take), so the right-hand sides are not
     //      solved one behind the other: up to SOLVE_CTX of them are in flight at once, each in a CONTEXT of its own -- its own stream, work vectors, message
@@ -1045,7 +1180,8 @@ public:
         if (!ready) { if (err_.empty()) err_ = "solve: solver not set up"; return false; }
         if (multi) return solve_dist(nrhs, dsrc, lds_, drhs, ld);
         if (timed) HIPCHK(hipEventRecord(ev0, stream));
-        int nctx = (nrhs > 1 && !prof_on && !V.strace && !knob_disabled("solve_ctx")) ? std::min(nrhs, SOLVE_CTX) : 1;
+        const bool blocked = solve_block_on && nrhs >= 2 && !prof_on && !V.strace;      // (the contexts and their one-off measurement are skipped)
+        int nctx = (!blocked && nrhs > 1 && !prof_on && !V.strace && !knob_disabled("solve_ctx")) ? std::min(nrhs, SOLVE_CTX) : 1;
         if (nctx > 1 && sctx_verdict == 0 && !sctx_tuning) {
             // measured ONCE per structure, on scratch vectors: three right-hand sides one after the other against the same three through the contexts.  On a
             // tree whose chain sweeps fill the device (synth_1e6: 5 290 spinning workgroups) the level launches of a second context starve next to them and the
@@ -1098,10 +1234,22 @@ public:
                 HIPCHK(hipEventRecord(sctx[c].done, sctx[c].strm)); HIPCHK(hipStreamWaitEvent(stream, sctx[c].done, 0));
                 if (!P.chain_segs.empty()) hipLaunchKernelGGL(k_merge_err, dim3(1), dim3(64), 0, stream, V.sepoch + 1, (const int*)(sctx[c].sepoch + 1));
             }
+        } else if (blocked) {
+            if (!sblk_ensure()) return false;
+            sblk_ev_used = 0;
+            for (int r = 0; r < nrhs; r += SOLVE_RB) {      // blocks of SOLVE_RB on the solver's stream; a remainder of one column takes the path of one column
+                const int nc = std::min(SOLVE_RB, nrhs - r);
+                if (nc == 1) { if (!solve_one(dsrc + (size_t)r * lds_, drhs + (size_t)r * ld)) return false; }
+                else if (!solve_block(nc, dsrc + (size_t)r * lds_, lds_, drhs + (size_t)r * ld, ld)) return false;
+            }
         } else
             for (int r = 0; r < nrhs; ++r) if (!solve_one(dsrc + (size_t)r * lds_, drhs + (size_t)r * ld)) return false;
         if (timed) {
             if (!finish_timed(solve_ms, false, h_stats + 6, V.sepoch + 1, P.chain_segs.empty() ? 0 : sizeof(int))) return false;
+            if (blocked) {
+                solve_block_ms = solve_ms; solve_block_top_ms = 0.0;
+                for (size_t i = 0; i + 1 < sblk_ev_used; i += 2) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, sblk_ev[i], sblk_ev[i + 1])); solve_block_top_ms += ms; }
+            }
             if (V.strace) {
                 std::vector<unsigned long long> h(strace_n);
                 HIPCHK(hipMemcpy(h.data(), V.strace, strace_n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
@@ -2122,6 +2270,15 @@ void* Numeric::prewarm(int device, size_t count)
 void Numeric::prewarm_discard(void* p) { if (p) (void)hipHostFree(p); }
 bool Numeric::factor(const double* dvals, bool reuse, FactorStats& st) { return p_->factor(dvals, reuse, st); }
 bool Numeric::solve_host(int nrhs, double* rhs, int ld) { return p_->solve_host(nrhs, rhs, ld); }
+void Numeric::set_solve_block(bool on) { p_->solve_block_on = on; }
+bool Numeric::solve_block_plan(int* first_top_level, int* blocked, int* bycol, int* top) const {
+    if (!p_->ready || p_->multi) return false;
+    const SolveBlockSchedule& B = p_->P.solve_block;
+    *first_top_level = B.first_top_level; *blocked = B.blocked; *bycol = B.bycol; *top = B.top;
+    return true;
+}
+double Numeric::last_solve_block_ms() const { return p_->solve_block_ms; }
+double Numeric::last_solve_block_top_ms() const { return p_->solve_block_top_ms; }
 bool Numeric::solve_device(int nrhs, double* drhs, int ld) { return p_->solve_device(nrhs, drhs, ld, drhs, ld, true); }
 bool Numeric::solve_device2(int nrhs, const double* db, int ldb, double* dx, int ldx) { return p_->solve_device(nrhs, db, ldb, dx, ldx, true); }
 void Numeric::set_pivtol(double u) { if (u != p_->opt.pivtol) p_->scale_valid = false; p_->opt.pivtol = u; }      // (IncreaseQuality: the scaling is computed afresh, as MA97's rescale)

@@ -73,6 +73,7 @@ ABI_SYMBOLS = [
     "mi355x_kkt_comm_unique_id", "mi355x_kkt_set_comm_rccl", "mi355x_kkt_comm_shm_id", "mi355x_kkt_comm_shm_discard", "mi355x_kkt_set_comm_shm", "mi355x_kkt_set_comm_callbacks", "mi355x_kkt_set_comm_range_callback", "mi355x_kkt_exchange_bytes", "mi355x_kkt_comm_plan", "mi355x_kkt_comm_info",
     "mi355x_kkt_set_scaling", "mi355x_kkt_get_scaling", "mi355x_kkt_ruiz_scaling", "mi355x_kkt_matching_scaling", "mi355x_kkt_zero_pivots", "mi355x_kkt_failed_pivots", "mi355x_kkt_delay_columns", "mi355x_kkt_set_delay_rounds", "mi355x_kkt_assembly_define", "mi355x_kkt_assembly_buffer", "mi355x_kkt_assembly_upload", "mi355x_kkt_factor_assembled",
     "mi355x_kkt_pd_define", "mi355x_kkt_pd_put_data", "mi355x_kkt_pd_put", "mi355x_kkt_pd_get", "mi355x_kkt_pd_solve_once", "mi355x_kkt_pd_residual",
+    "mi355x_kkt_set_solve_block", "mi355x_kkt_solve_block_info",
     "mi355x_kkt_lowrank_set", "mi355x_kkt_lowrank_update", "mi355x_kkt_lowrank_solve", "mi355x_kkt_lowrank_solve_device2", "mi355x_kkt_lowrank_clear", "mi355x_kkt_lowrank_info",
     "mi355x_kkt_lbfgs_define", "mi355x_kkt_lbfgs_push", "mi355x_kkt_lbfgs_push_device", "mi355x_kkt_lbfgs_reset", "mi355x_kkt_lbfgs_clear", "mi355x_kkt_lbfgs_info", "mi355x_kkt_lbfgs_get", "mi355x_kkt_lbfgs_coefficients",
     "mi355x_kkt_lbfgs_define_sr1", "mi355x_kkt_lbfgs_undo", "mi355x_kkt_lbfgs_sr1_info", "mi355x_kkt_lbfgs_sr1_coefficients",
@@ -153,6 +154,8 @@ def load_library():
     lib.mi355x_kkt_lowrank_update.argtypes = [vp, ip]
     lib.mi355x_kkt_lowrank_solve.argtypes = [vp, C.c_int, vp, C.c_int]
     lib.mi355x_kkt_lowrank_solve_device2.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int]
+    lib.mi355x_kkt_set_solve_block.argtypes = [vp, C.c_int]
+    lib.mi355x_kkt_solve_block_info.argtypes = [vp] + [C.POINTER(C.c_int)] * 6 + [C.POINTER(C.c_double)]
     lib.mi355x_kkt_lowrank_clear.argtypes = [vp]
     lib.mi355x_kkt_lowrank_info.argtypes = [vp, ip, ip, ip, ip, dp]
     lib.mi355x_kkt_lbfgs_define.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]
@@ -465,6 +468,19 @@ class KKTSolver:
         if self.lib.mi355x_kkt_lowrank_info(self._h, C.byref(r), C.byref(v), C.byref(u), C.byref(c), C.byref(ms)) != 0:
             raise KKTError("lowrank_info: " + self.last_error())
         return {"rows": r.value, "nv": v.value, "nu": u.value, "current": bool(c.value), "update_ms": ms.value}
+
+    # --- blocks of right-hand sides in the solves (include/mi355x_kkt.h mi355x_kkt_set_solve_block): opt-in, single-GPU handles ---
+    def set_solve_block(self, on) -> None:
+        """on: solve calls with nrhs >= 2 take their right-hand sides through the tree SOLVE_BLOCK at a time (same bits per column as a solve of its own)."""
+        if self.lib.mi355x_kkt_set_solve_block(self._h, 1 if on else 0) != 0:
+            raise KKTError("set_solve_block: " + self.last_error())
+
+    def solve_block_info(self) -> dict:
+        o, w, lv, nb, nc, nt, ms = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_double(0.0)
+        if self.lib.mi355x_kkt_solve_block_info(self._h, C.byref(o), C.byref(w), C.byref(lv), C.byref(nb), C.byref(nc), C.byref(nt), C.byref(ms)) != 0:
+            raise KKTError("solve_block_info: " + self.last_error())
+        return {"on": bool(o.value), "width": w.value, "first_top_level": lv.value, "blocked_launches": nb.value, "bycol_launches": nc.value,
+                "top_launches_per_column": nt.value, "last_ms": ms.value}
 
     # --- the row map (the reference's P_LowRank): row i of V, U, S, Y, DR is the caller's index idx[i] ---
     def lowrank_rowmap(self, idx):
